@@ -3,8 +3,18 @@
 Msamples/s (width x height x spp / s) at 1920x1080 on scenes/cornell (Lambert + area light),
 1024 spp, plus the achieved algorithmic HBM GB/s of the render kernel against the gfx950 peak.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--width X --height Y]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--width X --height Y] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline line needs: set up, warm up, time K steps, write the outputs
+(--dump-outputs) and print the line.  Everything else it can measure or check -- the CPU baselines, the
+merged-frame check and the extra weak-scaling and config-5 runs of N > 1 -- runs only with --full.
+
+--dump-outputs DIR writes what the last timed step computed, the framebuffer a caller receives, as
+DIR/framebuffer.npy (float32 [height, width, 4]; with N > 1 the frame merged on rank 0).  A frame of more
+than 64 MB is written as a fixed, seeded sample of its pixels instead: DIR/framebuffer_sample.npy
+(float32 [k, 4]) and DIR/framebuffer_sample_index.npy (float64 [k], row-major pixel indices).  The inputs
+(scene, camera, seed table) depend on the arguments only, so two builds can be compared output for output.
 
 A *step* is one complete render of the workload: reset, then frame-synchronous segments until
 every pixel has finished its S-th path (the reference's "N spp" in its own work accounting,
@@ -12,7 +22,7 @@ SURVEY.md s8d).  Inputs (scene, BVH, camera, seed table) are resident in HBM bef
 region.  With N > 1 the frame is split into interleaved row blocks, one set per rank (pixels are
 independent; seeds use global pixel coordinates, so the union is bit-identical to the 1-GPU
 image of that frame), and ONE RCCL collective per step -- a gather of every rank's rows to rank 0 --
-puts the framebuffer together there, inside the timed region.  By default rank 0 then renders
+puts the framebuffer together there, inside the timed region.  With --full rank 0 then renders
 the whole frame alone (untimed) and the JSON line says whether the merged frame equals it bit for bit.
 
 Scaling.  The N-GPU line is BASELINE's own frame: the FIXED 1920x1080 x 1024 spp frame of config 2 split N ways (strong scaling;
@@ -21,9 +31,9 @@ the merged frame checked against the one GPU's.  That stops scaling early for a 
 frame is 32 400 waves of pixels, one MI355X holds 6 144, so from N = 4 on a rank's share is one round of waves and its run time the
 sequential chain of its slowest pixel (spp x path length segments, one after the other), not work / N.  Pixels are independent
 units, so the path shards with no data-path exchange and its WEAK scaling -- fixed work per GPU: the same view with N x the pixels
-(both dimensions x sqrt(N): 2720x1530, 3840x2160, 5424x3051; same camera and spp, hence the same cost per pixel) -- rides along as
-the sub-record `weak` (one step).  `--scaling weak` makes that the headline line instead (its `metric` then names the bigger
-frame).  With N = 8 the run adds BASELINE config 5 -- the 871 k-triangle stand-in at 3840x2160, 8-way split -- as `config5`, verified.
+(both dimensions x sqrt(N): 2720x1530, 3840x2160, 5424x3051; same camera and spp, hence the same cost per pixel) -- rides along
+with --full as the sub-record `weak` (one step).  `--scaling weak` makes that the headline line instead (its `metric` then names the
+bigger frame).  With N = 8, --full adds BASELINE config 5 -- the 871 k-triangle stand-in at 3840x2160, 8-way split -- as `config5`, verified.
 
 The JSON line also carries
   roofline      the dominant kernel (render_kernel) priced in ALGORITHMIC bytes: 240 B per pixel
@@ -41,7 +51,7 @@ The JSON line also carries
                 (PMC passes of the same workload, profiles/r04_pmc_render_kernel.json) and, from this
                 run's segment rate, the share of the chip's vector issue slots they take.
   cpu_baseline  oracle/pt_oracle.c (a scalar-per-pixel CPU port, multi-threaded over pixels) on a
-                bounded sample of the same workload, rank 0, N = 1 only.
+                bounded sample of the same workload, rank 0, N = 1 only (--full).
 """
 import argparse
 import importlib
@@ -56,10 +66,27 @@ PKG_NAME = "photorealistic-rendering-using-opencl_amd"
 
 ALGO_BYTES_PER_SEGMENT = 240
 HBM_PEAK_GBPS = 8000.0                # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: at most this much in all
 
 
-def run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, scene_name, base_w, base_h, spp, env_name, phase, scaling, steps, warmup, verify):
-    """times `steps` renders of one workload on this rank's share of the frame; returns the measurements (rank 0: all of them)"""
+def dump_outputs(np, out_dir, frame):
+    """--dump-outputs: the framebuffer of the last timed step, whole, or a fixed seeded sample of its pixels when it is too big"""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "framebuffer.npy"), frame)
+        return
+    pixels = frame.reshape(-1, frame.shape[-1])
+    k = DUMP_LIMIT_BYTES // 2 // (pixels.shape[1] * 4 + 8)
+    index = np.sort(np.random.default_rng(12345).choice(pixels.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "framebuffer_sample.npy"), pixels[index])
+    np.save(os.path.join(out_dir, "framebuffer_sample_index.npy"), index.astype(np.float64))
+
+
+def run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, scene_name, base_w, base_h, spp, env_name, phase, scaling, steps, warmup, verify,
+                 dump_dir=None):
+    """times `steps` renders of one workload on this rank's share of the frame; returns the measurements (rank 0: all of them);
+    with `dump_dir`, rank 0 writes the frame of the last timed step there"""
     W, H = base_w, base_h
     if world > 1 and scaling == "weak":
         W = int(round(base_w * world ** 0.5 / 16.0)) * 16
@@ -127,6 +154,8 @@ def run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, scene_na
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if dump_dir and rank == 0:
+        dump_outputs(np, dump_dir, r.read_framebuffer() if world == 1 else merged[0].cpu().numpy())
 
     verified = None
     if verify and world > 1:
@@ -151,9 +180,8 @@ def run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, scene_na
         dist.all_reduce(seg, op=dist.ReduceOp.SUM)
     r.close()
     torch.cuda.set_stream(torch.cuda.default_stream())
-    steps_ = max(steps, 1)
     own_segments = float(counts.segments)
-    return {"W": W, "H": H, "spp": spp, "dt": dt, "msamples": W * H * spp * steps_ / dt / 1e6, "ms_per_step": dt / steps_ * 1e3,
+    return {"W": W, "H": H, "spp": spp, "dt": dt, "msamples": W * H * spp * steps / dt / 1e6, "ms_per_step": dt / steps * 1e3,
             "total_segments": float(seg[0]), "total_samples": float(seg[1]), "own_segments": own_segments, "verified": verified,
             "kernel_ms": m["kernel_ms"], "kernel_sum_ms": m["kernel_sum_ms"], "launches": m["launches"], "concurrent": m["concurrent"],
             "max_bounces": cfg.max_bounces, "variant": variant}
@@ -179,7 +207,14 @@ def main():
                     help="N > 1: skip the check that rank 0's merged frame equals, bit for bit, the frame one GPU renders alone")
     ap.add_argument("--config5-spp", type=int, default=256,
                     help="N = 8 only: spp of the extra BASELINE config 5 run (871 k-triangle stand-in, 3840x2160, 8-way split); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the framebuffer of the last one as DIR/framebuffer.npy (float32; a seeded sample above 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baselines (N = 1), and with N > 1 the merged-frame check, "
+                         "the weak-scaling run and the config-5 run")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -226,23 +261,23 @@ def main():
     prt = importlib.import_module(PKG_NAME)
     par = importlib.import_module(PKG_NAME + ".parallel")
 
-    verify = world > 1 and not a.no_verify
+    verify = a.full and world > 1 and not a.no_verify
     res = run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, a.scene, a.width, a.height, a.spp, a.env, a.phase,
-                       a.scaling, a.steps, a.warmup, verify)
+                       a.scaling, a.steps, a.warmup, verify, dump_dir=a.dump_outputs)
     # beside the line of BASELINE's frame: the other kind of scaling, one step
     res_other = None
-    if world > 1 and not a.no_weak:
+    if a.full and world > 1 and not a.no_weak:
         res_other = run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, a.scene, a.width, a.height, a.spp, a.env, a.phase,
                                  "weak" if a.scaling == "strong" else "strong", 1, 1, False)
     # BASELINE config 5 is defined on 8 GPUs: the 871 k-triangle stand-in at 3840x2160, 8-way tile split + framebuffer merge
     res5 = None
-    if (world == 8 or (world > 1 and os.environ.get("PRT_BENCH_CONFIG5") == "1")) and a.config5_spp > 0 and a.scene == "cornell_diffuse.json":
+    if a.full and (world == 8 or (world > 1 and os.environ.get("PRT_BENCH_CONFIG5") == "1")) and a.config5_spp > 0 and a.scene == "cornell_diffuse.json":
         res5 = run_workload(prt, par, torch, dist, np, a, world, rank, local_rank, "cornell_dragon.json", 3840, 2160, a.config5_spp, "", "isotropic",
                             "strong", 1, 1, verify)
 
     if rank == 0:
         W, H, spp = res["W"], res["H"], res["spp"]
-        steps = max(a.steps, 1)
+        steps = a.steps
         kernel_ms, kernel_sum_ms, launches, concurrent = res["kernel_ms"], res["kernel_sum_ms"], res["launches"], res["concurrent"]
         total_segments, total_samples, own_segments = res["total_segments"], res["total_samples"], res["own_segments"]
         # rank-0 kernel: its own segments per step over its own kernel time
@@ -328,7 +363,7 @@ def main():
                               "mean_path_length": round(res5["total_segments"] / max(res5["total_samples"], 1.0), 4),
                               "gsegments_per_s_all_gpus": round(res5["total_segments"] / (res5["dt"]) / 1e9, 4),
                               "merged_frame_equals_single_gpu_render": res5["verified"]}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prt, a)
             ref = cpu_reference_build(prt, a)
             if ref is not None:

@@ -1179,11 +1179,11 @@ def test_device_functions_match_reference_kat(prt):
 
 
 def test_bench_line_keeps_the_contract(prt):
-    """`python bench.py` as the driver runs it (fewer spp): ONE JSON line with the contract's keys, the roofline and the CPU baseline"""
+    """`python bench.py --full` as the driver runs it (fewer spp): ONE JSON line with the contract's keys, the roofline and the CPU baseline"""
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "16"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "16", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.split("\n") if l.startswith("{")]
@@ -1204,3 +1204,31 @@ def test_bench_line_keeps_the_contract(prt):
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in c, key
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and c["cores"] >= 1
+
+
+def test_plain_bench_run_is_lean_and_dumps_what_it_timed(prt, oracle, tmp_path):
+    """`python bench.py` without --full: the headline line (no CPU baseline), `steps` timed steps, and --dump-outputs writes the
+    framebuffer of the last timed step -- the same bits the oracle renders from the same inputs"""
+    import json
+    import subprocess
+    import sys
+    W, H, spp = 64, 48, 8
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", str(spp),
+                          "--width", str(W), "--height", str(H), "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.split("\n") if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in j, key
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert "cpu_baseline" not in j and "cpu_reference_build" not in j
+    assert abs(j["value"] - W * H * spp / (j["ms_per_step"] * 1e-3) / 1e6) <= 1e-2 * j["value"]
+    img = np.load(str(tmp_path / "framebuffer.npy"))
+    assert img.dtype == np.float32 and img.shape == (H, W, 4)
+    scene = prt.HostScene("cornell_diffuse.json")
+    cfg = scene.config()
+    seeds = prt.seed_pairs(max(64, spp * max(cfg.max_bounces, 8) + 64))
+    _, oimg = oracle.Restatement().render(cfg, scene.desc, prt.default_camera(W, H), W, H, seeds, spp_limit=spp, threads=4)
+    assert oracle.images_equal(oimg, img), "the dumped framebuffer is not the oracle's render of the benchmark's inputs"

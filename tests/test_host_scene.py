@@ -271,13 +271,27 @@ def test_obj_without_normals_gets_smooth_normals(prt, tmp_path):
     assert np.allclose(tri[2, :, 3:], [[0, 0, 1]] * 3) and np.allclose(tri[3, :, 3:], [[0, 0, -1]] * 3)    # no smoothing across 180 degrees
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/resources/models/teapot.obj"), reason="reference not present")
 def test_committed_teapot_soup_is_the_reference_obj(prt, tmp_path):
-    lib = prt.load_library()
-    err = C.create_string_buffer(256)
-    out = tmp_path / "t.prtmesh"
-    assert lib.prth_convert_model(b"/root/reference/resources/models/teapot.obj", str(out).encode(), err, 256) == 0
-    assert out.read_bytes() == open(os.path.join(prt.MODELS_DIR, "teapot.prtmesh"), "rb").read()
+    """the committed soup is the one converted from the reference's OBJ, whose digests tests/golden/teapot_provenance.json records;
+    where the reference checkout is present (the one oracle/ref/build_ref.py builds from), its OBJ must be the file on record and
+    convert to the committed soup byte for byte"""
+    import hashlib
+    import importlib.util
+    import json
+    rec = json.load(open(os.path.join(GOLDEN, "teapot_provenance.json")))
+    soup = open(os.path.join(ROOT, rec["prtmesh"]), "rb").read()
+    assert hashlib.sha256(soup).hexdigest() == rec["prtmesh_sha256"]
+    spec = importlib.util.spec_from_file_location("_build_ref", os.path.join(ROOT, "oracle", "ref", "build_ref.py"))
+    recipe = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(recipe)
+    obj = os.path.join(recipe.REF, rec["obj"])
+    if os.path.exists(obj):
+        assert hashlib.sha256(open(obj, "rb").read()).hexdigest() == rec["obj_sha256"]
+        lib = prt.load_library()
+        err = C.create_string_buffer(256)
+        out = tmp_path / "t.prtmesh"
+        assert lib.prth_convert_model(obj.encode(), str(out).encode(), err, 256) == 0
+        assert out.read_bytes() == soup
 
 
 def test_malformed_scene_is_an_error_not_a_crash(prt):

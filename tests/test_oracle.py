@@ -1,6 +1,10 @@
 """The CPU oracle (oracle/pt_oracle.c) against the golden fixtures produced by the reference
 build, against the reference build itself where it is present (development container), and
-through size-independent properties."""
+through size-independent properties.  The tests that compare with the reference build on inputs of
+their own find its outputs in tests/golden/ref_checks.json (digests of the exact bits) and
+tests/golden/ref_libm_images.npz (tests/golden/make_ref_checks.py)."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -15,6 +19,63 @@ def setup(prt, variant, W, H):
     cfg = variant_config(scene, variant)
     cfg.phase_function = phase
     return scene, cfg, variant_camera(prt, variant, W, H), (prt.make_sky(64, 32) if use_env else None)
+
+
+REF_CHECKS = os.path.join(GOLDEN, "ref_checks.json")
+REF_LIBM_IMAGES = os.path.join(GOLDEN, "ref_libm_images.npz")
+EQUALS_SIZE, EQUALS_FRAMES, EQUALS_CAMERA = (45, 27), 70, (-0.3, 0.15, -0.1)      # (d_yaw, d_pitch, d_radius) of the orbit camera
+DRAGON_SIZE, DRAGON_FRAMES = (40, 24), 40
+NAN_SLABS_SIZE, NAN_SLABS_FRAMES = (33, 21), 60
+LIBM_SIZE, LIBM_FRAMES = 48, 768
+
+
+def _digest(bits):
+    bits = np.ascontiguousarray(bits)
+    return hashlib.sha256(("%s %s " % (bits.dtype.str, bits.shape)).encode() + bits.tobytes()).hexdigest()
+
+
+def output_digests(oracle, state, img):
+    """SHA-256 of exactly the bits oracle.state_fields_equal (per field) and oracle.images_equal compare"""
+    fields = {}
+    for f in oracle.STATE_FIELDS:
+        x = state[f]
+        if f in ("origin", "dir", "mask"):
+            x = x[..., :3]
+        fields[f] = _digest(oracle.float_bits(x) if x.dtype.kind == "f" else x)
+    return {"state": fields, "image": _digest(oracle.float_bits(img))}
+
+
+def assert_reference_outputs(oracle, key, state, img):
+    """the restatement's (state, image) are, bit for bit, what the reference build left for the inputs of `key`"""
+    want = json.load(open(REF_CHECKS))[key]
+    got = output_digests(oracle, state, img)
+    assert [f for f in oracle.STATE_FIELDS if got["state"][f] != want["state"][f]] == []
+    assert got["image"] == want["image"]
+
+
+def equals_inputs(prt, variant):
+    """different size / frame count / camera than the goldens"""
+    W, H = EQUALS_SIZE
+    scene, cfg, _, env = setup(prt, variant, W, H)
+    d_yaw, d_pitch, d_radius = EQUALS_CAMERA
+    return scene, cfg, prt.orbit_camera(W, H, d_yaw=d_yaw, d_pitch=d_pitch, d_radius=d_radius), env, prt.seed_pairs(EQUALS_FRAMES)
+
+
+def dragon_inputs(prt):
+    prt.ensure_dragon_standin()
+    scene = prt.HostScene("cornell_dragon.json")
+    return scene, scene.config(), prt.default_camera(*DRAGON_SIZE), prt.seed_pairs(DRAGON_FRAMES)
+
+
+def nan_slabs_inputs(prt):
+    W, H = NAN_SLABS_SIZE
+    scene, cfg, _, env = setup(prt, "cornell_coat", W, H)
+    return scene, cfg, prt.orbit_camera(W, H, d_aperture=-1.0), env, prt.seed_pairs(NAN_SLABS_FRAMES)   # apertureRadius clamps to 0: pinhole
+
+
+def libm_inputs(prt, std):
+    scene, cfg, _, env = setup(prt, std, LIBM_SIZE, LIBM_SIZE)
+    return scene, cfg, prt.default_camera(LIBM_SIZE, LIBM_SIZE), env, prt.seed_pairs(LIBM_FRAMES)
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS) + ["cornell_diffuse_spp"])
@@ -47,17 +108,17 @@ def test_oracle_debug_views_reproduce_reference_golden(prt, oracle, fixture):
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_oracle_equals_reference_build(prt, oracle, variant):
-    """different size / frame count / camera than the goldens, straight against oracle/_ref"""
-    if not oracle.ref_available(variant):
-        pytest.skip("oracle/_ref not built (only possible where /root/reference exists)")
-    W, H, frames = 45, 27, 70
-    scene, cfg, cam, env = setup(prt, variant, W, H)
-    cam = prt.orbit_camera(W, H, d_yaw=-0.3, d_pitch=0.15, d_radius=-0.1)
-    seeds = prt.seed_pairs(frames)
-    rstate, rimg = oracle.RefOracle(variant).render(scene.desc, bytes(cam), W, H, seeds, env=env, threads=4)
+    """different size / frame count / camera than the goldens, against the reference build's outputs for these inputs, and
+    straight against oracle/_ref where it is built"""
+    W, H = EQUALS_SIZE
+    scene, cfg, cam, env, seeds = equals_inputs(prt, variant)
     state, img = oracle.Restatement().render(cfg, scene.desc, cam, W, H, seeds, env=env, threads=4)
-    assert oracle.state_fields_equal(rstate, state) == []
-    assert oracle.images_equal(rimg, img)
+    assert tuple(json.load(open(REF_CHECKS))["equals_camera"]) == EQUALS_CAMERA     # the fixture was made for this camera
+    assert_reference_outputs(oracle, "equals/" + variant, state, img)
+    if oracle.ref_available(variant):
+        rstate, rimg = oracle.RefOracle(variant).render(scene.desc, bytes(cam), W, H, seeds, env=env, threads=4)
+        assert oracle.state_fields_equal(rstate, state) == []
+        assert oracle.images_equal(rimg, img)
 
 
 def test_reference_shadow_stack_never_needed_more_than_eight(prt, oracle):
@@ -111,34 +172,30 @@ def test_spp_rule_properties(prt, oracle):
 def test_dragon_standin_oracle_equals_reference_build(prt, oracle):
     """config 5 geometry (871 k triangles, tree depth 23): needs any-hit stack depths > 8, where the
     unpatched reference is undefined; the reference build runs with the raised stack"""
-    if not oracle.ref_available("cornell_diffuse"):
-        pytest.skip("oracle/_ref not built")
-    prt.ensure_dragon_standin()
-    W, H, frames = 40, 24, 40
-    scene = prt.HostScene("cornell_dragon.json")
+    W, H = DRAGON_SIZE
+    scene, cfg, cam, seeds = dragon_inputs(prt)
     assert scene.desc.triangle_count == 871200
-    cfg, cam, seeds = scene.config(), prt.default_camera(W, H), prt.seed_pairs(frames)
-    rstate, rimg = oracle.RefOracle("cornell_diffuse").render(scene.desc, bytes(cam), W, H, seeds, threads=8)   # same specialisation: LIGHT|DIFF
     rs = oracle.Restatement()
     state, img = rs.render(cfg, scene.desc, cam, W, H, seeds, threads=8)
-    assert oracle.state_fields_equal(rstate, state) == [] and oracle.images_equal(rimg, img)
+    assert_reference_outputs(oracle, "dragon", state, img)
     assert rs.last_diag[1] > 8          # the any-hit stack really goes deeper than the reference's 8 entries
+    if oracle.ref_available("cornell_diffuse"):
+        rstate, rimg = oracle.RefOracle("cornell_diffuse").render(scene.desc, bytes(cam), W, H, seeds, threads=8)   # same specialisation: LIGHT|DIFF
+        assert oracle.state_fields_equal(rstate, state) == [] and oracle.images_equal(rimg, img)
 
 
 def test_axis_parallel_rays_nan_slabs(prt, oracle):
     """pinhole camera + odd width: the centre column has dir.x == 0 and origin.x == 0 exactly, so the slab test
     (bvh.cl:4-9) produces inf and NaN (0 * inf) in every node -- fmin/fmax must ignore the NaN operand exactly as
     the reference build does"""
-    if not oracle.ref_available("cornell_coat"):
-        pytest.skip("oracle/_ref not built")
-    W, H, frames = 33, 21, 60
-    scene, cfg, _, env = setup(prt, "cornell_coat", W, H)
-    cam = prt.orbit_camera(W, H, d_aperture=-1.0)                          # apertureRadius clamps to 0: pinhole
+    W, H = NAN_SLABS_SIZE
+    scene, cfg, cam, env, seeds = nan_slabs_inputs(prt)
     assert cam.apertureRadius == 0.0 and cam.view[0] == 0.0 and cam.position[0] == 0.0
-    seeds = prt.seed_pairs(frames)
-    rstate, rimg = oracle.RefOracle("cornell_coat").render(scene.desc, bytes(cam), W, H, seeds, threads=4)
     state, img = oracle.Restatement().render(cfg, scene.desc, cam, W, H, seeds, threads=4)
-    assert oracle.state_fields_equal(rstate, state) == [] and oracle.images_equal(rimg, img)
+    assert_reference_outputs(oracle, "nan_slabs", state, img)
+    if oracle.ref_available("cornell_coat"):
+        rstate, rimg = oracle.RefOracle("cornell_coat").render(scene.desc, bytes(cam), W, H, seeds, threads=4)
+        assert oracle.state_fields_equal(rstate, state) == [] and oracle.images_equal(rimg, img)
     # premise (by construction, camera.cl:26-52): view.x = up.x = position.x = 0 -> hAxis = (+-1,0,0), vAxis.x = 0,
     # and at x = (W-1)/2 the factor 2*sx-1 is exactly 0, so origin.x = dir.x = 0 for the whole centre column
 
@@ -152,19 +209,18 @@ def test_reference_build_with_glibc_math_agrees_as_an_estimate(prt, oracle, std,
     """The reference's kernel text linked against TWO built-in libraries: include/prt_detmath.h (the stated one, shared by the restatement
     and the HIP kernels) and, for the scalar transcendentals, the GNU C library's libm (oracle/ref/build_ref.py --math libm) -- math this
     repository did not write.  Individual pixels part ways at the first decision an ulp flips; the ESTIMATE must not move: image means
-    within the Monte-Carlo error of their difference (full-length run: tools/independent_math.py -> profiles/r03_independent_math.txt)."""
-    if not (oracle.ref_available(std) and oracle.ref_available(libm)):
-        pytest.skip("reference build not present (development container only)")
-    size, frames = 48, 768
-    scene = prt.HostScene(VARIANTS[std][0])
-    cam = prt.default_camera(size, size)
-    seeds = prt.seed_pairs(frames)
-    env = prt.make_sky(64, 32) if use_env else None
-    imgs = []
-    for name in (std, libm):
-        _, img = oracle.RefOracle(name).render(scene.desc, bytes(cam), size, size, seeds, env=env, threads=8)
-        imgs.append(img.astype(np.float64)[..., :3])
-    a, b = imgs
+    within the Monte-Carlo error of their difference (full-length run: tools/independent_math.py -> profiles/r03_independent_math.txt).
+    The include/prt_detmath.h side is rendered by the restatement, which is the reference build with that library bit for bit
+    (test_oracle_equals_reference_build); the libm side is the libm build's image for these inputs in tests/golden/ref_libm_images.npz."""
+    size = LIBM_SIZE
+    scene, cfg, cam, env, seeds = libm_inputs(prt, std)
+    assert cfg.phase_function == phase and (env is not None) == use_env
+    _, std_img = oracle.Restatement().render(cfg, scene.desc, cam, size, size, seeds, env=env, threads=8)
+    libm_img = np.load(REF_LIBM_IMAGES)[libm]
+    if oracle.ref_available(std) and oracle.ref_available(libm):
+        assert oracle.images_equal(oracle.RefOracle(std).render(scene.desc, bytes(cam), size, size, seeds, env=env, threads=8)[1], std_img)
+        assert oracle.images_equal(oracle.RefOracle(libm).render(scene.desc, bytes(cam), size, size, seeds, env=env, threads=8)[1], libm_img)
+    a, b = (img.astype(np.float64)[..., :3] for img in (std_img, libm_img))
     finite = np.isfinite(a).all(axis=2) & np.isfinite(b).all(axis=2)
     assert finite.mean() > 0.8                                # (the reference leaves NaN in some pixels of the medium scenes: 0 * inf in a weight)
     same = ((a == b) | ~finite[..., None]).all(axis=2).mean()
