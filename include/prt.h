@@ -176,6 +176,45 @@ int prt_render_frames(prt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, con
 int prt_render_spp(prt_ctx* ctx, uint32_t spp, uint32_t max_frames, const int32_t* seed_pairs,
                    uint32_t* frames_used);
 
+/* Adaptive sampling (no counterpart in the reference): "N spp" with a per-pixel N.  Frames 1, 2, ... as prt_render_spp (same
+ * preconditions: a freshly reset context -- PRT_ERR_NOT_READY otherwise --, seed_pairs for max_frames frames, PRT_ERR_NOT_READY when max_frames
+ * runs out with pixels unfrozen, each of them then having done exactly max_frames frames), under this freeze rule:
+ *
+ *   Per pixel a plane {l, s2} (8 bytes, allocated on first use, zeroed by prt_reset / prt_resize / prt_set_tile / prt_set_row_blocks) is
+ *   updated at the end of every path (a segment that leaves reset set), after the accumulate of acc (kernels/main.cl:142).  f32 operations,
+ *   left to right, no contraction:
+ *       lum = 0.2126f*acc.x + 0.7152f*acc.y + 0.0722f*acc.z;   y = lum - l;   s2 = s2 + y*y;   l = lum
+ *   At that path end, with n = samples >= min_spp, the pixel is judged (IEEE division):
+ *       m = l / n;   v = fmaxf((s2 - l*m) / ((float)n * (float)(n - 1)), 0);   t = rel_err * fmaxf(m, abs_floor);   converged = v < t*t
+ *   (v is clamped because the difference can round below zero when every path brought the same luminance; strict: rel_err = 0 never
+ *   converges).  The pixel freezes when reset && (samples >= max_spp || converged).  The converged bit lives in
+ *   the device state between launches (bit 31 of the state word that also holds reset); prt_read_state and the RTD layout do not show it --
+ *   a frozen pixel with samples < max_spp was frozen by convergence.
+ *
+ * A pixel frozen after k paths is bit-identical (path state and framebuffer) to the same pixel of prt_render_spp(k).  Refused: min_spp < 2,
+ * max_spp < min_spp, rel_err or abs_floor negative or NaN (PRT_ERR_INVALID_ARGUMENT); a debug view (PRT_ERR_UNSUPPORTED: it overwrites acc).
+ * Once fewer than a fraction of the frame's pixels are live, the launches run over a list of the live pixels packed 64 to a wave (option
+ * "compact"); run-ahead and pacing apply as in prt_render_spp, the tile order and the ray pool do not. */
+typedef struct prt_adaptive {
+    uint32_t min_spp;     /* >= 2 */
+    uint32_t max_spp;     /* >= min_spp */
+    float rel_err;        /* target relative standard error of the pixel's mean luminance; 0 = never converge (pure max_spp) */
+    float abs_floor;      /* mean luminance below which the error is judged absolutely (dark pixels) */
+} prt_adaptive;
+int prt_render_adaptive(prt_ctx* ctx, const prt_adaptive* a, uint32_t max_frames, const int32_t* seed_pairs, uint32_t* frames_used);
+/* the plane {l, s2} per pixel, framebuffer order (2 floats per pixel; zeros before the first adaptive render of a reset context) */
+int prt_read_adaptive_stats(prt_ctx* ctx, float* out2);
+/* what the last prt_render_adaptive did with its launches */
+typedef struct prt_adaptive_report {
+    uint32_t tile_launches;      /* launches over tiles (or scattered pixels) */
+    uint32_t list_launches;      /* launches over a live-pixel list */
+    uint32_t list_builds;        /* lists built */
+    uint32_t _pad;
+    uint64_t list_lanes;         /* lanes of the list launches' waves (64 per wave) */
+    uint64_t list_live_lanes;    /* ... that held a pixel still live when its launch was issued */
+} prt_adaptive_report;
+int prt_get_adaptive_report(prt_ctx* ctx, prt_adaptive_report* out);
+
 /* Scheduling knob of the render kernel (no counterpart in the reference; results do not depend on it, tests check
  * that): a wave ends a BVH-walk phase once fewer than `lanes` of its 64 lanes are still walking (and fewer than wait for the
  * phase to end); the lanes cut off resume in the wave's next phase.  1 = every walk runs to its end (lock step).
@@ -211,6 +250,9 @@ int prt_set_walk_min_lanes(prt_ctx* ctx, uint32_t lanes);
  *                               with more waves of fewer pixels: a wave lasts as long as the slowest of its pixels' chains of segments
  *   "pool"              0 | 1   1: render_kernel_rp (csrc/hip/pt_pool.h): workgroups of shading waves that post the rays that go deeper than the root
  *                               of the tree to walker waves through LDS.  Bit-exact, measured slower than the default kernel: off
+ *   "compact"           1 | 0   prt_render_adaptive: list launches once few pixels are live (see there); 0: tiles to the end
+ *   "compact_below"     0 .. 100   ... once fewer than this percentage of the frame's pixels are live (default 50); a list is rebuilt
+ *                               once its live pixels have fallen below half of it
  *   "test_drop_report"  0 | 1   tests only: the launches of prt_render_spp report their unfinished pixels into a spare word, so that the
  *                               call sees a launch end without a report (PRT_ERR_HIP, state unusable until prt_reset) */
 int prt_set_option(prt_ctx* ctx, const char* name, int value);

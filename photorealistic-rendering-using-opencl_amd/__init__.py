@@ -15,14 +15,14 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
+from ._capi import Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -155,6 +155,28 @@ def orbit_camera(width, height, fovx=45.0, d_yaw=0.0, d_pitch=0.0, d_radius=0.0,
     return cam
 
 
+def adaptive_luminance(acc):
+    """the luminance prt_render_adaptive keeps per pixel (prt.h): 0.2126 r + 0.7152 g + 0.0722 b in float32, left to right, of acc [..., >= 3]"""
+    acc = np.asarray(acc, dtype=np.float32)
+    return (np.float32(0.2126) * acc[..., 0] + np.float32(0.7152) * acc[..., 1]) + np.float32(0.0722) * acc[..., 2]
+
+
+def adaptive_converged(l, s2, n, rel_err, abs_floor):
+    """the convergence test of prt_render_adaptive (prt.h), elementwise in numpy float32 with the device's operations in the device's order:
+    m = l / n; v = max((s2 - l m) / (n (n - 1)), 0); t = rel_err max(m, abs_floor); converged = v < t^2.  l, s2: the plane of read_adaptive_stats();
+    n: paths (samples >= 2).  Returns (converged, standard error of the mean = sqrt(v), mean luminance m) -- the last two for error maps."""
+    f = np.float32
+    l = np.asarray(l, dtype=f)
+    s2 = np.asarray(s2, dtype=f)
+    n = np.asarray(n, dtype=np.uint32)
+    nf = n.astype(f)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = l / nf
+        v = np.fmax((s2 - l * m) / (nf * (n - np.uint32(1)).astype(f)), f(0))
+        t = f(rel_err) * np.fmax(m, f(abs_floor))
+        return v < t * t, np.sqrt(v), m
+
+
 def seed_pairs(n_frames, first_frame=1):
     """(random0, random1) per frame: the un-seeded glibc rand() stream of the reference host,
     two values consumed by initCLKernel first (src/main.cpp:226-227,301-302)."""
@@ -253,6 +275,27 @@ class Renderer:
         self._chk(self.lib.prt_render_spp(self.ctx, spp, len(seeds) // 2, seeds.ctypes.data_as(C.c_void_p), C.byref(used)),
                   "prt_render_spp")
         return used.value
+
+    def render_adaptive(self, seeds, min_spp, max_spp, rel_err, abs_floor=0.0):
+        """prt_render_adaptive: every pixel renders paths until its mean luminance is judged converged (at least min_spp, at most max_spp
+        paths; prt.h).  Returns the frames used."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        a = Adaptive(int(min_spp), int(max_spp), float(rel_err), float(abs_floor))
+        used = C.c_uint32(0)
+        self._chk(self.lib.prt_render_adaptive(self.ctx, C.byref(a), len(seeds) // 2, seeds.ctypes.data_as(C.c_void_p), C.byref(used)),
+                  "prt_render_adaptive")
+        return used.value
+
+    def read_adaptive_stats(self):
+        """the adaptive plane: float32 [rows * width, 2] = {l, s2} per pixel, framebuffer order"""
+        out = np.zeros((self.rows * self.width, 2), dtype=np.float32)
+        self._chk(self.lib.prt_read_adaptive_stats(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_adaptive_stats")
+        return out
+
+    def adaptive_report(self):
+        rep = AdaptiveReport()
+        self._chk(self.lib.prt_get_adaptive_report(self.ctx, C.byref(rep)), "prt_get_adaptive_report")
+        return rep
 
     def set_walk_min_lanes(self, lanes):
         self._chk(self.lib.prt_set_walk_min_lanes(self.ctx, int(lanes)), "prt_set_walk_min_lanes")

@@ -61,6 +61,15 @@ class Stats(C.Structure):
                 ("kernel_sum_ms", C.c_double), ("concurrent", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class Adaptive(C.Structure):
+    _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("rel_err", C.c_float), ("abs_floor", C.c_float)]
+
+
+class AdaptiveReport(C.Structure):
+    _fields_ = [("tile_launches", C.c_uint32), ("list_launches", C.c_uint32), ("list_builds", C.c_uint32), ("_pad", C.c_uint32),
+                ("list_lanes", C.c_uint64), ("list_live_lanes", C.c_uint64)]
+
+
 assert C.sizeof(Material) == 64 and C.sizeof(Mesh) == 256 and C.sizeof(BvhNode) == 36 and C.sizeof(Camera) == 80
 
 # numpy view of the 112-byte RTD (prt_path_state)
@@ -83,6 +92,9 @@ PRT_API = [
     ("prt_reset", C.c_int, [C.c_void_p]),
     ("prt_render_frames", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("prt_render_spp", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("prt_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("prt_read_adaptive_stats", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_get_adaptive_report", C.c_int, [C.c_void_p, C.POINTER(AdaptiveReport)]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("prt_kernel_variant", C.c_char_p, [C.c_void_p]),

@@ -92,6 +92,15 @@ struct prt_ctx {
     RenderLaunch last{};                           // what the last launch ran
     RenderLaunch last_sub[MAX_SUB] = {};           // ... per sub-part (their grids differ by up to one tile: so can the pixel mapping)
     std::string variant;                           // ... as text (prt_kernel_variant)
+    // prt_render_adaptive: the per-pixel plane {l, s2} and the live-pixel list (with ceil(npix / 64) + 1 words for the wave offsets and the
+    // count), allocated on first use with the frame's size, freed with the frame
+    float2* d_adapt = nullptr;
+    uint32_t* d_live = nullptr;
+    uint32_t* d_live_aux = nullptr;
+    bool fresh = false;                            // nothing rendered since prt_reset (or the frame's allocation)
+    int compact = 1;                               // option "compact": list launches once few pixels are live
+    int compact_below = 50;                        // option "compact_below": ... fewer than this percentage of the frame
+    prt_adaptive_report arep{};                    // what the last adaptive render did with its launches
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -174,6 +183,9 @@ static void free_frame(prt_ctx* c) {
     p = c->S.q3; free_dev(p); c->S.q3 = nullptr;
     p = c->S.q4; free_dev(p); c->S.q4 = nullptr;
     p = c->fb; free_dev(p); c->fb = nullptr;
+    p = c->d_adapt; free_dev(p); c->d_adapt = nullptr;
+    p = c->d_live; free_dev(p); c->d_live = nullptr;
+    p = c->d_live_aux; free_dev(p); c->d_live_aux = nullptr;
     for (int j = 0; j < prt_ctx::MAX_SUB; ++j) {
         p = c->d_tile_order[j]; free_dev(p); c->d_tile_order[j] = nullptr;
         p = c->d_tile_cost[j]; free_dev(p); c->d_tile_cost[j] = nullptr;
@@ -364,6 +376,8 @@ extern "C" int prt_reset(prt_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->S.q3, 0, c->npix * 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->S.q4, 0, c->npix * 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->fb, 0, c->npix * 16, c->stream));
+    if (c->d_adapt) HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, c->npix * sizeof(float2), c->stream));
+    c->fresh = true;
     return PRT_OK;
 }
 
@@ -401,6 +415,8 @@ static FrameArgs frame_args(prt_ctx* c, uint32_t first_frame, uint32_t n, const 
     fa.walk_min_lanes = c->walk_min_lanes;
     fa.shadow_min_lanes = c->shadow_min_lanes;
     fa.tri_sixteenths = c->tri_sixteenths;
+    fa.adapt = nullptr; fa.live = nullptr; fa.live_count = 0;             // (prt_render_adaptive sets them: every other launch is "N spp" / frame mode)
+    fa.min_spp = 0; fa.rel_err = 0.0f; fa.abs_floor = 0.0f;
     return fa;
 }
 
@@ -451,6 +467,7 @@ extern "C" int prt_render_frames(prt_ctx* c, uint32_t first_frame, uint32_t n_fr
     HIPCHK(c, hipSetDevice(c->device));
     c->stats.launches = 0; c->stats.frames = 0; c->stats.kernel_ms = 0.0; c->stats.kernel_sum_ms = 0.0; c->stats.concurrent = 1;
     if (!n_frames) return PRT_OK;
+    c->fresh = false;
     if ((rc = ensure_seeds(c, seed_pairs, n_frames))) return rc;
     const unsigned step = c->frames_per_launch ? c->frames_per_launch : (c->sc.n_pairs > 65536u ? 4096u : 512u);
     const int K = sub_parts(c, n_frames);
@@ -482,6 +499,7 @@ extern "C" int prt_render_spp(prt_ctx* c, uint32_t spp, uint32_t max_frames, con
     HIPCHK(c, hipSetDevice(c->device));
     c->stats.launches = 0; c->stats.frames = 0; c->stats.kernel_ms = 0.0; c->stats.kernel_sum_ms = 0.0; c->stats.concurrent = 1;
     if ((rc = ensure_seeds(c, seed_pairs, max_frames))) return rc;
+    c->fresh = false;
     const unsigned step = c->frames_per_launch ? c->frames_per_launch : (c->sc.n_pairs > 65536u ? 4096u : 512u);
     const int K = sub_parts(c, 8ull * spp);            // (a path takes 4.4 ... 7.2 segments on the BASELINE scenes)
     c->stats.concurrent = (uint32_t)K;
@@ -620,6 +638,146 @@ extern "C" int prt_render_spp(prt_ctx* c, uint32_t spp, uint32_t max_frames, con
     return PRT_OK;
 }
 
+// prt_render_adaptive (prt.h).  Rounds of launches: a round covers the same window of frames in each of the K sub-parts, on their streams,
+// and waits for all of them -- their reports plan the next round.  While many pixels are live a sub-part is prt_render_spp's interleaved set
+// of tiles; once fewer than compact_below % of the frame are, the live pixels are listed in increasing order (launch_live_list) and the
+// sub-parts are consecutive shares of the list, which is rebuilt once its live pixels have fallen below half of it.  Every live pixel has done
+// exactly the frames of the rounds so far (plus its run-ahead lead, kept in its state), so any list of them can take the next window.
+extern "C" int prt_render_adaptive(prt_ctx* c, const prt_adaptive* a, uint32_t max_frames, const int32_t* seed_pairs, uint32_t* frames_used) {
+    CTX_CHECK(c);
+    int rc = ready(c, "prt_render_adaptive");
+    if (rc) return rc;
+    if (!a || !max_frames || !seed_pairs) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_adaptive: bad arguments");
+    if (a->min_spp < 2 || a->max_spp < a->min_spp) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_adaptive: needs 2 <= min_spp <= max_spp");
+    if (!(a->rel_err >= 0.0f) || !(a->abs_floor >= 0.0f))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_adaptive: rel_err and abs_floor must be >= 0 (and not NaN)");
+    if (max_frames >= (1u << 29))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_adaptive: max_frames must be below 2^29 (the run-ahead lead shares its word with the converged bit)");
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_render_adaptive: a debug view overwrites acc: there is no noise to judge");
+    if (!c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_render_adaptive: needs a freshly reset context (prt_reset)");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->stats.launches = 0; c->stats.frames = 0; c->stats.kernel_ms = 0.0; c->stats.kernel_sum_ms = 0.0; c->stats.concurrent = 1;
+    c->arep = prt_adaptive_report{};
+    if ((rc = ensure_seeds(c, seed_pairs, max_frames))) return rc;
+    const unsigned n_waves = (unsigned)((c->npix + 63) / 64);
+    if (!c->d_adapt) {
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_adapt), c->npix * sizeof(float2)));
+        HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, c->npix * sizeof(float2), c->stream));
+    }
+    if (!c->d_live) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_live), c->npix * sizeof(uint32_t)));
+    if (!c->d_live_aux) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_live_aux), (n_waves + 1) * sizeof(uint32_t)));
+    c->fresh = false;
+    const unsigned step = c->frames_per_launch ? c->frames_per_launch : (c->sc.n_pairs > 65536u ? 4096u : 512u);
+    const int K = sub_parts(c, 8ull * a->max_spp);
+    c->stats.concurrent = (uint32_t)K;
+    const bool pacing = c->pace && c->run_ahead && c->sc.n_pairs <= 65536u;
+    float pace_inv_ref = 0.0f;
+    const unsigned n_tiles = render_tile_count(c->width, c->rows);
+    HIPCHK(c, hipMemsetAsync(c->d_counters + 4, 0, 2 * prt_ctx::MAX_SUB * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (K > 1 && (rc = fork_streams(c, K))) return rc;
+    auto stream_of = [&](int j) { return K > 1 ? c->sub_stream[j] : c->stream; };
+    auto abort_streams = [&](int code, const std::string& msg) {
+        for (int j = 0; j < K; ++j) (void)hipStreamSynchronize(stream_of(j));
+        (void)hipMemsetAsync(c->d_counters + 4, 0, 2 * prt_ctx::MAX_SUB * sizeof(unsigned long long), c->stream);
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipGetLastError();
+        c->state_undefined = true;
+        return fail(c, code, msg);
+    };
+#define SUBCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return abort_streams(PRT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
+    bool done[prt_ctx::MAX_SUB] = {false, false, false, false};     // tile rounds: every pixel of the sub-part's tiles is frozen
+    for (int j = 0; j < K; ++j) done[j] = (unsigned)j >= n_tiles;
+    unsigned long long live = c->npix;
+    uint32_t list_count = 0;
+    bool list_mode = false;
+    uint32_t f = 0;
+    while (f < max_frames && live) {
+        const uint32_t n = (max_frames - f < step) ? max_frames - f : step;
+        if (c->compact && live * 100ull < (unsigned long long)c->npix * (unsigned)c->compact_below && (!list_mode || 2ull * live < list_count)) {
+            // (every stream is idle: the last round has been waited for)
+            launch_live_list(c->S, c->npix, a->max_spp, c->d_live_aux, c->d_live, c->d_live_aux + n_waves, c->stream);
+            uint32_t cnt = 0;
+            SUBCHK(hipMemcpyAsync(&cnt, c->d_live_aux + n_waves, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+            SUBCHK(hipStreamSynchronize(c->stream));
+            if (cnt != live) return abort_streams(PRT_ERR_HIP, "prt_render_adaptive: the live-pixel list disagrees with the launches' reports");
+            list_count = cnt; list_mode = true;
+            ++c->arep.list_builds;
+        }
+        const uint32_t chunk = list_mode ? (((list_count + 63u) / 64u + (uint32_t)K - 1u) / (uint32_t)K) * 64u : 0u;   // (whole waves per sub-part)
+        bool launched[prt_ctx::MAX_SUB] = {false, false, false, false};
+        for (int j = 0; j < K; ++j) {
+            FrameArgs fa = frame_args(c, 1 + f, n, c->d_seeds + 2 * (size_t)f, a->max_spp, true);
+            fa.seed_frames = max_frames - f; fa.run_ahead = c->run_ahead;
+            fa.pace_inv_ref = pacing ? pace_inv_ref : 0.0f;
+            fa.adapt = c->d_adapt; fa.min_spp = a->min_spp; fa.rel_err = a->rel_err; fa.abs_floor = a->abs_floor;
+            fa.unfinished = c->d_counters + 4 + 2 * j;
+            fa.unfinished_host = c->h_unfinished + 2 * j;
+            if (list_mode) {
+                const uint32_t start = (uint32_t)j * chunk;
+                if (start >= list_count) continue;
+                fa.live = c->d_live + start;
+                fa.live_count = std::min(chunk, list_count - start);
+                c->arep.list_lanes += 64ull * ((fa.live_count + 63u) / 64u);
+                ++c->arep.list_launches;
+            } else {
+                if (done[j]) continue;
+                fa.tile_first = (uint32_t)j; fa.tile_stride = (uint32_t)K;
+                ++c->arep.tile_launches;
+            }
+            c->h_unfinished[2 * j] = ~0ull;
+            if (K > 1) SUBCHK(hipEventRecord(c->sub_ev0[j][0], stream_of(j)));
+            c->last = launch_render(c->sc, c->cam, c->S, fa, c->fb, stream_of(j), c->lo);
+            if (K > 1) SUBCHK(hipEventRecord(c->sub_ev[j][0], stream_of(j)));
+            ++c->stats.launches;
+            launched[j] = true;
+        }
+        if (list_mode) c->arep.list_live_lanes += live;
+        SUBCHK(hipGetLastError());
+        live = 0;
+        for (int j = 0; j < K; ++j) {
+            if (!launched[j]) continue;
+            SUBCHK(hipStreamSynchronize(stream_of(j)));
+            float ms = 0.f;
+            if (K > 1 && hipEventElapsedTime(&ms, c->sub_ev0[j][0], c->sub_ev[j][0]) == hipSuccess) c->stats.kernel_sum_ms += ms;
+            const unsigned long long left = __atomic_load_n(c->h_unfinished + 2 * j, __ATOMIC_ACQUIRE);
+            if (c->launch_log) std::fprintf(stderr, "prt adaptive launch: part %d frames %u..%u %s %.3f ms, %llu pixels unfinished\n", j, 1 + f, f + n,
+                                            list_mode ? "list" : "tiles", ms, left);
+            if (left == ~0ull) return abort_streams(PRT_ERR_HIP, "prt_render_adaptive: a launch ended without reporting its unfinished pixels");
+            if (!list_mode) done[j] = left == 0;
+            live += left;
+        }
+        f += n;
+        if (pacing && pace_inv_ref == 0.0f && live) pace_inv_ref = inverse_mean_path_length(c, a->max_spp, c->stream);
+    }
+#undef SUBCHK
+    if (K > 1 && (rc = join_streams(c, K))) return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->timing_pending = true;
+    c->stats.frames = f;
+    if (frames_used) *frames_used = f;
+    if (live) return fail(c, PRT_ERR_NOT_READY, "prt_render_adaptive: max_frames reached before every pixel froze");
+    return PRT_OK;
+}
+
+extern "C" int prt_read_adaptive_stats(prt_ctx* c, float* out2) {
+    CTX_CHECK(c);
+    if (!out2 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_adaptive_stats: bad arguments");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    if (!c->d_adapt) { std::memset(out2, 0, c->npix * 2 * sizeof(float)); return PRT_OK; }    // (no adaptive render since the frame was made)
+    HIPCHK(c, hipMemcpy(out2, c->d_adapt, c->npix * sizeof(float2), hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+extern "C" int prt_get_adaptive_report(prt_ctx* c, prt_adaptive_report* out) {
+    CTX_CHECK(c);
+    if (!out) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_get_adaptive_report: null");
+    *out = c->arep;
+    return PRT_OK;
+}
+
 extern "C" int prt_set_walk_min_lanes(prt_ctx* c, uint32_t lanes) {
     CTX_CHECK(c);
     if (lanes < 1 || lanes > 64) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_walk_min_lanes: 1..64");
@@ -653,6 +811,8 @@ extern "C" int prt_set_option(prt_ctx* c, const char* name, int value) {
         if (value != c->tile_sort) for (int j = 0; j < prt_ctx::MAX_SUB; ++j) c->have_order[j] = false;      // (setting it again keeps a measured order)
         c->tile_sort = value;
     }
+    else if (n == "compact") { if (value < 0 || value > 1) return bad(); c->compact = value; }
+    else if (n == "compact_below") { if (value < 0 || value > 100) return bad(); c->compact_below = value; }
     else if (n == "test_drop_report") { if (value < 0 || value > 1) return bad(); c->test_drop_report = value != 0; }
     else return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_option: unknown option " + n);
     return PRT_OK;
@@ -660,7 +820,10 @@ extern "C" int prt_set_option(prt_ctx* c, const char* name, int value) {
 
 extern "C" const char* prt_kernel_variant(prt_ctx* c) {
     if (!c) return "";
-    c->variant = std::string(c->last.name) + (c->last.waves ? " waves=" + std::to_string(c->last.waves) + (c->last.scatter ? " pixels=scattered" : (c->last.ordered ? " pixels=tiles, expensive first" : " pixels=tiles")) + (c->last.pix_per_wave != 64 ? ", " + std::to_string(c->last.pix_per_wave) + " per wave" : "") + (c->last.pool ? ", pool" : "") : "");
+    const RenderLaunch& l = c->last;
+    const char* pixels = l.list ? " pixels=live list" : (l.scatter ? " pixels=scattered" : (l.ordered ? " pixels=tiles, expensive first" : " pixels=tiles"));
+    c->variant = std::string(l.name) + (l.waves ? " waves=" + std::to_string(l.waves) + pixels + (l.pix_per_wave != 64 ? ", " + std::to_string(l.pix_per_wave) + " per wave" : "") +
+                                        (l.pool ? ", pool" : "") + (l.adaptive ? ", adaptive" : "") : "");
     return c->variant.c_str();
 }
 
@@ -736,6 +899,7 @@ extern "C" int prt_write_state(prt_ctx* c, const prt_path_state* state) {
     (void)hipFree(d);
     HIPCHK(c, e);
     c->state_undefined = false;
+    c->fresh = false;
     return PRT_OK;
 }
 

@@ -1082,7 +1082,11 @@ PT_DEV float coat_pdf(const Event& e, const Mat& mat) {
 // exponential and no Phong power (whose binary64 polynomials alone are 40 - 80 B of scratch per lane)
 #define PT_MATS_DIST_SHIFT 24
 #define PT_MATS_DISTS (7u << PT_MATS_DIST_SHIFT)
-#define PT_MATS_FLAGS (PT_MATS_SDF | PT_MATS_VIEW | PT_MATS_PICK | PT_MATS_ENVIS | PT_MATS_DISTS)
+// PT_MATS_ADAPT bit: the adaptive-sampling build of a set (prt_render_adaptive): the freeze rule of lane_frozen, the {l, s2} plane updated at
+// every path end, and the live-pixel list mapping of render_kernel.  A bit of MATS rather than a template parameter of its own: the
+// pre-existing instances keep their names and their code
+#define PT_MATS_ADAPT 0x08000000u
+#define PT_MATS_FLAGS (PT_MATS_SDF | PT_MATS_VIEW | PT_MATS_PICK | PT_MATS_ENVIS | PT_MATS_DISTS | PT_MATS_ADAPT)
 template <unsigned MATS>
 PT_HD constexpr unsigned dist_mask() { return ((MATS >> PT_MATS_DIST_SHIFT) & 7u) ? ((MATS >> PT_MATS_DIST_SHIFT) & 7u) : 7u; }
 template <unsigned MATS>
@@ -1367,6 +1371,8 @@ struct Lane {
     unsigned occluded : 1;
     unsigned sh_vertex : 1;  // PT_MATS_ENVIS: the shadow ray starts at the vertex (= origin of the probe), not where the probe ended
     unsigned posted : 1;     // render_kernel_rp (pt_pool.h): the lane's ray is with the workgroup's walker waves
+    unsigned conv : 1;       // PT_MATS_ADAPT builds only: the path that ended last was judged converged (adaptive_converged); between launches
+                             // bit 31 of DevState::q4.w
 };
 
 // position of the hit in L.h: intersect_scene's `ray.pos = ray.origin + ray.dir * t` (same operations, same bits) on the ray that was walked
@@ -1402,6 +1408,31 @@ PT_DEV bool lane_runnable(const FrameArgs& fa, const Lane& L, const bool laggard
     if (L.begun) return true;
     if (fa.spp_limit && L.reset && L.samples >= fa.spp_limit) return false;
     return L.f < target || (fa.run_ahead && laggards && L.f < fa.seed_frames);
+}
+// The adaptive freeze rule (prt_render_adaptive, the PT_MATS_ADAPT builds; fa.spp_limit = max_spp): the pixel's max_spp-th path has ended, or a
+// path of at least min_spp was judged converged at its end (Lane::conv).  Functions of their own, not a flag of the ones above: the "N spp"
+// builds compile to the code they had (a template parameter there moved their spills: view set 236 -> 180 B of scratch, coat 124 -> 112)
+PT_DEV bool lane_frozen_adaptive(const FrameArgs& fa, const Lane& L) { return L.reset && (L.samples >= fa.spp_limit || L.conv); }
+PT_DEV bool lane_owes_frames_adaptive(const FrameArgs& fa, const Lane& L, const unsigned target) {
+    if (L.stage != ST_READY || L.begun) return L.f < target;
+    if (lane_frozen_adaptive(fa, L)) return false;
+    return L.f < target;
+}
+PT_DEV bool lane_runnable_adaptive(const FrameArgs& fa, const Lane& L, const bool laggards, const unsigned target) {
+    if (L.stage != ST_READY) return false;
+    if (L.begun) return true;
+    if (lane_frozen_adaptive(fa, L)) return false;
+    return L.f < target || (fa.run_ahead && laggards && L.f < fa.seed_frames);
+}
+// prt.h prt_render_adaptive: the standard error of the pixel's mean luminance against rel_err x max(mean, abs_floor), from the plane {l, s2}
+// after n paths.  IEEE f32 operations in this order, no contraction: the host repeats it in numpy float32 bit for bit.
+PT_HD bool adaptive_converged(const float l, const float s2, const unsigned n, const float rel_err, const float abs_floor) {
+    const float m = l / (float)n;
+    // (at 0: the difference can round below zero for a pixel whose paths all bring (nearly) the same luminance, and rel_err = 0 must
+    // never converge)
+    const float v = __builtin_fmaxf((s2 - l * m) / ((float)n * (float)(n - 1u)), 0.0f);
+    const float t = rel_err * __builtin_fmaxf(m, abs_floor);
+    return v < t * t;
 }
 PT_DEV bool lane_runnable(const FrameArgs& fa, const Lane& L, const bool laggards) { return lane_runnable(fa, L, laggards, fa.n_frames); }
 

@@ -3,6 +3,7 @@
 //   render_kernel<MATS, MEDIUM, WAVES>   pt_render.h, instantiated by pt_inst_*.hip (one file per material set: they compile in parallel)
 //   state_to_rtd / rtd_to_state          80 B/px SoA planes <-> the reference's 112 B RTD records
 //   count_kernel                         sum of samples / segments / frozen pixels (Msamples/s accounting)
+//   live_count / live_scan / live_write  the live-pixel list of prt_render_adaptive's list launches
 //   tonemap_kernel                       shaders/tonemapper.glsl
 //   selftest_*                           per-function known-answer entries
 #include "pt_render.h"
@@ -78,6 +79,48 @@ __global__ void count_kernel(const DevState S, size_t n, unsigned spp, unsigned 
         s += __shfl_down(s, off); g += __shfl_down(g, off); z += __shfl_down(z, off);
     }
     if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], s); atomicAdd(&out[1], g); atomicAdd(&out[2], z); }
+}
+
+// ---- live-pixel list (prt_render_adaptive) ----------------------------------------------------------------
+// A pixel is live until the adaptive freeze rule holds for it (pt_device.h lane_frozen_adaptive: reset && (samples >= max_spp || converged), the
+// converged bit being bit 31 of q4.w between launches).  The list holds the live pixels' local ids in increasing order -- a wave of a list launch
+// gets neighbouring pixels, and the order does not depend on timing: one wave per 64 consecutive pixels counts its live lanes (ballot +
+// popcount), one workgroup turns the counts into offsets, and the same waves write their live ids at offset + live lanes below them.
+PT_DEV bool pixel_live(const DevState& S, size_t id, unsigned max_spp) {
+    const uint4 e = S.q4[id];
+    return !((e.w & 2u) && (e.x >= max_spp || (e.w >> 31) != 0u));
+}
+__global__ void live_count_kernel(const DevState S, size_t n, unsigned max_spp, uint32_t* __restrict__ wave_count) {
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long m = __ballot(id < n && pixel_live(S, id, max_spp));
+    if ((threadIdx.x & 63u) == 0u && id < n) wave_count[id >> 6] = (uint32_t)__popcll(m);
+}
+// exclusive prefix sum of wave_count[0 .. n_waves) in place; the total into *total.  One workgroup of 1024: each thread sums a run of
+// consecutive entries, the workgroup scans the 1024 sums in LDS, each thread writes its run's offsets
+__global__ void __launch_bounds__(1024) live_scan_kernel(uint32_t* __restrict__ wave_count, unsigned n_waves, uint32_t* __restrict__ total) {
+    __shared__ uint32_t part[1024];
+    const unsigned t = threadIdx.x;
+    const unsigned per = (n_waves + 1023u) / 1024u;
+    const unsigned b = t * per, e = min(b + per, n_waves);
+    uint32_t s = 0;
+    for (unsigned k = b; k < e; ++k) s += wave_count[k];
+    part[t] = s;
+    __syncthreads();
+    for (unsigned off = 1; off < 1024u; off <<= 1) {
+        const uint32_t v = t >= off ? part[t - off] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - s;
+    for (unsigned k = b; k < e; ++k) { const uint32_t c = wave_count[k]; wave_count[k] = run; run += c; }
+    if (t == 1023u) *total = part[1023];
+}
+__global__ void live_write_kernel(const DevState S, size_t n, unsigned max_spp, const uint32_t* __restrict__ wave_off, uint32_t* __restrict__ list) {
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = id < n && pixel_live(S, id, max_spp);
+    const unsigned long long m = __ballot(live);
+    if (live) list[wave_off[id >> 6] + (unsigned)__popcll(m & ((1ull << (threadIdx.x & 63u)) - 1ull))] = (uint32_t)id;
 }
 
 // shaders/tonemapper.glsl:12-23,47-64 -- display transform of the linear framebuffer (not part of the radiance
@@ -277,6 +320,12 @@ void launch_selftest_fn(int fn, const float* params, const float* in, float* out
 void launch_tonemap(const float4* fb, unsigned char* out, const FrameArgs& fa, hipStream_t stream) {
     const size_t npix = (size_t)fa.width * (size_t)fa.rows;
     hipLaunchKernelGGL(tonemap_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, fb, reinterpret_cast<uchar4*>(out), fa);
+}
+void launch_live_list(const DevState& S, size_t n, unsigned max_spp, uint32_t* wave_off, uint32_t* list, uint32_t* count, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((n + 255) / 256), n_waves = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(live_count_kernel, dim3(blocks), dim3(256), 0, stream, S, n, max_spp, wave_off);
+    hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, wave_off, n_waves, count);
+    hipLaunchKernelGGL(live_write_kernel, dim3(blocks), dim3(256), 0, stream, S, n, max_spp, wave_off, list);
 }
 void launch_count(const DevState& S, size_t n, unsigned spp, unsigned long long* out3, hipStream_t stream) {
     unsigned blocks = (unsigned)((n + 255) / 256);

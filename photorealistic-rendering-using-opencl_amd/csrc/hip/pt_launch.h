@@ -17,7 +17,7 @@ struct LaunchOpts {
     int pool = 0;           // 1: render_kernel_pool (pt_pool.h: shading waves + walker waves around a pool of parked contexts) where a launch can take it
 };
 // what a launch ran: kernel variant, wave-count build, pixel-to-wave mapping (prt_kernel_variant)
-struct RenderLaunch { const char* name = ""; int waves = 0; int scatter = 0; int ordered = 0; int pool = 0; int pix_per_wave = 64; };   // ordered: the tiles were taken in the launcher's order
+struct RenderLaunch { const char* name = ""; int waves = 0; int scatter = 0; int ordered = 0; int pool = 0; int pix_per_wave = 64; int adaptive = 0; int list = 0; };   // ordered: the tiles were taken in the launcher's order; adaptive: the PT_MATS_ADAPT build, list: over a live-pixel list
 
 // launches the scene-specialised variant (the AOT analogue of the reference's per-scene program
 // build, include/CL/cl_kernel.h:226-345)
@@ -53,5 +53,8 @@ void launch_selftest_math(int fn, const float* a, const float* b, float* out, in
 void launch_selftest_fn(int fn, const float* params, const float* in, float* out, int n, hipStream_t stream);
 void launch_tonemap(const float4* fb, unsigned char* out, const FrameArgs& fa, hipStream_t stream);
 void launch_count(const DevState& S, size_t n, unsigned spp, unsigned long long* out3, hipStream_t stream);
+// prt_render_adaptive: the local ids of the n-pixel frame's pixels that the adaptive freeze rule (max_spp, DevState::q4.w bit 31) has not frozen,
+// in increasing order, into list; their number into *count (device).  wave_off: ceil(n / 64) words of scratch
+void launch_live_list(const DevState& S, size_t n, unsigned max_spp, uint32_t* wave_off, uint32_t* list, uint32_t* count, hipStream_t stream);
 
 }  // namespace prt

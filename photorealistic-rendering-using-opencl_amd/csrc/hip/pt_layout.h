@@ -126,7 +126,8 @@ struct DevState {
     float4* q1;   // dir.xyz, dist
     float4* q2;   // mask.xyz, bits(total)
     float4* q3;   // acc
-    uint4* q4;    // samples, diff | spec << 16, trans | scatters << 16, was_specular | reset << 1 | frames ahead << 2
+    uint4* q4;    // samples, diff | spec << 16, trans | scatters << 16, was_specular | reset << 1 | frames ahead << 2 (| converged << 31: adaptive
+                  // renders only, Lane::conv; the frames ahead then stay below 2^29)
 };
 
 struct FrameArgs {
@@ -157,6 +158,12 @@ struct FrameArgs {
     uint32_t walk_min_lanes;                // lane machine: a closest-hit walk phase of a wave ends once fewer lanes than this are still walking
     uint32_t shadow_min_lanes;              // ... and an any-hit (shadow ray) phase below this many
     uint32_t tri_sixteenths;                // the pending triangle tests of a walk phase run once this many sixteenths of its walking lanes have one
+    // adaptive renders (prt_render_adaptive, the PT_MATS_ADAPT builds; spp_limit = max_spp).  Last in the block: the other builds never read them
+    float2* adapt;                          // per pixel {l, s2}: luminance of acc at the last path end, sum of squared per-path increments
+    const uint32_t* live;                   // null: tiles (or scattered pixels) as above.  Else lane l of wave g renders pixel live[64 g + l] (local
+    uint32_t live_count;                    // framebuffer index) when 64 g + l < live_count: the unfrozen pixels packed into full waves
+    uint32_t min_spp;
+    float rel_err, abs_floor;
 };
 
 }  // namespace prt

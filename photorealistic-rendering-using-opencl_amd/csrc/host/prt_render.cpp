@@ -2,7 +2,8 @@
 // the prt C ABI: same argv flags (-scene -width -height -hdr -alpha), same start-up order
 // (scene -> model -> BVH -> buffers -> camera -> kernel args), same per-frame protocol
 // (frame counter from 1, two rand() values per frame after two consumed at start-up), with the
-// GLFW loop replaced by "-frames N" or "-spp N" and PrtSc replaced by "-out file.{png,hdr,pfm}" (default render.png / render.hdr by -encoder, as saveImage()).
+// GLFW loop replaced by "-frames N" or "-spp N" (with "-adaptive E [-min-spp M] [-abs-floor F] [-spp-map file.pfm]": adaptive sampling,
+// -spp the maximum) and PrtSc replaced by "-out file.{png,hdr,pfm}" (default render.png / render.hdr by -encoder, as saveImage()).
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -88,6 +89,9 @@ int main(int argc, char** argv) {
     bool alpha = false;
     uint32_t view = PRT_VIEW_RESULTS;                              // kernels/main.cl:15: a source edit in the reference, a flag here
     unsigned frames = 0, spp = 16;
+    float adaptive = -1.0f, abs_floor = 0.0f;                      // -adaptive <rel_err>: prt_render_adaptive between -min-spp and -spp paths
+    unsigned min_spp = 16;
+    std::string spp_map_path;                                      // -spp-map file.pfm: paths per pixel of the adaptive render
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -103,6 +107,10 @@ int main(int argc, char** argv) {
         else if (a == "-frames") frames = (unsigned)std::atoi(next());
         else if (a == "-spp") spp = (unsigned)std::atoi(next());
         else if (a == "-out") out_path = next();
+        else if (a == "-adaptive") adaptive = (float)std::atof(next());
+        else if (a == "-min-spp") min_spp = (unsigned)std::atoi(next());
+        else if (a == "-abs-floor") abs_floor = (float)std::atof(next());
+        else if (a == "-spp-map") spp_map_path = next();
         else if (a == "-device") device = std::atoi(next());
     }
     prt_ctx* ctx = nullptr;
@@ -161,7 +169,10 @@ int main(int argc, char** argv) {
         std::vector<int32_t> seeds((size_t)max_frames * 2);
         prth_seed_pairs(1, max_frames, seeds.data());              // rand() protocol, :226-227,301-302
         if (frames) CHECK(prt_render_frames(ctx, 1, frames, seeds.data()));
-        else CHECK(prt_render_spp(ctx, spp, max_frames, seeds.data(), nullptr));
+        else if (adaptive >= 0.0f) {
+            const prt_adaptive ad = {std::min(min_spp, spp), spp, adaptive, abs_floor};
+            CHECK(prt_render_adaptive(ctx, &ad, max_frames, seeds.data(), nullptr));
+        } else CHECK(prt_render_spp(ctx, spp, max_frames, seeds.data(), nullptr));
 
         std::vector<float> rgba((size_t)window_width * window_height * 4);
         CHECK(prt_read_framebuffer(ctx, rgba.data()));             // saveImage(), include/GL/cl_gl_interop.h:144-160
@@ -169,6 +180,18 @@ int main(int argc, char** argv) {
         CHECK(prt_query_counts(ctx, frames ? 0 : spp, &st));
         std::printf("%dx%d: %llu samples, %llu segments, %.1f ms on the device (%u launches)\n", window_width, window_height,
                     (unsigned long long)st.samples, (unsigned long long)st.segments, st.kernel_ms, st.launches);
+        if (!frames && adaptive >= 0.0f) {
+            const size_t npix = (size_t)window_width * window_height;
+            std::printf("adaptive: %.1f paths per pixel on average (%u ... %u, relative error %g)\n", (double)st.samples / (double)npix,
+                        std::min(min_spp, spp), spp, (double)adaptive);
+            if (!spp_map_path.empty()) {                           // paths per pixel as a grey PFM (framebuffer order: bottom-up, as PFM)
+                std::vector<prt_path_state> state(npix);
+                CHECK(prt_read_state(ctx, state.data()));
+                std::vector<float> map(npix * 4);
+                for (size_t k = 0; k < npix; ++k) map[4 * k] = map[4 * k + 1] = map[4 * k + 2] = (float)state[k].samples;
+                if (!write_pfm(spp_map_path, map, window_width, window_height)) { std::fprintf(stderr, "cannot write %s\n", spp_map_path.c_str()); return 1; }
+            }
+        }
         // saveImage(), include/GL/cl_gl_interop.h:144-160: -encoder 0 -> render.png (the displayed, tonemapped picture), -encoder 1 ->
         // render.hdr (the linear one); -out <file> picks the name, and the format by its extension (.png / .hdr / .pfm)
         if (out_path.empty()) out_path = encoder == 1 ? "render.hdr" : "render.png";
