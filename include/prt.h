@@ -215,6 +215,70 @@ typedef struct prt_adaptive_report {
 } prt_adaptive_report;
 int prt_get_adaptive_report(prt_ctx* ctx, prt_adaptive_report* out);
 
+/* Guide (feature) buffers (no counterpart in the reference: its VIEW_ALBEDO is named, kernels/main.cl:6-15, but has no branch).
+ * prt_render_guides traces `samples` (1 .. 64) guide samples per pixel of the context's frame part (tiles and row blocks included: global
+ * pixel coordinates, as the render kernel):
+ *   - Sample s sits at the fractional pixel offset (fx, fy) = (0.5, 0.5) for s = 0, else ((0.5 + s*0.7548776662) mod 1, (0.5 + s*0.5698402910)
+ *     mod 1) (the R2 sequence, f32).  The camera ray is create_cam_ray's (kernels/camera.cl:17-66) through the image-plane point
+ *     sx = (x + fx - 0.5) / (width - 1), sy = (height - 1 - y - (fy - 0.5)) / (height - 1) -- (fx, fy) = (0.5, 0.5) is the point the render
+ *     samples -- and, with apertureRadius > 0.00001, the lens sample (random1, random2) = ((fx + 0.25) mod 1, (fy + 0.75) mod 1).
+ *   - Delta chain: at a smooth conductor (PRT_MAT_COND without PRT_MAT_ROUGH_COND) the ray reflects about the shading normal; at a smooth
+ *     dielectric (PRT_MAT_DIEL without PRT_MAT_ROUGH_DIEL) it refracts with the index dielectric_sample uses (the material's eta.x, inverted
+ *     when the ray arrives on the side the shading normal points to), or reflects on total internal reflection.  At most 4 such events are followed;
+ *     the hit after them -- or the first non-delta hit -- gives the sample's values.  Albedo is multiplied by each conductor's
+ *     clamp(color, 0, 1) on the way (a dielectric's tint is 1); depth is the summed path length of the chain.
+ *   - Per hit: albedo = clamp(material color, 0, 1) (lights included); normal = the shading normal finish_closest yields (interpolated for
+ *     triangles), negated when dot(n, dir) > 0.  The global medium, alpha testing and env importance sampling are ignored.
+ *   - Miss: albedo = clamp(env lookup of the direction, 0, 1) (times the chain's tint), no hit.
+ *   - Per pixel 8 floats, framebuffer order: {albedo.rgb mean over the samples, coverage = hits / samples, normal = normalize(sum over
+ *     hits of the finite normals) (0 without hits or for a zero sum), depth = mean over hits (0 without hits)}.
+ * The plane is allocated on first use.  It goes stale on prt_upload_scene, prt_set_camera, prt_upload_envmap, prt_resize, prt_set_tile and
+ * prt_set_row_blocks (prt_reset keeps it).  prt_read_guides: PRT_ERR_NOT_READY while there are no valid guides. */
+int prt_render_guides(prt_ctx* ctx, uint32_t samples);
+int prt_read_guides(prt_ctx* ctx, float* out8);
+
+/* Denoiser: the spatial part of SVGF (Schied et al. 2017), an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010), guided by the
+ * guides above.  L(c) = 0.2126 r + 0.7152 g + 0.0722 b.  Inputs: the framebuffer colour c, the guides {a, cov, n, z} and the luminance
+ * variance of the pixel's mean, v, from
+ *   PRT_DENOISE_VAR_STATS    the {l, s2} plane of prt_render_adaptive with n = the pixel's paths: m = l / n, v = max((s2 - l m) / (n (n - 1)), 0)
+ *                            (0 for n < 2).  Needs the last render since the reset to be prt_render_adaptive (else PRT_ERR_NOT_READY); for a
+ *                            plain "N spp" picture with its plane render adaptively with min_spp = max_spp = N, rel_err = 0.
+ *   PRT_DENOISE_VAR_SPATIAL  the unweighted 5x5 moments of L around the pixel, E[L^2] - E[L]^2 clamped at 0, window coordinates clamped into
+ *                            the frame, non-finite colours left out
+ *   PRT_DENOISE_VAR_AUTO     (default) stats when valid, else spatial.
+ * Pass i = 0 .. passes-1, step s = 2^i:
+ *   1. g = 3x3 Gaussian 1/16 [1 2 1; 2 4 2; 1 2 1] of v, coordinates clamped into the frame.
+ *   2. Taps q = p + s (dx, dy), dx, dy in -2..2; taps outside the frame or with a non-finite colour are skipped.
+ *        h   = k(dx) k(dy), k = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *        w_n = max(0, n_p.n_q)^sigma_n when both pixels have cov > 0; 1 when neither has; 0 when one has
+ *        w_z = exp(-|z_p - z_q| / (sigma_z grad_p s sqrt(dx^2 + dy^2) + 1e-4)); grad_p = max over x and y of the absolute difference of z:
+ *              central (|z(+1) - z(-1)| / 2) when both neighbours are in the frame with cov > 0, one-sided (|z(+-1) - z_p|) when one is,
+ *              0 when none is or cov_p = 0
+ *        w_a = exp(-|a_p - a_q|^2 / sigma_a^2)
+ *        w_l = exp(-|L(c_p) - L(c_q)| / (sigma_l sqrt(g_p) + 1e-6))
+ *        w = w_n w_z w_a w_l, except w = 1 for the centre tap (dx = dy = 0; what the product is for guides with a unit normal) and
+ *        w = 0 where the product is NaN (a tap is dropped);   c' = sum h w c / sum h w;   v' = sum h^2 w^2 v / (sum h w)^2
+ * Output: rgba with the framebuffer's alpha; a pixel whose own colour is not finite keeps it.  f32 arithmetic, deterministic (the same
+ * inputs give the same bits).  prt_denoise reads the framebuffer, the state and the stats plane and writes none of them; `rgba` (may be NULL)
+ * gets the filtered image in prt_read_framebuffer's layout, `rgba8` (may be NULL) prt_tonemap_rgba8's display transform of it.
+ * Refused: PRT_ERR_NOT_READY without valid guides or without a render since the reset; PRT_ERR_UNSUPPORTED on tile and row-block contexts
+ * (the filter needs the whole frame) and with a debug view; PRT_ERR_INVALID_ARGUMENT for passes outside 1..8, a sigma that is not > 0
+ * (NaN included) or an unknown var_source.  params NULL = the defaults below. */
+#define PRT_DENOISE_VAR_AUTO 0u
+#define PRT_DENOISE_VAR_STATS 1u
+#define PRT_DENOISE_VAR_SPATIAL 2u
+#define PRT_DENOISE_DEFAULT_PASSES 5u
+#define PRT_DENOISE_DEFAULT_SIGMA_L 3.0f      /* (4 moved a 4096-spp picture of cornell_mixed by relMSE 1.1e-3: DESIGN.md s4) */
+#define PRT_DENOISE_DEFAULT_SIGMA_N 128.0f
+#define PRT_DENOISE_DEFAULT_SIGMA_Z 1.0f
+#define PRT_DENOISE_DEFAULT_SIGMA_A 0.1f
+typedef struct prt_denoise_params {
+    uint32_t passes;      /* 1 .. 8 */
+    uint32_t var_source;  /* PRT_DENOISE_VAR_* */
+    float sigma_l, sigma_n, sigma_z, sigma_a;
+} prt_denoise_params;
+int prt_denoise(prt_ctx* ctx, const prt_denoise_params* params, float* rgba, uint8_t* rgba8);
+
 /* Scheduling knob of the render kernel (no counterpart in the reference; results do not depend on it, tests check
  * that): a wave ends a BVH-walk phase once fewer than `lanes` of its 64 lanes are still walking (and fewer than wait for the
  * phase to end); the lanes cut off resume in the wave's next phase.  1 = every walk runs to its end (lock step).

@@ -15,14 +15,14 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
+from ._capi import DENOISE_DEFAULTS, DenoiseParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -296,6 +296,31 @@ class Renderer:
         rep = AdaptiveReport()
         self._chk(self.lib.prt_get_adaptive_report(self.ctx, C.byref(rep)), "prt_get_adaptive_report")
         return rep
+
+    def render_guides(self, samples=4):
+        """prt_render_guides: `samples` guide samples per pixel (1 .. 64; prt.h has the sample positions and the delta chain)"""
+        self._chk(self.lib.prt_render_guides(self.ctx, int(samples)), "prt_render_guides")
+
+    def read_guides(self):
+        """the guide plane: float32 [rows, width, 8] = {albedo.rgb, coverage, normal.xyz, depth} per pixel, framebuffer order"""
+        out = np.zeros((self.rows, self.width, 8), dtype=np.float32)
+        self._chk(self.lib.prt_read_guides(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_guides")
+        return out
+
+    _VAR_SOURCES = {"auto": _capi.PRT_DENOISE_VAR_AUTO, "stats": _capi.PRT_DENOISE_VAR_STATS, "spatial": _capi.PRT_DENOISE_VAR_SPATIAL}
+
+    def denoise(self, passes=DENOISE_DEFAULTS["passes"], var_source="auto", sigma_l=DENOISE_DEFAULTS["sigma_l"],
+                sigma_n=DENOISE_DEFAULTS["sigma_n"], sigma_z=DENOISE_DEFAULTS["sigma_z"], sigma_a=DENOISE_DEFAULTS["sigma_a"], tonemap=False):
+        """prt_denoise: the a-trous filter of prt.h over the framebuffer, guided by the guides.  var_source: "auto" | "stats" | "spatial".
+        Returns float32 [rows, width, 4] (prt_read_framebuffer's layout), or with tonemap=True uint8 [rows, width, 4] (prt_tonemap_rgba8's)"""
+        p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
+        if tonemap:
+            out = np.zeros((self.rows, self.width, 4), dtype=np.uint8)
+            self._chk(self.lib.prt_denoise(self.ctx, C.byref(p), None, out.ctypes.data_as(C.c_void_p)), "prt_denoise")
+        else:
+            out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+            self._chk(self.lib.prt_denoise(self.ctx, C.byref(p), out.ctypes.data_as(C.c_void_p), None), "prt_denoise")
+        return out
 
     def set_walk_min_lanes(self, lanes):
         self._chk(self.lib.prt_set_walk_min_lanes(self.ctx, int(lanes)), "prt_set_walk_min_lanes")

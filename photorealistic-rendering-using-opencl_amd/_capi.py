@@ -70,6 +70,16 @@ class AdaptiveReport(C.Structure):
                 ("list_lanes", C.c_uint64), ("list_live_lanes", C.c_uint64)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("var_source", C.c_uint32), ("sigma_l", C.c_float), ("sigma_n", C.c_float),
+                ("sigma_z", C.c_float), ("sigma_a", C.c_float)]
+
+
+# prt_denoise_params::var_source and the defaults of a NULL params pointer (include/prt.h)
+PRT_DENOISE_VAR_AUTO, PRT_DENOISE_VAR_STATS, PRT_DENOISE_VAR_SPATIAL = 0, 1, 2
+DENOISE_DEFAULTS = dict(passes=5, sigma_l=3.0, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1)
+
+
 assert C.sizeof(Material) == 64 and C.sizeof(Mesh) == 256 and C.sizeof(BvhNode) == 36 and C.sizeof(Camera) == 80
 
 # numpy view of the 112-byte RTD (prt_path_state)
@@ -95,6 +105,9 @@ PRT_API = [
     ("prt_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("prt_read_adaptive_stats", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_get_adaptive_report", C.c_int, [C.c_void_p, C.POINTER(AdaptiveReport)]),
+    ("prt_render_guides", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("prt_read_guides", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_denoise", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("prt_kernel_variant", C.c_char_p, [C.c_void_p]),

@@ -101,6 +101,13 @@ struct prt_ctx {
     int compact = 1;                               // option "compact": list launches once few pixels are live
     int compact_below = 50;                        // option "compact_below": ... fewer than this percentage of the frame
     prt_adaptive_report arep{};                    // what the last adaptive render did with its launches
+    bool stats_valid = false;                      // the last render since prt_reset was prt_render_adaptive: d_adapt belongs to the framebuffer
+    // prt_render_guides / prt_denoise (pt_denoise.hip): the guide plane (2 float4 per pixel) and the filter's buffers (two ping-pong planes,
+    // the output plane, the Gaussian of v), allocated on first use with the frame's size, freed with the frame
+    float4* d_guides = nullptr;
+    bool guides_valid = false;                     // cleared by everything that changes what a primary ray sees (prt.h)
+    float4* d_dn = nullptr;
+    float* d_dn_g = nullptr;
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -186,6 +193,10 @@ static void free_frame(prt_ctx* c) {
     p = c->d_adapt; free_dev(p); c->d_adapt = nullptr;
     p = c->d_live; free_dev(p); c->d_live = nullptr;
     p = c->d_live_aux; free_dev(p); c->d_live_aux = nullptr;
+    p = c->d_guides; free_dev(p); c->d_guides = nullptr;
+    p = c->d_dn; free_dev(p); c->d_dn = nullptr;
+    p = c->d_dn_g; free_dev(p); c->d_dn_g = nullptr;
+    c->guides_valid = false;
     for (int j = 0; j < prt_ctx::MAX_SUB; ++j) {
         p = c->d_tile_order[j]; free_dev(p); c->d_tile_order[j] = nullptr;
         p = c->d_tile_cost[j]; free_dev(p); c->d_tile_cost[j] = nullptr;
@@ -247,6 +258,7 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     (void)hipStreamSynchronize(c->stream);
     // from here on the old buffers are being replaced: the context has no scene until every upload has succeeded
     c->have_scene = false;
+    c->guides_valid = false;
     const float* env = c->sc.env; const int env_w = c->sc.env_w, env_h = c->sc.env_h;    // the environment map survives scene uploads
     const float* env_rows = c->sc.env_cdf_rows; const float* env_cols = c->sc.env_cdf_cols;
     c->sc = DevScene{};
@@ -281,6 +293,7 @@ extern "C" int prt_set_camera(prt_ctx* c, const prt_camera* cam) {
     if (!cam) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_camera: null camera");
     make_dev_camera(*cam, c->cam);
     c->have_cam = true;
+    c->guides_valid = false;
     for (int j = 0; j < prt_ctx::MAX_SUB; ++j) c->have_order[j] = false;      // (tile costs are the view's)
     return PRT_OK;
 }
@@ -290,6 +303,7 @@ extern "C" int prt_upload_envmap(prt_ctx* c, const float* rgb, int w, int h) {
     if (!rgb || w <= 0 || h <= 0) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_envmap: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->guides_valid = false;
     free_dev(c->d_env);
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     HIPCHK(c, hipMalloc(&c->d_env, bytes));
@@ -378,6 +392,7 @@ extern "C" int prt_reset(prt_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->fb, 0, c->npix * 16, c->stream));
     if (c->d_adapt) HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, c->npix * sizeof(float2), c->stream));
     c->fresh = true;
+    c->stats_valid = false;
     return PRT_OK;
 }
 
@@ -468,6 +483,7 @@ extern "C" int prt_render_frames(prt_ctx* c, uint32_t first_frame, uint32_t n_fr
     c->stats.launches = 0; c->stats.frames = 0; c->stats.kernel_ms = 0.0; c->stats.kernel_sum_ms = 0.0; c->stats.concurrent = 1;
     if (!n_frames) return PRT_OK;
     c->fresh = false;
+    c->stats_valid = false;
     if ((rc = ensure_seeds(c, seed_pairs, n_frames))) return rc;
     const unsigned step = c->frames_per_launch ? c->frames_per_launch : (c->sc.n_pairs > 65536u ? 4096u : 512u);
     const int K = sub_parts(c, n_frames);
@@ -500,6 +516,7 @@ extern "C" int prt_render_spp(prt_ctx* c, uint32_t spp, uint32_t max_frames, con
     c->stats.launches = 0; c->stats.frames = 0; c->stats.kernel_ms = 0.0; c->stats.kernel_sum_ms = 0.0; c->stats.concurrent = 1;
     if ((rc = ensure_seeds(c, seed_pairs, max_frames))) return rc;
     c->fresh = false;
+    c->stats_valid = false;
     const unsigned step = c->frames_per_launch ? c->frames_per_launch : (c->sc.n_pairs > 65536u ? 4096u : 512u);
     const int K = sub_parts(c, 8ull * spp);            // (a path takes 4.4 ... 7.2 segments on the BASELINE scenes)
     c->stats.concurrent = (uint32_t)K;
@@ -667,6 +684,7 @@ extern "C" int prt_render_adaptive(prt_ctx* c, const prt_adaptive* a, uint32_t m
     if (!c->d_live) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_live), c->npix * sizeof(uint32_t)));
     if (!c->d_live_aux) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_live_aux), (n_waves + 1) * sizeof(uint32_t)));
     c->fresh = false;
+    c->stats_valid = true;                       // (prt_denoise PRT_DENOISE_VAR_STATS)
     const unsigned step = c->frames_per_launch ? c->frames_per_launch : (c->sc.n_pairs > 65536u ? 4096u : 512u);
     const int K = sub_parts(c, 8ull * a->max_spp);
     c->stats.concurrent = (uint32_t)K;
@@ -775,6 +793,71 @@ extern "C" int prt_get_adaptive_report(prt_ctx* c, prt_adaptive_report* out) {
     CTX_CHECK(c);
     if (!out) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_get_adaptive_report: null");
     *out = c->arep;
+    return PRT_OK;
+}
+
+extern "C" int prt_render_guides(prt_ctx* c, uint32_t samples) {
+    CTX_CHECK(c);
+    int rc = ready(c, "prt_render_guides");
+    if (rc) return rc;
+    if (samples < 1 || samples > 64) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_guides: samples must be 1 .. 64");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->guides_valid = false;
+    if (!c->d_guides) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_guides), c->npix * 2 * sizeof(float4)));
+    launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->guides_valid = true;
+    return PRT_OK;
+}
+
+extern "C" int prt_read_guides(prt_ctx* c, float* out8) {
+    CTX_CHECK(c);
+    if (!out8 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_guides: bad arguments");
+    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_guides: no guides for this scene, camera, map and frame (prt_render_guides)");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(out8, c->d_guides, c->npix * 2 * sizeof(float4), hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
+                         PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
+    if (params) p = *params;
+    if (p.passes < 1 || p.passes > 8) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise: passes must be 1 .. 8");
+    if (!(p.sigma_l > 0.0f) || !(p.sigma_n > 0.0f) || !(p.sigma_z > 0.0f) || !(p.sigma_a > 0.0f))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise: every sigma must be > 0 (and not NaN)");
+    if (p.var_source > PRT_DENOISE_VAR_SPATIAL) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise: unknown var_source");
+    int rc = ready(c, "prt_denoise");
+    if (rc) return rc;
+    if (c->row0 != 0 || c->rows != c->full_height || c->n_parts != 1)
+        return fail(c, PRT_ERR_UNSUPPORTED, "prt_denoise: the filter needs the whole frame (tile and row-block contexts are refused)");
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_denoise: a debug view is not a picture to filter");
+    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_denoise: no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_denoise: nothing rendered since the reset");
+    const bool stats = c->stats_valid && c->d_adapt;
+    if (p.var_source == PRT_DENOISE_VAR_STATS && !stats)
+        return fail(c, PRT_ERR_NOT_READY, "prt_denoise: PRT_DENOISE_VAR_STATS needs the last render since the reset to be prt_render_adaptive");
+    const bool spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL || (p.var_source == PRT_DENOISE_VAR_AUTO && !stats);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
+    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
+    float4* out = c->d_dn + 2 * c->npix;
+    launch_denoise(c->fb, c->S.q4, c->d_adapt, spatial, c->d_guides, c->width, c->rows, p, c->d_dn, c->d_dn + c->npix, c->d_dn_g, out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (rgba8) {
+        unsigned char* d = nullptr;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), c->npix * 4));
+        launch_tonemap(out, d, frame_args(c, 1, 0, nullptr, 0, false), c->stream);
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(rgba8, d, c->npix * 4, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rgba) HIPCHK(c, hipMemcpy(rgba, out, c->npix * 16, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -900,6 +983,7 @@ extern "C" int prt_write_state(prt_ctx* c, const prt_path_state* state) {
     HIPCHK(c, e);
     c->state_undefined = false;
     c->fresh = false;
+    c->stats_valid = false;
     return PRT_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "prt.h"
 #include "prt_types.h"
 #include "pt_layout.h"
 
@@ -56,5 +57,11 @@ void launch_count(const DevState& S, size_t n, unsigned spp, unsigned long long*
 // prt_render_adaptive: the local ids of the n-pixel frame's pixels that the adaptive freeze rule (max_spp, DevState::q4.w bit 31) has not frozen,
 // in increasing order, into list; their number into *count (device).  wave_off: ceil(n / 64) words of scratch
 void launch_live_list(const DevState& S, size_t n, unsigned max_spp, uint32_t* wave_off, uint32_t* list, uint32_t* count, hipStream_t stream);
+// pt_denoise.hip.  prt_render_guides: `samples` guide samples per pixel of the frame part of `fa` into out (2 float4 per pixel: {albedo, coverage},
+// {normal, depth}).  prt_denoise: the filter of prt.h on the full frame W x H, out = filtered rgba (alpha of fb); buf0 / buf1: W x H float4,
+// g: W x H float of scratch
+void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream);
+void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
+                    const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
 
 }  // namespace prt

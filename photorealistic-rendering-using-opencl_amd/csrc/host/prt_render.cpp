@@ -4,6 +4,8 @@
 // (frame counter from 1, two rand() values per frame after two consumed at start-up), with the
 // GLFW loop replaced by "-frames N" or "-spp N" (with "-adaptive E [-min-spp M] [-abs-floor F] [-spp-map file.pfm]": adaptive sampling,
 // -spp the maximum) and PrtSc replaced by "-out file.{png,hdr,pfm}" (default render.png / render.hdr by -encoder, as saveImage()).
+// "-denoise" writes the picture through prt_denoise (guides of "-guide-spp K" samples, default 4; with -adaptive the variance comes from
+// the stats plane); "-guides-out base" writes base_albedo.pfm, base_normal.pfm and base_depth.pfm.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -92,6 +94,9 @@ int main(int argc, char** argv) {
     float adaptive = -1.0f, abs_floor = 0.0f;                      // -adaptive <rel_err>: prt_render_adaptive between -min-spp and -spp paths
     unsigned min_spp = 16;
     std::string spp_map_path;                                      // -spp-map file.pfm: paths per pixel of the adaptive render
+    bool denoise = false;                                          // -denoise: the output goes through prt_denoise
+    unsigned guide_spp = 4;                                        // -guide-spp K: guide samples per pixel
+    std::string guides_out;                                        // -guides-out base: base_{albedo,normal,depth}.pfm
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -112,6 +117,9 @@ int main(int argc, char** argv) {
         else if (a == "-abs-floor") abs_floor = (float)std::atof(next());
         else if (a == "-spp-map") spp_map_path = next();
         else if (a == "-device") device = std::atoi(next());
+        else if (a == "-denoise") denoise = true;
+        else if (a == "-guide-spp") guide_spp = (unsigned)std::atoi(next());
+        else if (a == "-guides-out") guides_out = next();
     }
     prt_ctx* ctx = nullptr;
     try {
@@ -192,6 +200,22 @@ int main(int argc, char** argv) {
                 if (!write_pfm(spp_map_path, map, window_width, window_height)) { std::fprintf(stderr, "cannot write %s\n", spp_map_path.c_str()); return 1; }
             }
         }
+        if (denoise || !guides_out.empty()) CHECK(prt_render_guides(ctx, guide_spp));
+        if (!guides_out.empty()) {                                 // the guide plane as three PFMs (framebuffer order: bottom-up, as PFM)
+            const size_t npix = (size_t)window_width * window_height;
+            std::vector<float> g(npix * 8), alb(npix * 4), nrm(npix * 4), dep(npix * 4);
+            CHECK(prt_read_guides(ctx, g.data()));
+            for (size_t k = 0; k < npix; ++k)
+                for (int c = 0; c < 3; ++c) { alb[4 * k + c] = g[8 * k + c]; nrm[4 * k + c] = g[8 * k + 4 + c]; dep[4 * k + c] = g[8 * k + 7]; }
+            const std::pair<const char*, const std::vector<float>*> files[3] = {{"_albedo.pfm", &alb}, {"_normal.pfm", &nrm}, {"_depth.pfm", &dep}};
+            for (const auto& f : files)
+                if (!write_pfm(guides_out + f.first, *f.second, window_width, window_height)) {
+                    std::fprintf(stderr, "cannot write %s\n", (guides_out + f.first).c_str());
+                    prt_destroy(ctx);
+                    return 1;
+                }
+        }
+        if (denoise) CHECK(prt_denoise(ctx, nullptr, rgba.data(), nullptr));       // (the variance source: the stats plane after -adaptive)
         // saveImage(), include/GL/cl_gl_interop.h:144-160: -encoder 0 -> render.png (the displayed, tonemapped picture), -encoder 1 ->
         // render.hdr (the linear one); -out <file> picks the name, and the format by its extension (.png / .hdr / .pfm)
         if (out_path.empty()) out_path = encoder == 1 ? "render.hdr" : "render.png";
@@ -199,7 +223,8 @@ int main(int argc, char** argv) {
         bool ok;
         if (ends_with(".png")) {                                   // encoder 0 of the reference: the tonemapped picture
             std::vector<uint8_t> ldr((size_t)window_width * window_height * 4);
-            CHECK(prt_tonemap_rgba8(ctx, ldr.data()));
+            if (denoise) CHECK(prt_denoise(ctx, nullptr, nullptr, ldr.data()));
+            else CHECK(prt_tonemap_rgba8(ctx, ldr.data()));
             ok = write_png(out_path, ldr, window_width, window_height);
         } else if (ends_with(".hdr")) {                            // encoder 1: the linear picture as Radiance RGBE
             char herr[256] = "";
