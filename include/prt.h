@@ -279,6 +279,60 @@ typedef struct prt_denoise_params {
 } prt_denoise_params;
 int prt_denoise(prt_ctx* ctx, const prt_denoise_params* params, float* rgba, uint8_t* rgba8);
 
+/* Temporal reprojection: the temporal part of SVGF (Schied et al. 2017) in front of prt_denoise's filter, for a moving camera (the reference
+ * restarts accumulation from black on every camera move: src/main.cpp:283-291).  The intended loop per displayed frame: prt_set_camera,
+ * prt_reset, render N spp with fresh seeds, prt_render_guides, prt_denoise_temporal.  For a still camera plain accumulation (no reset) plus
+ * prt_denoise is the better path: the mean of all paths has less variance than any exponential average of it.
+ * Inputs: the framebuffer colour c (the mean since the last prt_reset), the current guides {a, cov, n, z} and the history: per pixel
+ * {c_h, n_h, m1, m2}, the guides of the previous call and its camera basis (DevCamera of camera_basis: P = position, M = middle,
+ * Hz = horizontal, Vt = vertical).  At the end of each call the history takes the current guides and camera.  L(c) as in prt_denoise.
+ *   World point of pixel p = (x, y): d = normalize(onPlane(p) - position), onPlane = create_cam_ray's expression at the pixel centre
+ *     (sx = x / (W-1), sy = (H-1-y) / (H-1)), with the current camera.  cov_p > 0: X = position + z_p d -- the pinhole centre ray (with a
+ *     lens an approximation; after a mirror or glass chain the virtual point behind the surface).  cov_p = 0: the pixel reprojects as the
+ *     direction d (a point at infinity).
+ *   Projection into the previous camera: e = X - P (d for a direction); no history when dot(e, M - P) <= 0.  f = M - P,
+ *     q = e dot(f, f) / dot(e, f) - f, a = dot(q, Hz) / dot(Hz, Hz), b = dot(q, Vt) / dot(Vt, Vt); x' = (a + 1)/2 (W-1),
+ *     y' = (H-1) - (b + 1)/2 (H-1) (the inverse of create_cam_ray's centre ray); no history unless -1 < x' < W and -1 < y' < H.
+ *   Taps: the 2x2 around (x', y'): x0 = floor(x'), y0 = floor(y'), fx = x' - x0, fy = y' - y0, bilinear weights (1-fx)(1-fy), fx (1-fy),
+ *     (1-fx) fy, fx fy.  A tap t is valid when it lies in the frame, its stored colour is finite, the coverages agree (cov_p > 0 and
+ *     cov_prev(t) > 0, or both 0) and, when covered, |z_prev(t) - |X - P|| <= tau_z |X - P| + grad_p (grad_p: prt_denoise's depth
+ *     gradient of the current guides) and dot(n_p, n_prev(t)) >= cos_n.  No history when the sum w of the valid taps' weights is < 0.01, the
+ *     history is empty or the point is behind the previous camera.
+ *   Accumulation.  With history: c_h, m1_h, m2_h, n_h = the sums over the valid taps of w times the stored values, divided by sum w;
+ *     n = min(n_h + 1, history_cap), ac = max(alpha_color, 1/n), am = max(alpha_moments, 1/n), c_i = c_h + ac (c - c_h),
+ *     m1 = m1_h + am (L - m1_h), m2 = m2_h + am (L^2 - m2_h), L = L(c).  Without history: n = 1, c_i = c, m1 = L, m2 = L^2.  A pixel whose
+ *     c is not finite keeps it: c_i = c, and its history restarts (n = 1).
+ *   Variance: v = max(m2 - m1^2, 0) when n >= 4, else prt_denoise's v of the current frame for the var_source of `spatial`.
+ *   Filter: {c_i, v} go through prt_denoise's passes unchanged, with the current guides; output as prt_denoise's (rgba with the framebuffer's
+ *     alpha, rgba8 its display transform; either may be NULL).  The history stores n, m1, m2, v and the colour
+ *       PRT_TEMPORAL_FEEDBACK_ATROUS      (default, SVGF) the output of a-trous pass 0
+ *       PRT_TEMPORAL_FEEDBACK_INTEGRATED  c_i.
+ * f32 arithmetic, deterministic, no atomics.  The call reads the framebuffer, the state, the stats plane and the guides and writes none of them.
+ * History lifetime: allocated on first use (96 bytes per pixel); prt_reset and prt_set_camera keep it; prt_upload_scene, prt_upload_envmap,
+ * prt_resize, prt_set_tile, prt_set_row_blocks and prt_reset_history empty it.  prt_read_history: per pixel 8 floats {c.rgb, n, m1, m2, v, 0},
+ * framebuffer order; PRT_ERR_NOT_READY while the history is empty.
+ * Refused as prt_denoise (NOT_READY without valid guides or without a render since the reset, UNSUPPORTED on tile and row-block contexts and
+ * with a debug view), and PRT_ERR_INVALID_ARGUMENT for any parameter of either struct out of range or NaN or an unknown feedback.
+ * NULL params = the defaults (the temporal ones are SVGF's). */
+#define PRT_TEMPORAL_FEEDBACK_INTEGRATED 0u
+#define PRT_TEMPORAL_FEEDBACK_ATROUS 1u
+#define PRT_TEMPORAL_DEFAULT_ALPHA_COLOR 0.2f
+#define PRT_TEMPORAL_DEFAULT_ALPHA_MOMENTS 0.2f
+#define PRT_TEMPORAL_DEFAULT_TAU_Z 0.05f
+#define PRT_TEMPORAL_DEFAULT_COS_N 0.9f
+#define PRT_TEMPORAL_DEFAULT_HISTORY_CAP 32u
+typedef struct prt_temporal_params {
+    float alpha_color;     /* [0, 1]: blend floor of the colour; 0 = a plain running mean up to history_cap */
+    float alpha_moments;   /* [0, 1] */
+    float tau_z;           /* > 0: relative depth tolerance of a history tap */
+    float cos_n;           /* [-1, 1]: minimum n_cur . n_prev of a history tap */
+    uint32_t history_cap;  /* >= 1 */
+    uint32_t feedback;     /* PRT_TEMPORAL_FEEDBACK_* */
+} prt_temporal_params;
+int prt_denoise_temporal(prt_ctx* ctx, const prt_denoise_params* spatial, const prt_temporal_params* temporal, float* rgba, uint8_t* rgba8);
+int prt_read_history(prt_ctx* ctx, float* out8);
+int prt_reset_history(prt_ctx* ctx);
+
 /* Scheduling knob of the render kernel (no counterpart in the reference; results do not depend on it, tests check
  * that): a wave ends a BVH-walk phase once fewer than `lanes` of its 64 lanes are still walking (and fewer than wait for the
  * phase to end); the lanes cut off resume in the wave's next phase.  1 = every walk runs to its end (lock step).

@@ -15,14 +15,14 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import DENOISE_DEFAULTS, DenoiseParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
+from ._capi import DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -321,6 +321,33 @@ class Renderer:
             out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
             self._chk(self.lib.prt_denoise(self.ctx, C.byref(p), out.ctypes.data_as(C.c_void_p), None), "prt_denoise")
         return out
+
+    _FEEDBACK = {"integrated": _capi.PRT_TEMPORAL_FEEDBACK_INTEGRATED, "atrous": _capi.PRT_TEMPORAL_FEEDBACK_ATROUS}
+
+    def denoise_temporal(self, passes=DENOISE_DEFAULTS["passes"], var_source="auto", sigma_l=DENOISE_DEFAULTS["sigma_l"],
+                         sigma_n=DENOISE_DEFAULTS["sigma_n"], sigma_z=DENOISE_DEFAULTS["sigma_z"], sigma_a=DENOISE_DEFAULTS["sigma_a"],
+                         alpha_color=TEMPORAL_DEFAULTS["alpha_color"], alpha_moments=TEMPORAL_DEFAULTS["alpha_moments"],
+                         tau_z=TEMPORAL_DEFAULTS["tau_z"], cos_n=TEMPORAL_DEFAULTS["cos_n"], history_cap=TEMPORAL_DEFAULTS["history_cap"],
+                         feedback=TEMPORAL_DEFAULTS["feedback"], tonemap=False):
+        """prt_denoise_temporal: the history reprojected into this camera and blended with the framebuffer, then denoise()'s filter (prt.h).
+        Takes denoise()'s keywords plus the temporal ones; feedback: "atrous" (pass 0's output becomes the history) | "integrated".
+        Returns what denoise() returns"""
+        p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
+        t = TemporalParams(float(alpha_color), float(alpha_moments), float(tau_z), float(cos_n), int(history_cap), self._FEEDBACK[feedback])
+        out = np.zeros((self.rows, self.width, 4), dtype=np.uint8 if tonemap else np.float32)
+        ptr = out.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.prt_denoise_temporal(self.ctx, C.byref(p), C.byref(t), None if tonemap else ptr, ptr if tonemap else None),
+                  "prt_denoise_temporal")
+        return out
+
+    def read_history(self):
+        """the temporal history: float32 [rows, width, 8] = {c.rgb, n, m1, m2, v, 0} per pixel, framebuffer order"""
+        out = np.zeros((self.rows, self.width, 8), dtype=np.float32)
+        self._chk(self.lib.prt_read_history(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_history")
+        return out
+
+    def reset_history(self):
+        self._chk(self.lib.prt_reset_history(self.ctx), "prt_reset_history")
 
     def set_walk_min_lanes(self, lanes):
         self._chk(self.lib.prt_set_walk_min_lanes(self.ctx, int(lanes)), "prt_set_walk_min_lanes")

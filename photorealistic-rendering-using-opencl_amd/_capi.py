@@ -80,6 +80,16 @@ PRT_DENOISE_VAR_AUTO, PRT_DENOISE_VAR_STATS, PRT_DENOISE_VAR_SPATIAL = 0, 1, 2
 DENOISE_DEFAULTS = dict(passes=5, sigma_l=3.0, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1)
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("alpha_color", C.c_float), ("alpha_moments", C.c_float), ("tau_z", C.c_float), ("cos_n", C.c_float),
+                ("history_cap", C.c_uint32), ("feedback", C.c_uint32)]
+
+
+# prt_temporal_params::feedback and the defaults of a NULL params pointer (include/prt.h)
+PRT_TEMPORAL_FEEDBACK_INTEGRATED, PRT_TEMPORAL_FEEDBACK_ATROUS = 0, 1
+TEMPORAL_DEFAULTS = dict(alpha_color=0.2, alpha_moments=0.2, tau_z=0.05, cos_n=0.9, history_cap=32, feedback="atrous")
+
+
 assert C.sizeof(Material) == 64 and C.sizeof(Mesh) == 256 and C.sizeof(BvhNode) == 36 and C.sizeof(Camera) == 80
 
 # numpy view of the 112-byte RTD (prt_path_state)
@@ -108,6 +118,9 @@ PRT_API = [
     ("prt_render_guides", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_read_guides", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_denoise", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]),
+    ("prt_denoise_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]),
+    ("prt_read_history", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_reset_history", C.c_int, [C.c_void_p]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("prt_kernel_variant", C.c_char_p, [C.c_void_p]),

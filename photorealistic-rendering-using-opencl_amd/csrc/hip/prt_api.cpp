@@ -108,6 +108,14 @@ struct prt_ctx {
     bool guides_valid = false;                     // cleared by everything that changes what a primary ray sees (prt.h)
     float4* d_dn = nullptr;
     float* d_dn_g = nullptr;
+    // prt_denoise_temporal (pt_temporal.hip): the history, allocated on first use with the frame's size, freed with the frame.  d_hist holds
+    // two halves of {c, n} and {m1, m2, v, 0} planes (half hist_cur is the last call's, the other one is written by the next call: a flip of
+    // hist_cur swaps them), d_hist_guides the guides of the last call; hist_cam its camera
+    float4* d_hist = nullptr;
+    float4* d_hist_guides = nullptr;
+    int hist_cur = 0;
+    bool hist_valid = false;                       // emptied by everything prt.h lists
+    DevCamera hist_cam{};
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -196,7 +204,10 @@ static void free_frame(prt_ctx* c) {
     p = c->d_guides; free_dev(p); c->d_guides = nullptr;
     p = c->d_dn; free_dev(p); c->d_dn = nullptr;
     p = c->d_dn_g; free_dev(p); c->d_dn_g = nullptr;
+    p = c->d_hist; free_dev(p); c->d_hist = nullptr;
+    p = c->d_hist_guides; free_dev(p); c->d_hist_guides = nullptr;
     c->guides_valid = false;
+    c->hist_valid = false;
     for (int j = 0; j < prt_ctx::MAX_SUB; ++j) {
         p = c->d_tile_order[j]; free_dev(p); c->d_tile_order[j] = nullptr;
         p = c->d_tile_cost[j]; free_dev(p); c->d_tile_cost[j] = nullptr;
@@ -259,6 +270,7 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     // from here on the old buffers are being replaced: the context has no scene until every upload has succeeded
     c->have_scene = false;
     c->guides_valid = false;
+    c->hist_valid = false;
     const float* env = c->sc.env; const int env_w = c->sc.env_w, env_h = c->sc.env_h;    // the environment map survives scene uploads
     const float* env_rows = c->sc.env_cdf_rows; const float* env_cols = c->sc.env_cdf_cols;
     c->sc = DevScene{};
@@ -304,6 +316,7 @@ extern "C" int prt_upload_envmap(prt_ctx* c, const float* rgb, int w, int h) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->guides_valid = false;
+    c->hist_valid = false;
     free_dev(c->d_env);
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     HIPCHK(c, hipMalloc(&c->d_env, bytes));
@@ -821,32 +834,29 @@ extern "C" int prt_read_guides(prt_ctx* c, float* out8) {
     return PRT_OK;
 }
 
-extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* rgba, uint8_t* rgba8) {
-    CTX_CHECK(c);
-    prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
-                         PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
-    if (params) p = *params;
-    if (p.passes < 1 || p.passes > 8) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise: passes must be 1 .. 8");
+// the checks prt_denoise and prt_denoise_temporal share; *spatial: the variance source the call resolves to
+static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* who, bool* spatial) {
+    const std::string w(who);
+    if (p.passes < 1 || p.passes > 8) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": passes must be 1 .. 8");
     if (!(p.sigma_l > 0.0f) || !(p.sigma_n > 0.0f) || !(p.sigma_z > 0.0f) || !(p.sigma_a > 0.0f))
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise: every sigma must be > 0 (and not NaN)");
-    if (p.var_source > PRT_DENOISE_VAR_SPATIAL) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise: unknown var_source");
-    int rc = ready(c, "prt_denoise");
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": every sigma must be > 0 (and not NaN)");
+    if (p.var_source > PRT_DENOISE_VAR_SPATIAL) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown var_source");
+    int rc = ready(c, who);
     if (rc) return rc;
     if (c->row0 != 0 || c->rows != c->full_height || c->n_parts != 1)
-        return fail(c, PRT_ERR_UNSUPPORTED, "prt_denoise: the filter needs the whole frame (tile and row-block contexts are refused)");
-    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_denoise: a debug view is not a picture to filter");
-    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_denoise: no guides for this scene, camera, map and frame (prt_render_guides)");
-    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_denoise: nothing rendered since the reset");
+        return fail(c, PRT_ERR_UNSUPPORTED, w + ": the filter needs the whole frame (tile and row-block contexts are refused)");
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, w + ": a debug view is not a picture to filter");
+    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, w + ": no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, w + ": nothing rendered since the reset");
     const bool stats = c->stats_valid && c->d_adapt;
     if (p.var_source == PRT_DENOISE_VAR_STATS && !stats)
-        return fail(c, PRT_ERR_NOT_READY, "prt_denoise: PRT_DENOISE_VAR_STATS needs the last render since the reset to be prt_render_adaptive");
-    const bool spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL || (p.var_source == PRT_DENOISE_VAR_AUTO && !stats);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
-    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
-    float4* out = c->d_dn + 2 * c->npix;
-    launch_denoise(c->fb, c->S.q4, c->d_adapt, spatial, c->d_guides, c->width, c->rows, p, c->d_dn, c->d_dn + c->npix, c->d_dn_g, out, c->stream);
-    HIPCHK(c, hipGetLastError());
+        return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs the last render since the reset to be prt_render_adaptive");
+    *spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL || (p.var_source == PRT_DENOISE_VAR_AUTO && !stats);
+    return PRT_OK;
+}
+
+// the filtered plane `out` to the caller: rgba (prt_read_framebuffer's layout) and / or rgba8 (prt_tonemap_rgba8's transform); both may be NULL
+static int denoise_output(prt_ctx* c, const float4* out, float* rgba, uint8_t* rgba8) {
     if (rgba8) {
         unsigned char* d = nullptr;
         HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), c->npix * 4));
@@ -858,6 +868,91 @@ extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* 
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (rgba) HIPCHK(c, hipMemcpy(rgba, out, c->npix * 16, hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
+                         PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
+    if (params) p = *params;
+    bool spatial = false;
+    int rc = denoise_checks(c, p, "prt_denoise", &spatial);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
+    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
+    float4* out = c->d_dn + 2 * c->npix;
+    launch_denoise(c->fb, c->S.q4, c->d_adapt, spatial, c->d_guides, c->width, c->rows, p, c->d_dn, c->d_dn + c->npix, c->d_dn_g, out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return denoise_output(c, out, rgba, rgba8);
+}
+
+extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
+                         PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
+    if (spatial) p = *spatial;
+    prt_temporal_params t{PRT_TEMPORAL_DEFAULT_ALPHA_COLOR, PRT_TEMPORAL_DEFAULT_ALPHA_MOMENTS, PRT_TEMPORAL_DEFAULT_TAU_Z, PRT_TEMPORAL_DEFAULT_COS_N,
+                          PRT_TEMPORAL_DEFAULT_HISTORY_CAP, PRT_TEMPORAL_FEEDBACK_ATROUS};
+    if (temporal) t = *temporal;
+    if (!(t.alpha_color >= 0.0f && t.alpha_color <= 1.0f) || !(t.alpha_moments >= 0.0f && t.alpha_moments <= 1.0f))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: alpha_color and alpha_moments must be in [0, 1]");
+    if (!(t.tau_z > 0.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: tau_z must be > 0 (and not NaN)");
+    if (!(t.cos_n >= -1.0f && t.cos_n <= 1.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: cos_n must be in [-1, 1]");
+    if (t.history_cap < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: history_cap must be >= 1");
+    if (t.feedback > PRT_TEMPORAL_FEEDBACK_ATROUS) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: unknown feedback");
+    bool spatial_var = false;
+    int rc = denoise_checks(c, p, "prt_denoise_temporal", &spatial_var);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
+    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
+    if (!c->d_hist) {
+        c->hist_valid = false;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_hist), c->npix * 4 * sizeof(float4)));
+    }
+    if (!c->d_hist_guides) {
+        c->hist_valid = false;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_hist_guides), c->npix * 2 * sizeof(float4)));
+    }
+    float4* half_prev = c->d_hist + 2 * c->npix * (size_t)c->hist_cur;          // {c, n} plane, then {m1, m2, v, 0}
+    float4* half_next = c->d_hist + 2 * c->npix * (size_t)(c->hist_cur ^ 1);
+    TemporalHistory h;
+    h.cn_prev = half_prev; h.m_prev = half_prev + c->npix; h.guides_prev = c->d_hist_guides; h.cam_prev = c->hist_cam; h.valid = c->hist_valid;
+    h.cn = half_next; h.m = half_next + c->npix;
+    float4* out = c->d_dn + 2 * c->npix;
+    c->hist_valid = false;                         // (until the call has run: a failure leaves the history empty)
+    launch_denoise_temporal(c->fb, c->S.q4, c->d_adapt, spatial_var, c->d_guides, c->width, c->rows, p, t, c->cam, h, c->d_dn,
+                            c->d_dn + c->npix, c->d_dn_g, out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->d_hist_guides, c->d_guides, c->npix * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->hist_cur ^= 1;
+    c->hist_cam = c->cam;
+    c->hist_valid = true;
+    return denoise_output(c, out, rgba, rgba8);
+}
+
+extern "C" int prt_read_history(prt_ctx* c, float* out8) {
+    CTX_CHECK(c);
+    if (!out8 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_history: bad arguments");
+    if (!c->hist_valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_history: the history is empty (prt_denoise_temporal)");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    std::vector<float4> h(2 * c->npix);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_hist + 2 * c->npix * (size_t)c->hist_cur, 2 * c->npix * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < c->npix; ++k) {
+        const float4 a = h[k], b = h[c->npix + k];
+        float* o = out8 + 8 * k;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    }
+    return PRT_OK;
+}
+
+extern "C" int prt_reset_history(prt_ctx* c) {
+    CTX_CHECK(c);
+    c->hist_valid = false;
     return PRT_OK;
 }
 

@@ -187,19 +187,30 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const float4* __restrict
     out[id] = r;
 }
 
+// the filter's pieces for prt_denoise_temporal (pt_temporal.hip): {rgb, v} of the framebuffer into out, and a-trous pass i (its Gaussian
+// into g first) from `in` to `out` -- alpha_src non-null for the last pass
+void launch_denoise_var(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, int W, int H, float4* out, hipStream_t stream) {
+    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+    hipLaunchKernelGGL(dn_var_kernel, grd, blk, 0, stream, fb, q4, adapt, spatial ? 1 : 0, W, H, out);
+}
+void launch_denoise_pass(const float4* in, const float4* guides, int W, int H, const prt_denoise_params& p, unsigned i, float* g,
+                         const float4* alpha_src, float4* out, hipStream_t stream) {
+    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+    DnParams P;
+    P.step = 1 << i; P.sigma_l = p.sigma_l; P.sigma_n = p.sigma_n; P.sigma_z = p.sigma_z; P.inv_sigma_a2 = 1.0f / (p.sigma_a * p.sigma_a);
+    hipLaunchKernelGGL(dn_gauss_kernel, grd, blk, 0, stream, in, W, H, g);
+    hipLaunchKernelGGL(dn_atrous_kernel, grd, blk, 0, stream, in, g, guides, W, H, P, alpha_src, out);
+}
+
 // passes of the filter: var -> (gauss, a-trous) x passes, ping-pong between buf0 and buf1, the last pass into `out` (rgba of the frame)
 void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                     const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
-    hipLaunchKernelGGL(dn_var_kernel, grd, blk, 0, stream, fb, q4, adapt, spatial ? 1 : 0, W, H, buf0);
+    launch_denoise_var(fb, q4, adapt, spatial, W, H, buf0, stream);
     float4* cur = buf0;
     float4* nxt = buf1;
     for (unsigned i = 0; i < p.passes; ++i) {
-        DnParams P;
-        P.step = 1 << i; P.sigma_l = p.sigma_l; P.sigma_n = p.sigma_n; P.sigma_z = p.sigma_z; P.inv_sigma_a2 = 1.0f / (p.sigma_a * p.sigma_a);
         const bool last = i + 1 == p.passes;
-        hipLaunchKernelGGL(dn_gauss_kernel, grd, blk, 0, stream, cur, W, H, g);
-        hipLaunchKernelGGL(dn_atrous_kernel, grd, blk, 0, stream, cur, g, guides, W, H, P, last ? fb : nullptr, last ? out : nxt);
+        launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, last ? out : nxt, stream);
         float4* t = cur; cur = nxt; nxt = t;
     }
 }

@@ -63,5 +63,23 @@ void launch_live_list(const DevState& S, size_t n, unsigned max_spp, uint32_t* w
 void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream);
 void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                     const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
+// ... its pieces: dn_var_kernel's {rgb, v} into out; a-trous pass i (step 2^i, its Gaussian into g first) from `in` into `out`, with the
+// framebuffer's alpha when alpha_src is non-null (the last pass)
+void launch_denoise_var(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, int W, int H, float4* out, hipStream_t stream);
+void launch_denoise_pass(const float4* in, const float4* guides, int W, int H, const prt_denoise_params& p, unsigned i, float* g,
+                         const float4* alpha_src, float4* out, hipStream_t stream);
+// pt_temporal.hip.  prt_denoise_temporal: the previous call's history (read) and the halves this call writes; `valid` false = empty history
+struct TemporalHistory {
+    const float4* cn_prev;          // {c.rgb, n} per pixel
+    const float4* m_prev;           // {m1, m2, v, 0}
+    const float4* guides_prev;      // the guides of the previous call (2 float4 per pixel)
+    DevCamera cam_prev;
+    bool valid;
+    float4* cn;                     // written by this call
+    float4* m;
+};
+void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
+                             const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
+                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
 
 }  // namespace prt

@@ -1,0 +1,149 @@
+// pt_temporal.hip -- temporal reprojection in front of the a-trous filter (prt_denoise_temporal; include/prt.h has the contract).
+// A translation unit of its own: no code object of the render kernels or of pt_denoise.hip changes with it.
+//
+//   tm_reproject_kernel  per pixel: the world point of the current guides, projected into the previous camera; the valid ones of the 2x2
+//                        bilinear taps of the previous history and guides blended with the framebuffer into {c_i, v} (the filter's input)
+//                        and the new history {c, n}, {m1, m2, v, 0}
+//   tm_feedback_kernel   PRT_TEMPORAL_FEEDBACK_ATROUS: a-trous pass 0's colour into the new history
+//
+// The history is double-buffered (taps read neighbours: never updated in place); the caller flips the two halves after each call.  16x16
+// workgroups, one lane per pixel, straight global loads as the filter's kernels: at 1080p the planes a call touches (~100 B per pixel) stay
+// in the L2 / Infinity Cache.  A pixel reads its 2x2 taps (2 guide float4 + 2 history float4 each) and its own and four neighbours' guides.
+#include "pt_device.h"
+#include "pt_launch.h"
+
+namespace prt {
+using namespace dev;
+
+struct TmParams { float alpha_color, alpha_moments, tau_z, cos_n, cap; int has_hist; };
+
+PT_DEV float tm_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+PT_DEV bool tm_finite3(float4 c) { return isfinite(c.x) && isfinite(c.y) && isfinite(c.z); }
+
+// prt_denoise's depth gradient (pt_denoise.hip dn_grad1): central / one-sided difference of z towards (x + sx, y + sy) and (x - sx, y - sy)
+PT_DEV float tm_grad1(const float4* __restrict__ gd, int x, int y, int sx, int sy, int W, int H, float zp) {
+    const int xa = x + sx, ya = y + sy, xb = x - sx, yb = y - sy;
+    const bool a_in = xa < W && ya < H, b_in = xb >= 0 && yb >= 0;
+    bool ha = false, hb = false;
+    float za = 0.0f, zb = 0.0f;
+    if (a_in) { const size_t q = (size_t)ya * W + xa; ha = gd[2 * q].w > 0.0f; za = gd[2 * q + 1].w; }
+    if (b_in) { const size_t q = (size_t)yb * W + xb; hb = gd[2 * q].w > 0.0f; zb = gd[2 * q + 1].w; }
+    if (ha && hb) return 0.5f * fabsf(za - zb);
+    if (ha) return fabsf(za - zp);
+    if (hb) return fabsf(zp - zb);
+    return 0.0f;
+}
+
+// fb: framebuffer; var: dn_var_kernel's {c, v} of the current frame (v for n < 4); gd / gd_prev: current / previous guides (2 float4 per
+// pixel); h_cn_prev / h_m_prev: previous history {c, n} / {m1, m2, v, 0}.  Out: {c_i, v} and the new history.
+__global__ __launch_bounds__(256) void tm_reproject_kernel(const float4* __restrict__ fb, const float4* __restrict__ var,
+                                                           const float4* __restrict__ gd, const float4* __restrict__ gd_prev,
+                                                           const float4* __restrict__ h_cn_prev, const float4* __restrict__ h_m_prev,
+                                                           const DevCamera cur, const DevCamera prev, int W, int H, const TmParams P,
+                                                           float4* __restrict__ out, float4* __restrict__ h_cn, float4* __restrict__ h_m) {
+    const int x = (int)(blockIdx.x * 16 + threadIdx.x), y = (int)(blockIdx.y * 16 + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const size_t id = (size_t)y * W + x;
+    const float4 c = fb[id];
+    const float L = tm_lum(c.x, c.y, c.z);
+    float sw = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, h1 = 0.0f, h2 = 0.0f;
+    if (P.has_hist && tm_finite3(c)) {
+        const float4 ap = gd[2 * id], np = gd[2 * id + 1];
+        const bool covp = ap.w > 0.0f;
+        // create_cam_ray's centre ray of the pixel (pt_device.h), then the point at its guide depth
+        const float sx = (float)x / (W - 1.0f);
+        const float sy = (float)(H - y - 1) / (H - 1.0f);
+        const f3 position = ld3(cur.position);
+        const f3 onPlane = ld3(cur.middle) + (ld3(cur.horizontal) * ((2 * sx) - 1)) + (ld3(cur.vertical) * ((2 * sy) - 1));
+        const f3 d = normalize(onPlane - position);
+        const f3 Pp = ld3(prev.position), Hz = ld3(prev.horizontal), Vt = ld3(prev.vertical);
+        const f3 f = ld3(prev.middle) - Pp;
+        const f3 e = covp ? (position + d * np.w) - Pp : d;
+        const float dist = covp ? length(e) : 0.0f;
+        const float ef = dot(e, f);
+        if (ef > 0.0f) {
+            const f3 q = e * (dot(f, f) / ef) - f;
+            const float a = dot(q, Hz) / dot(Hz, Hz), b = dot(q, Vt) / dot(Vt, Vt);
+            const float xp = (a + 1.0f) * 0.5f * (float)(W - 1);
+            const float yp = (float)(H - 1) - (b + 1.0f) * 0.5f * (float)(H - 1);
+            if (xp > -1.0f && xp < (float)W && yp > -1.0f && yp < (float)H) {
+                const float x0f = floorf(xp), y0f = floorf(yp);
+                const int x0 = (int)x0f, y0 = (int)y0f;
+                const float fx = xp - x0f, fy = yp - y0f;
+                const float grad = covp ? fmaxf(tm_grad1(gd, x, y, 1, 0, W, H, np.w), tm_grad1(gd, x, y, 0, 1, W, H, np.w)) : 0.0f;
+                const float ztol = P.tau_z * dist + grad;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
+                    if (tx < 0 || tx >= W || ty < 0 || ty >= H) continue;
+                    const size_t qi = (size_t)ty * W + tx;
+                    const float4 hc = h_cn_prev[qi];
+                    if (!tm_finite3(hc)) continue;
+                    if ((gd_prev[2 * qi].w > 0.0f) != covp) continue;
+                    if (covp) {
+                        const float4 nq = gd_prev[2 * qi + 1];
+                        if (!(fabsf(nq.w - dist) <= ztol)) continue;
+                        if (!(np.x * nq.x + np.y * nq.y + np.z * nq.z >= P.cos_n)) continue;
+                    }
+                    const float w = ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy);
+                    const float4 hm = h_m_prev[qi];
+                    sw += w;
+                    hr += w * hc.x; hg += w * hc.y; hb += w * hc.z; hn += w * hc.w;
+                    h1 += w * hm.x; h2 += w * hm.y;
+                }
+            }
+        }
+    }
+    float4 ci;
+    float n, m1, m2;
+    if (sw >= 0.01f) {
+        const float inv = 1.0f / sw;
+        const float chr = hr * inv, chg = hg * inv, chb = hb * inv, m1h = h1 * inv, m2h = h2 * inv;
+        n = fminf(hn * inv + 1.0f, P.cap);
+        const float ac = fmaxf(P.alpha_color, 1.0f / n), am = fmaxf(P.alpha_moments, 1.0f / n);
+        ci = make_float4(chr + ac * (c.x - chr), chg + ac * (c.y - chg), chb + ac * (c.z - chb), c.w);
+        m1 = m1h + am * (L - m1h);
+        m2 = m2h + am * (L * L - m2h);
+    } else {
+        n = 1.0f;
+        ci = c;
+        m1 = L;
+        m2 = L * L;
+    }
+    const float v = n >= 4.0f ? fmaxf(m2 - m1 * m1, 0.0f) : var[id].w;
+    out[id] = make_float4(ci.x, ci.y, ci.z, v);
+    h_cn[id] = make_float4(ci.x, ci.y, ci.z, n);
+    h_m[id] = make_float4(m1, m2, v, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void tm_feedback_kernel(const float4* __restrict__ pass0, int W, int H, float4* __restrict__ h_cn) {
+    const int x = (int)(blockIdx.x * 16 + threadIdx.x), y = (int)(blockIdx.y * 16 + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const size_t id = (size_t)y * W + x;
+    const float4 p = pass0[id];
+    h_cn[id] = make_float4(p.x, p.y, p.z, h_cn[id].w);
+}
+
+void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
+                             const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
+                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream) {
+    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+    launch_denoise_var(fb, q4, adapt, spatial, W, H, buf1, stream);
+    TmParams P;
+    P.alpha_color = t.alpha_color; P.alpha_moments = t.alpha_moments; P.tau_z = t.tau_z; P.cos_n = t.cos_n; P.cap = (float)t.history_cap;
+    P.has_hist = h.valid ? 1 : 0;
+    hipLaunchKernelGGL(tm_reproject_kernel, grd, blk, 0, stream, fb, buf1, guides, h.guides_prev, h.cn_prev, h.m_prev, cam, h.cam_prev, W, H,
+                       P, buf0, h.cn, h.m);
+    float4* cur = buf0;
+    float4* nxt = buf1;
+    for (unsigned i = 0; i < p.passes; ++i) {
+        const bool last = i + 1 == p.passes;
+        float4* dst = last ? out : nxt;
+        launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, dst, stream);
+        if (i == 0 && t.feedback == PRT_TEMPORAL_FEEDBACK_ATROUS)
+            hipLaunchKernelGGL(tm_feedback_kernel, grd, blk, 0, stream, dst, W, H, h.cn);
+        float4* tmp = cur; cur = nxt; nxt = tmp;
+    }
+}
+
+}  // namespace prt

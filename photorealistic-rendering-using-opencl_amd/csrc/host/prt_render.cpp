@@ -5,7 +5,9 @@
 // GLFW loop replaced by "-frames N" or "-spp N" (with "-adaptive E [-min-spp M] [-abs-floor F] [-spp-map file.pfm]": adaptive sampling,
 // -spp the maximum) and PrtSc replaced by "-out file.{png,hdr,pfm}" (default render.png / render.hdr by -encoder, as saveImage()).
 // "-denoise" writes the picture through prt_denoise (guides of "-guide-spp K" samples, default 4; with -adaptive the variance comes from
-// the stats plane); "-guides-out base" writes base_albedo.pfm, base_normal.pfm and base_depth.pfm.
+// the stats plane); "-guides-out base" writes base_albedo.pfm, base_normal.pfm and base_depth.pfm.  "-orbit-frames F -orbit-yaw RAD"
+// renders F frames along a yaw orbit (InteractiveCamera::changeYaw by RAD between frames), each -spp fresh paths after a prt_reset, guides and
+// prt_denoise_temporal -- the loop of a moving camera -- and writes the last one.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -97,6 +99,8 @@ int main(int argc, char** argv) {
     bool denoise = false;                                          // -denoise: the output goes through prt_denoise
     unsigned guide_spp = 4;                                        // -guide-spp K: guide samples per pixel
     std::string guides_out;                                        // -guides-out base: base_{albedo,normal,depth}.pfm
+    unsigned orbit_frames = 0;                                     // -orbit-frames F: F frames through prt_denoise_temporal ...
+    float orbit_yaw = 0.0f;                                        // -orbit-yaw RAD: ... RAD of yaw apart
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -120,6 +124,8 @@ int main(int argc, char** argv) {
         else if (a == "-denoise") denoise = true;
         else if (a == "-guide-spp") guide_spp = (unsigned)std::atoi(next());
         else if (a == "-guides-out") guides_out = next();
+        else if (a == "-orbit-frames") orbit_frames = (unsigned)std::atoi(next());
+        else if (a == "-orbit-yaw") orbit_yaw = (float)std::atof(next());
     }
     prt_ctx* ctx = nullptr;
     try {
@@ -176,7 +182,26 @@ int main(int argc, char** argv) {
         const unsigned max_frames = frames ? frames : spp * (unsigned)(cfg.max_bounces > 8 ? cfg.max_bounces : 8) + 64;
         std::vector<int32_t> seeds((size_t)max_frames * 2);
         prth_seed_pairs(1, max_frames, seeds.data());              // rand() protocol, :226-227,301-302
-        if (frames) CHECK(prt_render_frames(ctx, 1, frames, seeds.data()));
+        std::vector<float> orbit_rgba;
+        std::vector<uint8_t> orbit_ldr;
+        if (orbit_frames) {                                        // the reference restarts from black on each move (:283-291); here the history carries over
+            const size_t npix = (size_t)window_width * window_height;
+            orbit_rgba.resize(npix * 4);
+            orbit_ldr.resize(npix * 4);
+            for (unsigned f = 0; f < orbit_frames; ++f) {
+                if (f) {
+                    ic.changeYaw(orbit_yaw);
+                    ic.buildRenderCamera(&cam);
+                    CHECK(prt_set_camera(ctx, &cam));
+                }
+                CHECK(prt_reset(ctx));
+                prth_seed_pairs(1 + f * max_frames, max_frames, seeds.data());
+                CHECK(prt_render_spp(ctx, spp, max_frames, seeds.data(), nullptr));
+                CHECK(prt_render_guides(ctx, guide_spp));
+                const bool last = f + 1 == orbit_frames;
+                CHECK(prt_denoise_temporal(ctx, nullptr, nullptr, last ? orbit_rgba.data() : nullptr, last ? orbit_ldr.data() : nullptr));
+            }
+        } else if (frames) CHECK(prt_render_frames(ctx, 1, frames, seeds.data()));
         else if (adaptive >= 0.0f) {
             const prt_adaptive ad = {std::min(min_spp, spp), spp, adaptive, abs_floor};
             CHECK(prt_render_adaptive(ctx, &ad, max_frames, seeds.data(), nullptr));
@@ -215,7 +240,8 @@ int main(int argc, char** argv) {
                     return 1;
                 }
         }
-        if (denoise) CHECK(prt_denoise(ctx, nullptr, rgba.data(), nullptr));       // (the variance source: the stats plane after -adaptive)
+        if (denoise && !orbit_frames) CHECK(prt_denoise(ctx, nullptr, rgba.data(), nullptr));       // (the variance source: the stats plane after -adaptive)
+        if (orbit_frames) rgba = orbit_rgba;
         // saveImage(), include/GL/cl_gl_interop.h:144-160: -encoder 0 -> render.png (the displayed, tonemapped picture), -encoder 1 ->
         // render.hdr (the linear one); -out <file> picks the name, and the format by its extension (.png / .hdr / .pfm)
         if (out_path.empty()) out_path = encoder == 1 ? "render.hdr" : "render.png";
@@ -223,7 +249,8 @@ int main(int argc, char** argv) {
         bool ok;
         if (ends_with(".png")) {                                   // encoder 0 of the reference: the tonemapped picture
             std::vector<uint8_t> ldr((size_t)window_width * window_height * 4);
-            if (denoise) CHECK(prt_denoise(ctx, nullptr, nullptr, ldr.data()));
+            if (orbit_frames) ldr = orbit_ldr;
+            else if (denoise) CHECK(prt_denoise(ctx, nullptr, nullptr, ldr.data()));
             else CHECK(prt_tonemap_rgba8(ctx, ldr.data()));
             ok = write_png(out_path, ldr, window_width, window_height);
         } else if (ends_with(".hdr")) {                            // encoder 1: the linear picture as Radiance RGBE
