@@ -333,6 +333,48 @@ int prt_denoise_temporal(prt_ctx* ctx, const prt_denoise_params* spatial, const 
 int prt_read_history(prt_ctx* ctx, float* out8);
 int prt_reset_history(prt_ctx* ctx);
 
+/* Pixel reconstruction filter of the primary rays: antialiasing (no counterpart in the reference, whose every path starts through the exact
+ * pixel centre; opt-in, the default is that centre ray, bit for bit).  Filter importance sampling (Ernst et al. 2006): path k of pixel (x, y)
+ * starts through (x + dx, y + dy), (dx, dy) drawn from a separable non-negative filter F(dx, dy) = f(dx) f(dy), every sample with weight 1 --
+ * the framebuffer's mean estimates the filter-weighted pixel integral, and a pixel's estimate still depends on its own paths only (tiles,
+ * row blocks, run-ahead, pacing, adaptive freezing, checkpoints keep their bits; no atomics, no splatting).
+ *   Sample point of path k (0-based index of the path in its pixel since the last reset: samples - 1 after the path start counted it), global
+ *   pixel coordinates, integer arithmetic mod 2^32:
+ *       s = gy * 0x9E3779B9 + gx;   hx = lowbias32(s);   hy = lowbias32(s ^ 0x68E31DA4)
+ *       lowbias32(v): v ^= v >> 16; v *= 0x7FEB352D; v ^= v >> 15; v *= 0x846CA68B; v ^= v >> 16
+ *       ux = k * 3242174889 + hx;   uy = k * 2447445414 + hy                 (R2 in 0.32 fixed point, rotated per pixel)
+ *       u = (float)(ux >> 8) * 2^-24,  v = (float)(uy >> 8) * 2^-24        (exact, in [0, 1));   dx = w(u), dy = w(v)
+ *   It takes no draw from the path's RNG stream: apart from the ray direction every path keeps the reference's random sequence.
+ *   The warp w, f32, no contraction, sqrtf correctly rounded:
+ *       BOX              w(u) = (u - 0.5f) * (2r)
+ *       TENT             w(u) = r * (sqrtf(2u) - 1) for u < 0.5f, else r * (1 - sqrtf(2 - 2u))
+ *       GAUSSIAN         f(x) = exp(-x^2 / 2s^2) - exp(-r^2 / 2s^2), s = r / 3
+ *       BLACKMAN_HARRIS  f(x) = 0.35875 + 0.48829 cos(pi x / r) + 0.14128 cos(2 pi x / r) + 0.01168 cos(3 pi x / r)
+ *     the last two through a table T[0 .. 256] built when the filter is set: T[i] = F^-1(i / 256) in float64 rounded to f32, F the normalised
+ *     CDF of f on [-r, r] in closed form, built antisymmetric (T[256 - i] = -T[i], T[128] = 0: w(0.5) = 0 exactly);
+ *       t = u * 256.0f;  j = (int)t;  t -= j;  w = T[j] + t * (T[j+1] - T[j])
+ *   Camera ray: create_cam_ray's expression at sx = (x + dx) / (W-1), sy = (H-1-y - dy) / (H-1) (the convention of the guides); the lens
+ *   sample and the time draw are unchanged.
+ *   Radius: 0 <= r <= 4, PRT_FILTER_DEFAULT_RADIUS = the kind's default; NaN, infinities, other negatives, values above 4 and unknown kinds:
+ *   PRT_ERR_INVALID_ARGUMENT.  r = 0 is accepted for every kind: every ray goes through the centre, through the filter instances (bit-exact
+ *   with PRT_FILTER_NONE: a plumbing check).
+ *   Lifetime: a context starts with PRT_FILTER_NONE.  Setting a filter implies a reset of the frame (when it has one) and makes the guides stale;
+ *   the temporal history is kept (as with prt_set_camera).  The filter survives prt_resize, prt_set_tile, prt_set_row_blocks, prt_upload_scene.
+ *   Guides under a filter: guide sample s sits at the offset (w(fx), w(fy)) instead of (fx - 0.5, fy - 0.5) (the lens sample still comes from
+ *   the unwarped (fx, fy)): box 0.5 gives the unfiltered guides bit for bit, K = 1 the centre for every filter.
+ *   prt_render_frames, prt_render_spp, prt_render_adaptive and prt_render_guides honour it; the option "pool" is not used under a filter.
+ *   Refused with PRT_ERR_UNSUPPORTED (no filter instances of these sets): a debug view, SDF primitives (geom_flags), pick_random_light,
+ *   env_importance_sampling.
+ * prt_pixel_filter_offsets needs no device and no context: out2 = {dx, dy} of paths k0 .. k0+n-1 (mod 2^32) of global pixel (gx, gy). */
+#define PRT_FILTER_NONE 0u              /* default: the reference's pixel-centre ray (bit-exact, the existing kernels) */
+#define PRT_FILTER_BOX 1u               /* default radius 0.5 */
+#define PRT_FILTER_TENT 2u              /* default radius 1.0 */
+#define PRT_FILTER_GAUSSIAN 3u          /* default radius 1.5, sigma = radius / 3 */
+#define PRT_FILTER_BLACKMAN_HARRIS 4u   /* default radius 2.0 */
+#define PRT_FILTER_DEFAULT_RADIUS (-1.0f)
+int prt_set_pixel_filter(prt_ctx* ctx, uint32_t kind, float radius);
+int prt_pixel_filter_offsets(uint32_t kind, float radius, uint32_t gx, uint32_t gy, uint32_t k0, uint32_t n, float* out2);
+
 /* Scheduling knob of the render kernel (no counterpart in the reference; results do not depend on it, tests check
  * that): a wave ends a BVH-walk phase once fewer than `lanes` of its 64 lanes are still walking (and fewer than wait for the
  * phase to end); the lanes cut off resume in the wave's next phase.  1 = every walk runs to its end (lock step).
@@ -381,7 +423,7 @@ int prt_set_option(prt_ctx* ctx, const char* name, int value);
  * not the working tree's; tests/conftest.py asserts the same.  Needs no device and no context. */
 const char* prt_build_id(void);
 /* what the last launch ran, as text: "render_kernel<LIGHT|DIFF> waves=6 pixels=tiles" ("" before the first launch; "pixels=scattered",
- * "pixels=tiles, expensive first": see prt_set_option) */
+ * "pixels=tiles, expensive first": see prt_set_option; the pixel filter's builds: "render_kernel<LIGHT|DIFF,filter=tent> ...") */
 const char* prt_kernel_variant(prt_ctx* ctx);
 
 int prt_synchronize(prt_ctx* ctx);
@@ -417,7 +459,8 @@ int prt_query_counts(prt_ctx* ctx, uint32_t spp, prt_stats* stats);
 int prt_selftest_math(prt_ctx* ctx, int fn, const float* a, const float* b, float* out, int n);
 /* test hook: one device FUNCTION of the radiance loop on `n` cases (BSDF sampling / evaluation, microfacet terms,
  * Fresnel, light sampling, medium and phase sampling, camera ray, primitive tests, environment lookup -- fn 1..11, layouts in
- * csrc/hip/pt_selftest.h): 80 floats of shared parameters, 32 floats in and 32 floats out per case.  The known-answer
+ * csrc/hip/pt_selftest.h; fn 12: the pixel filter's offset, params {kind as uint bits, radius}, in {gx, gy, k as uint bits}, out {dx, dy},
+ * csrc/hip/pt_filter.hip): 80 floats of shared parameters, 32 floats in and 32 floats out per case.  The known-answer
  * fixtures tests/golden/kat_*.npz hold what the REFERENCE's own functions return on the same cases. */
 int prt_selftest_fn(prt_ctx* ctx, int fn, const float* params, const float* in, float* out, int n);
 

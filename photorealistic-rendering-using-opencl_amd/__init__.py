@@ -15,14 +15,14 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
+from ._capi import PIXEL_FILTERS, PIXEL_FILTER_DEFAULT_RADIUS, DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["PIXEL_FILTERS", "PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -175,6 +175,26 @@ def adaptive_converged(l, s2, n, rel_err, abs_floor):
         v = np.fmax((s2 - l * m) / (nf * (n - np.uint32(1)).astype(f)), f(0))
         t = f(rel_err) * np.fmax(m, f(abs_floor))
         return v < t * t, np.sqrt(v), m
+
+
+def _filter_kind(kind):
+    if isinstance(kind, str):
+        if kind not in PIXEL_FILTERS:
+            raise ValueError("unknown pixel filter %r (one of %s)" % (kind, ", ".join(PIXEL_FILTERS)))
+        return PIXEL_FILTERS[kind]
+    return int(kind)
+
+
+def pixel_filter_offsets(kind, radius, gx, gy, k0, n):
+    """prt_pixel_filter_offsets: the filter offsets {dx, dy} of paths k0 .. k0+n-1 of global pixel (gx, gy) as float32 [n, 2] (prt.h; kind by name
+    or PRT_FILTER_* number, radius None = the kind's default).  Needs no GPU"""
+    out = np.zeros((int(n), 2), dtype=np.float32)
+    r = -1.0 if radius is None else float(radius)
+    rc = load_library().prt_pixel_filter_offsets(_filter_kind(kind), C.c_float(r), int(gx) & 0xFFFFFFFF, int(gy) & 0xFFFFFFFF,
+                                                 int(k0) & 0xFFFFFFFF, int(n), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise PrtError("prt_pixel_filter_offsets failed (%d): %s" % (rc, load_library().prt_last_global_error().decode()), rc)
+    return out
 
 
 def seed_pairs(n_frames, first_frame=1):
@@ -348,6 +368,12 @@ class Renderer:
 
     def reset_history(self):
         self._chk(self.lib.prt_reset_history(self.ctx), "prt_reset_history")
+
+    def set_pixel_filter(self, kind="tent", radius=None):
+        """prt_set_pixel_filter: antialiasing by filter importance sampling (prt.h).  kind: a name of PIXEL_FILTERS ("none", "box", "tent",
+        "gaussian", "blackman-harris") or its number; radius None = the kind's default.  Resets the frame and makes the guides stale"""
+        r = -1.0 if radius is None else float(radius)
+        self._chk(self.lib.prt_set_pixel_filter(self.ctx, _filter_kind(kind), C.c_float(r)), "prt_set_pixel_filter")
 
     def set_walk_min_lanes(self, lanes):
         self._chk(self.lib.prt_set_walk_min_lanes(self.ctx, int(lanes)), "prt_set_walk_min_lanes")

@@ -89,6 +89,10 @@ class TemporalParams(C.Structure):
 PRT_TEMPORAL_FEEDBACK_INTEGRATED, PRT_TEMPORAL_FEEDBACK_ATROUS = 0, 1
 TEMPORAL_DEFAULTS = dict(alpha_color=0.2, alpha_moments=0.2, tau_z=0.05, cos_n=0.9, history_cap=32, feedback="atrous")
 
+# prt_set_pixel_filter kinds by name, and the default radius of each (include/prt.h)
+PIXEL_FILTERS = {"none": 0, "box": 1, "tent": 2, "gaussian": 3, "blackman-harris": 4}
+PIXEL_FILTER_DEFAULT_RADIUS = {"none": 0.0, "box": 0.5, "tent": 1.0, "gaussian": 1.5, "blackman-harris": 2.0}
+
 
 assert C.sizeof(Material) == 64 and C.sizeof(Mesh) == 256 and C.sizeof(BvhNode) == 36 and C.sizeof(Camera) == 80
 
@@ -121,6 +125,8 @@ PRT_API = [
     ("prt_denoise_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]),
     ("prt_read_history", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_reset_history", C.c_int, [C.c_void_p]),
+    ("prt_set_pixel_filter", C.c_int, [C.c_void_p, C.c_uint32, C.c_float]),
+    ("prt_pixel_filter_offsets", C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("prt_kernel_variant", C.c_char_p, [C.c_void_p]),

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "prt.h"
+#include "pt_filter.h"
 #include "pt_launch.h"
 #include "pt_layout.h"
 #include "pt_pack.h"
@@ -116,6 +117,11 @@ struct prt_ctx {
     int hist_cur = 0;
     bool hist_valid = false;                       // emptied by everything prt.h lists
     DevCamera hist_cam{};
+    // prt_set_pixel_filter: the kind, its radius and, for the Gaussian and Blackman-Harris kinds, the table T[0 .. 256] on the device (allocated on
+    // first use).  Every launch carries them in FrameArgs
+    uint32_t filter_kind = PRT_FILTER_NONE;
+    float filter_r = 0.0f;
+    float* d_filter_tab = nullptr;
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -243,6 +249,7 @@ extern "C" void prt_destroy(prt_ctx* c) {
     free_dev(c->d_env); free_dev(c->d_env_rows); free_dev(c->d_env_cols);
     void* p = c->d_seeds; free_dev(p);
     p = c->d_counters; free_dev(p);
+    p = c->d_filter_tab; free_dev(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -445,6 +452,8 @@ static FrameArgs frame_args(prt_ctx* c, uint32_t first_frame, uint32_t n, const 
     fa.tri_sixteenths = c->tri_sixteenths;
     fa.adapt = nullptr; fa.live = nullptr; fa.live_count = 0;             // (prt_render_adaptive sets them: every other launch is "N spp" / frame mode)
     fa.min_spp = 0; fa.rel_err = 0.0f; fa.abs_floor = 0.0f;
+    fa.filter_kind = c->filter_kind; fa.filter_r = c->filter_r;
+    fa.filter_tab = c->filter_kind >= PRT_FILTER_GAUSSIAN ? c->d_filter_tab : nullptr;
     return fa;
 }
 
@@ -956,6 +965,60 @@ extern "C" int prt_reset_history(prt_ctx* c) {
     return PRT_OK;
 }
 
+// ---- the pixel filter (prt.h prt_set_pixel_filter) ------------------------------------------------------------------------------------------
+static const char* const k_filter_names[] = {"none", "box", "tent", "gaussian", "blackman-harris"};
+
+// the radius a (kind, radius) pair means: PRT_FILTER_DEFAULT_RADIUS = the kind's default; false for an unknown kind or a radius outside [0, 4]
+// (NaN and the infinities included)
+static bool filter_radius(uint32_t kind, float radius, float& r) {
+    static const float defaults[] = {0.0f, 0.5f, 1.0f, 1.5f, 2.0f};
+    if (kind > PRT_FILTER_BLACKMAN_HARRIS) return false;
+    if (radius == PRT_FILTER_DEFAULT_RADIUS) { r = defaults[kind]; return true; }
+    if (!(radius >= 0.0f && radius <= 4.0f)) return false;
+    r = kind == PRT_FILTER_NONE ? 0.0f : radius;
+    return true;
+}
+
+extern "C" int prt_set_pixel_filter(prt_ctx* c, uint32_t kind, float radius) {
+    CTX_CHECK(c);
+    float r = 0.0f;
+    if (!filter_radius(kind, radius, r))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_pixel_filter: unknown kind, or a radius outside 0 .. 4 (PRT_FILTER_DEFAULT_RADIUS: the kind's default)");
+    if (kind != PRT_FILTER_NONE) {
+        const char* no = c->cfg.view_option != PRT_VIEW_RESULTS ? "a debug view" : (c->cfg.geom_flags & PRT_GEOM_SDF) ? "SDF primitives"
+                       : c->cfg.pick_random_light ? "pick_random_light" : c->cfg.env_importance_sampling ? "env_importance_sampling" : nullptr;
+        if (no) return fail(c, PRT_ERR_UNSUPPORTED, std::string("prt_set_pixel_filter: no filter instances are built for ") + no);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // (launches still queued read the current table)
+    if (kind >= PRT_FILTER_GAUSSIAN) {
+        float tab[PT_FILTER_TAB + 1];
+        build_filter_table(kind, r, tab);
+        if (!c->d_filter_tab) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_filter_tab), sizeof(tab)));
+        HIPCHK(c, hipMemcpy(c->d_filter_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    c->filter_kind = kind;
+    c->filter_r = r;
+    c->guides_valid = false;                               // (the temporal history is kept, as by prt_set_camera)
+    return c->have_size ? prt_reset(c) : PRT_OK;
+}
+
+extern "C" int prt_pixel_filter_offsets(uint32_t kind, float radius, uint32_t gx, uint32_t gy, uint32_t k0, uint32_t n, float* out2) {
+    float r = 0.0f;
+    if (!filter_radius(kind, radius, r)) {
+        g_global_error = "prt_pixel_filter_offsets: unknown kind, or a radius outside 0 .. 4";
+        return PRT_ERR_INVALID_ARGUMENT;
+    }
+    if (n && !out2) { g_global_error = "prt_pixel_filter_offsets: null output"; return PRT_ERR_INVALID_ARGUMENT; }
+    float tab[PT_FILTER_TAB + 1] = {};
+    if (kind >= PRT_FILTER_GAUSSIAN) build_filter_table(kind, r, tab);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (kind == PRT_FILTER_NONE) { out2[2 * i] = 0.0f; out2[2 * i + 1] = 0.0f; continue; }
+        dev::filter_offset(kind, r, tab, gx, gy, k0 + i, out2[2 * i], out2[2 * i + 1]);
+    }
+    return PRT_OK;
+}
+
 extern "C" int prt_set_walk_min_lanes(prt_ctx* c, uint32_t lanes) {
     CTX_CHECK(c);
     if (lanes < 1 || lanes > 64) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_walk_min_lanes: 1..64");
@@ -1000,7 +1063,10 @@ extern "C" const char* prt_kernel_variant(prt_ctx* c) {
     if (!c) return "";
     const RenderLaunch& l = c->last;
     const char* pixels = l.list ? " pixels=live list" : (l.scatter ? " pixels=scattered" : (l.ordered ? " pixels=tiles, expensive first" : " pixels=tiles"));
-    c->variant = std::string(l.name) + (l.waves ? " waves=" + std::to_string(l.waves) + pixels + (l.pix_per_wave != 64 ? ", " + std::to_string(l.pix_per_wave) + " per wave" : "") +
+    std::string name(l.name);
+    const size_t f = name.rfind(",filter>");                // the filter builds: the context's kind
+    if (f != std::string::npos && c->filter_kind != PRT_FILTER_NONE) name.insert(f + 7, std::string("=") + k_filter_names[c->filter_kind]);
+    c->variant = name + (l.waves ? " waves=" + std::to_string(l.waves) + pixels + (l.pix_per_wave != 64 ? ", " + std::to_string(l.pix_per_wave) + " per wave" : "") +
                                         (l.pool ? ", pool" : "") + (l.adaptive ? ", adaptive" : "") : "");
     return c->variant.c_str();
 }
@@ -1136,8 +1202,16 @@ extern "C" int prt_selftest_math(prt_ctx* c, int fn, const float* a, const float
 
 extern "C" int prt_selftest_fn(prt_ctx* c, int fn, const float* params, const float* in, float* out, int n) {
     CTX_CHECK(c);
-    if (!params || !in || !out || n <= 0 || fn < 1 || fn > 11) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: bad arguments");
+    if (!params || !in || !out || n <= 0 || fn < 1 || fn > 12) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
+    float tab[PT_FILTER_TAB + 1] = {};
+    float r = 0.0f;
+    uint32_t kind = 0;
+    if (fn == 12) {                                            // the pixel filter's offsets (pt_filter.hip): params {kind (bits), radius}
+        std::memcpy(&kind, params, sizeof(kind));
+        if (!filter_radius(kind, params[1], r) || kind == PRT_FILTER_NONE) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: fn 12 needs a filter kind and radius");
+        if (kind >= PRT_FILTER_GAUSSIAN) build_filter_table(kind, r, tab);
+    }
     float *dp = nullptr, *di = nullptr, *dout = nullptr;
     const size_t bytes = (size_t)n * 32 * sizeof(float);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&dp), 80 * sizeof(float));
@@ -1145,7 +1219,15 @@ extern "C" int prt_selftest_fn(prt_ctx* c, int fn, const float* params, const fl
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), bytes);
     if (e == hipSuccess) e = hipMemcpy(dp, params, 80 * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(di, in, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { launch_selftest_fn(fn, dp, di, dout, n, c->stream); e = hipStreamSynchronize(c->stream); }
+    float* dtab = nullptr;
+    if (e == hipSuccess && fn == 12) e = hipMalloc(reinterpret_cast<void**>(&dtab), sizeof(tab));
+    if (e == hipSuccess && fn == 12) e = hipMemcpy(dtab, tab, sizeof(tab), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (fn == 12) launch_selftest_filter(kind, r, kind >= PRT_FILTER_GAUSSIAN ? dtab : nullptr, di, dout, n, c->stream);
+        else launch_selftest_fn(fn, dp, di, dout, n, c->stream);
+        e = hipStreamSynchronize(c->stream);
+    }
+    if (dtab) (void)hipFree(dtab);
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
     if (dp) (void)hipFree(dp);
     if (di) (void)hipFree(di);

@@ -15,9 +15,9 @@ namespace prt {
 using namespace dev;
 
 // ---- guides --------------------------------------------------------------------------------------------------------------------------
-template <bool SDF>
-__global__ __launch_bounds__(64) void guide_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
-                                                   float4* __restrict__ out) {
+// FILTER: the sample offsets warped by the context's pixel filter (prt.h prt_set_pixel_filter; filtered_guides_kernel)
+template <bool SDF, bool FILTER>
+PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* __restrict__ out) {
     const int tiles_x = (fa.width + 7) / 8;
     const int lane = threadIdx.x & 63;
     const int lx = (int)(blockIdx.x % (unsigned)tiles_x) * 8 + (lane & 7);
@@ -34,7 +34,12 @@ __global__ __launch_bounds__(64) void guide_kernel(const DevScene sc, const DevC
     for (unsigned s = 0; s < samples; ++s) {
         float fx, fy;
         guide_offsets(s, fx, fy);
-        const Ray ray = guide_cam_ray(gx, gy, fa.width, fa.full_height, cam, fx, fy, guide_frac(fx + 0.25f), guide_frac(fy + 0.75f));
+        Ray ray;
+        if constexpr (FILTER)
+            ray = guide_cam_ray_at(gx, gy, fa.width, fa.full_height, cam, filter_warp(fa.filter_kind, fa.filter_r, fa.filter_tab, fx),
+                                   filter_warp(fa.filter_kind, fa.filter_r, fa.filter_tab, fy), guide_frac(fx + 0.25f), guide_frac(fy + 0.75f));
+        else
+            ray = guide_cam_ray(gx, gy, fa.width, fa.full_height, cam, fx, fy, guide_frac(fx + 0.25f), guide_frac(fy + 0.75f));
         const GuideSample g = guide_sample<SDF>(sc, ray, stk);
         albedo = albedo + g.albedo;
         if (g.hit) {
@@ -50,21 +55,34 @@ __global__ __launch_bounds__(64) void guide_kernel(const DevScene sc, const DevC
     out[2 * id] = make_float4(albedo.x * inv_k, albedo.y * inv_k, albedo.z * inv_k, (float)hits * inv_k);
     out[2 * id + 1] = make_float4(n.x, n.y, n.z, hits ? zsum / (float)hits : 0.0f);
 }
-
 template <bool SDF>
+__global__ __launch_bounds__(64) void guide_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
+                                                   float4* __restrict__ out) {
+    guide_pixel<SDF, false>(sc, cam, fa, samples, out);
+}
+// under a pixel filter (no SDF build: prt_set_pixel_filter refuses SDF scenes)
+__global__ __launch_bounds__(64) void filtered_guides_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
+                                                          float4* __restrict__ out) {
+    guide_pixel<false, true>(sc, cam, fa, samples, out);
+}
+
+template <bool SDF, bool FILTER>
 static void launch_guides_t(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream) {
     const size_t lds = (size_t)sc.stack_levels * 64 * sizeof(unsigned);
     static size_t lds_attr = 0;
+    const void* k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_kernel) : reinterpret_cast<const void*>(&guide_kernel<SDF>);
     if (lds > 65536u && lds > lds_attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&guide_kernel<SDF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         lds_attr = lds;
     }
     const unsigned tiles = (unsigned)(((fa.width + 7) / 8) * ((fa.rows + 7) / 8));
-    hipLaunchKernelGGL((guide_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
+    if constexpr (FILTER) hipLaunchKernelGGL(filtered_guides_kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
+    else hipLaunchKernelGGL((guide_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
 }
 void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream) {
-    if (sc.n_sdfs) launch_guides_t<true>(sc, cam, fa, samples, out, stream);
-    else launch_guides_t<false>(sc, cam, fa, samples, out, stream);
+    if (fa.filter_kind != PRT_FILTER_NONE) launch_guides_t<false, true>(sc, cam, fa, samples, out, stream);
+    else if (sc.n_sdfs) launch_guides_t<true, false>(sc, cam, fa, samples, out, stream);
+    else launch_guides_t<false, false>(sc, cam, fa, samples, out, stream);
 }
 
 // ---- the filter ----------------------------------------------------------------------------------------------------------------------

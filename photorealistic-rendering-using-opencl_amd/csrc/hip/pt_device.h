@@ -17,6 +17,7 @@
 
 #include "prt_detmath.h"
 #include "prt_types.h"
+#include "pt_filter.h"
 #include "pt_layout.h"
 
 namespace prt {
@@ -256,6 +257,38 @@ PT_DEV Ray create_cam_ray(int cx, int cy, int width, int height, const DevCamera
         float distance = cam.apertureRadius * hw_sqrt(random2);
         float apertureX = prt_cos(angle) * distance;
         float apertureY = prt_sin(angle) * distance;
+        aperturePoint = position + (hAxis * apertureX) + (vAxis * apertureY);
+    } else {
+        aperturePoint = position;
+    }
+    Ray ray;
+    ray.backside = false;
+    ray.origin = aperturePoint;
+    ray.dir = normalize(onImagePlane - aperturePoint);
+    ray.time = next1D(rng);
+    ray.normal = splat(0.0f);
+    ray.pos = splat(0.0f);
+    ray.t = 0.0f;
+    return ray;
+}
+// create_cam_ray through the image-plane point of (cx + dx, cy + dy): the pixel filter's path start (PT_MATS_FILTER builds, prt.h
+// prt_set_pixel_filter).  The same operations otherwise; dx = dy = 0 gives create_cam_ray's bits
+PT_DEV Ray create_cam_ray_at(int cx, int cy, float dx, float dy, int width, int height, const DevCamera& cam, Rng& rng) {
+    const f3 hAxis = ld3(cam.hAxis), vAxis = ld3(cam.vAxis), position = ld3(cam.position);
+    const f3 middle = ld3(cam.middle), horizontal = ld3(cam.horizontal), vertical = ld3(cam.vertical);
+    const int pixely = height - cy - 1;
+    const float sx = ((float)cx + dx) / (width - 1.0f);
+    const float sy = ((float)pixely - dy) / (height - 1.0f);
+    const f3 onPlane = middle + (horizontal * ((2 * sx) - 1)) + (vertical * ((2 * sy) - 1));
+    const f3 onImagePlane = position + ((onPlane - position) * cam.focalDistance);
+    f3 aperturePoint;
+    if (cam.apertureRadius > 0.00001f) {
+        const float random1 = next1D(rng);
+        const float random2 = next1D(rng);
+        const float angle = 2 * PT_PI * random1;
+        const float distance = cam.apertureRadius * hw_sqrt(random2);
+        const float apertureX = prt_cos(angle) * distance;
+        const float apertureY = prt_sin(angle) * distance;
         aperturePoint = position + (hAxis * apertureX) + (vAxis * apertureY);
     } else {
         aperturePoint = position;
@@ -1086,7 +1119,10 @@ PT_DEV float coat_pdf(const Event& e, const Mat& mat) {
 // every path end, and the live-pixel list mapping of render_kernel.  A bit of MATS rather than a template parameter of its own: the
 // pre-existing instances keep their names and their code
 #define PT_MATS_ADAPT 0x08000000u
-#define PT_MATS_FLAGS (PT_MATS_SDF | PT_MATS_VIEW | PT_MATS_PICK | PT_MATS_ENVIS | PT_MATS_DISTS | PT_MATS_ADAPT)
+// PT_MATS_FILTER bit: the pixel-filter build of a set (prt_set_pixel_filter, pt_filter.h): a path starts through its filter offset
+// (create_cam_ray_at) instead of the pixel centre.  A bit of MATS for the reason PT_MATS_ADAPT is one
+#define PT_MATS_FILTER 0x00800000u
+#define PT_MATS_FLAGS (PT_MATS_SDF | PT_MATS_VIEW | PT_MATS_PICK | PT_MATS_ENVIS | PT_MATS_DISTS | PT_MATS_ADAPT | PT_MATS_FILTER)
 template <unsigned MATS>
 PT_HD constexpr unsigned dist_mask() { return ((MATS >> PT_MATS_DIST_SHIFT) & 7u) ? ((MATS >> PT_MATS_DIST_SHIFT) & 7u) : 7u; }
 template <unsigned MATS>
@@ -1498,7 +1534,14 @@ PT_DEV void lane_front(const DevScene& sc, const DevCamera& cam, const FrameArgs
             L.reset = false;
             L.mask = splat(1.0f);
             L.h_valid = false;
-            const Ray cr = create_cam_ray(gx, gy, fa.width, fa.full_height, cam, L.rng);
+            Ray cr;
+            if constexpr ((MATS & PT_MATS_FILTER) != 0u) {                         // prt_set_pixel_filter: path samples - 1 of the pixel
+                float dx, dy;
+                filter_offset(fa.filter_kind, fa.filter_r, fa.filter_tab, (unsigned)gx, (unsigned)gy, L.samples - 1u, dx, dy);
+                cr = create_cam_ray_at(gx, gy, dx, dy, fa.width, fa.full_height, cam, L.rng);
+            } else {
+                cr = create_cam_ray(gx, gy, fa.width, fa.full_height, cam, L.rng);
+            }
             L.origin = cr.origin; L.dir = cr.dir; L.t = cr.t; L.time = cr.time;
         }
         L.begun = true;

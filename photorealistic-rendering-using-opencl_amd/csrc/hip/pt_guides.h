@@ -22,13 +22,13 @@ PT_DEV void guide_offsets(unsigned s, float& fx, float& fy) {
     fy = s ? guide_frac(0.5f + (float)s * 0.5698402910f) : 0.5f;
 }
 
-// create_cam_ray (pt_device.h) with explicit sample values instead of RNG draws: the image-plane point of (cx + fx - 0.5, cy + fy - 0.5)
-// and, with an aperture, the lens point of (lx, ly) in [0, 1)^2
-PT_DEV Ray guide_cam_ray(int cx, int cy, int width, int height, const DevCamera& cam, float fx, float fy, float lx, float ly) {
+// create_cam_ray (pt_device.h) with explicit sample values instead of RNG draws: the image-plane point of (cx + ox, cy + oy) and, with
+// an aperture, the lens point of (lx, ly) in [0, 1)^2
+PT_DEV Ray guide_cam_ray_at(int cx, int cy, int width, int height, const DevCamera& cam, float ox, float oy, float lx, float ly) {
     const f3 hAxis = ld3(cam.hAxis), vAxis = ld3(cam.vAxis), position = ld3(cam.position);
     const f3 middle = ld3(cam.middle), horizontal = ld3(cam.horizontal), vertical = ld3(cam.vertical);
-    const float px = (float)cx + (fx - 0.5f);
-    const float py = (float)(height - cy - 1) - (fy - 0.5f);
+    const float px = (float)cx + ox;
+    const float py = (float)(height - cy - 1) - oy;
     const float sx = px / (width - 1.0f);
     const float sy = py / (height - 1.0f);
     const f3 onPlane = middle + (horizontal * ((2 * sx) - 1)) + (vertical * ((2 * sy) - 1));
@@ -48,6 +48,10 @@ PT_DEV Ray guide_cam_ray(int cx, int cy, int width, int height, const DevCamera&
     ray.pos = splat(0.0f);
     ray.t = 0.0f;
     return ray;
+}
+// ... at the sample's fractional position (fx, fy): the offset (fx - 0.5, fy - 0.5)
+PT_DEV Ray guide_cam_ray(int cx, int cy, int width, int height, const DevCamera& cam, float fx, float fy, float lx, float ly) {
+    return guide_cam_ray_at(cx, cy, width, height, cam, fx - 0.5f, fy - 0.5f, lx, ly);
 }
 
 // closest hit of `ray` against the whole scene: the tree walked to its end, then finish_closest.  Out: ray.t / pos / normal / backside

@@ -23,6 +23,11 @@
 #include "pt_inst_view_sdf.hip"
 #include "pt_inst_pick.hip"
 #include "pt_inst_envis.hip"
+#include "pt_inst_filter_light_diff.hip"
+#include "pt_inst_filter_coat.hip"
+#include "pt_inst_filter_rough_cond.hip"
+#include "pt_inst_filter_rough_diel.hip"
+#include "pt_inst_filter_generic.hip"
 #endif
 #elif defined(PT_PHASE_CLOCKS) || defined(PT_DEV_ONE_VARIANT)
 #error "PT_PHASE_CLOCKS / PT_DEV_ONE_VARIANT builds are unity builds: add -DPT_UNITY"
@@ -282,6 +287,15 @@ RenderLaunch launch_render(const DevScene& sc, const DevCamera& cam, const DevSt
     if (sc.n_sdfs || medium || sc.view || am != (PRT_MAT_LIGHT | PRT_MAT_DIFF)) return RenderLaunch{};
     return launch_set_light_diff(false, sc, cam, S, fa, fb, stream, lo);
 #else
+    if (fa.filter_kind != PRT_FILTER_NONE) {       // prt_set_pixel_filter (which refuses the env-sampling, light-pick, view and SDF configs)
+        if (!lo.generic) {
+            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF)) return launch_set_filter_light_diff(medium, sc, cam, S, fa, fb, stream, lo);
+            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_COAT)) return launch_set_filter_coat(medium, sc, cam, S, fa, fb, stream, lo);
+            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_ROUGH_COND)) return launch_set_filter_rough_cond(medium, sc, cam, S, fa, fb, stream, lo);
+            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL)) return launch_set_filter_rough_diel(medium, sc, cam, S, fa, fb, stream, lo);
+        }
+        return launch_set_filter_generic(medium, sc, cam, S, fa, fb, stream, lo);
+    }
     if (sc.env_is) return launch_set_envis(medium, sc, cam, S, fa, fb, stream, lo);              // (pack_scene refuses it with a medium, SDFs, views, the light pick)
     if (sc.pick_random_light) return launch_set_pick(medium, sc, cam, S, fa, fb, stream, lo);     // PICK_RANDOM_LIGHT: the generic set (pack_scene refuses it with SDFs / views)
     if (sc.view) return sc.n_sdfs ? launch_set_view_sdf(medium, sc, cam, S, fa, fb, stream, lo) : launch_set_view(medium, sc, cam, S, fa, fb, stream, lo);

@@ -37,6 +37,12 @@ PT_DECLARE_SET(launch_set_view);
 PT_DECLARE_SET(launch_set_view_sdf);
 PT_DECLARE_SET(launch_set_pick);
 PT_DECLARE_SET(launch_set_envis);
+// the PT_MATS_FILTER builds (prt_set_pixel_filter; pt_inst_filter_*.hip): the same sets with the filter's path start
+PT_DECLARE_SET(launch_set_filter_light_diff);
+PT_DECLARE_SET(launch_set_filter_coat);
+PT_DECLARE_SET(launch_set_filter_rough_cond);
+PT_DECLARE_SET(launch_set_filter_rough_diel);
+PT_DECLARE_SET(launch_set_filter_generic);
 
 // workgroups (tiles) launch_render uses for a width x rows frame part
 unsigned render_tile_count(int width, int rows);
@@ -52,6 +58,11 @@ void launch_state_to_rtd(const DevState& S, prt_path_state* out, size_t n, hipSt
 void launch_rtd_to_state(const prt_path_state* in, const DevState& S, float4* fb, size_t n, hipStream_t stream);
 void launch_selftest_math(int fn, const float* a, const float* b, float* out, int n, hipStream_t stream);
 void launch_selftest_fn(int fn, const float* params, const float* in, float* out, int n, hipStream_t stream);
+// prt_selftest_fn fn 12 (pt_filter.hip): filter_offset of pt_filter.h on the device, n cases of 32 floats in / out (in: gx, gy, k as uint bits;
+// out: dx, dy); tab: the kind's table (device) or null
+void launch_selftest_filter(unsigned kind, float r, const float* tab, const float* in, float* out, int n, hipStream_t stream);
+// the Gaussian and Blackman-Harris kinds' table T[0 .. PT_FILTER_TAB] of radius r (prt.h prt_set_pixel_filter; host, float64 rounded to f32)
+void build_filter_table(unsigned kind, float r, float* tab);
 void launch_tonemap(const float4* fb, unsigned char* out, const FrameArgs& fa, hipStream_t stream);
 void launch_count(const DevState& S, size_t n, unsigned spp, unsigned long long* out3, hipStream_t stream);
 // prt_render_adaptive: the local ids of the n-pixel frame's pixels that the adaptive freeze rule (max_spp, DevState::q4.w bit 31) has not frozen,

@@ -164,6 +164,11 @@ struct FrameArgs {
     uint32_t live_count;                    // framebuffer index) when 64 g + l < live_count: the unfrozen pixels packed into full waves
     uint32_t min_spp;
     float rel_err, abs_floor;
+    // the pixel filter (prt_set_pixel_filter; read by the PT_MATS_FILTER builds and the filtered guide kernel only, pt_filter.h).  Set from the
+    // context by every launch: no kernel argument of its own
+    const float* filter_tab;                // the Gaussian and Blackman-Harris kinds: T[0 .. 256] (device), else null
+    float filter_r;                         // radius
+    uint32_t filter_kind;                   // PRT_FILTER_*
 };
 
 }  // namespace prt

@@ -190,7 +190,8 @@ static RenderLaunch launch_variant(const char* name, const DevScene& sc, const D
     r.pix_per_wave = 64 >> fs.sub_shift;
     r.ordered = (!scatter && fa.tile_order && waves >= PT_BIG_WAVES) ? 1 : 0;
     // render_kernel_rp (pt_pool.h): the same launch -- same tiles or scattered pixels, same order -- with the deep walks on walker waves
-    if (lo.pool) {
+    // (not built for the pixel filter: its launches take the kernels below)
+    if constexpr (!(MATS & PT_MATS_FILTER)) if (lo.pool) {
         FrameArgs fp = fa;
         fp.scatter = scatter ? 1u : 0u;
         const bool ordered = !scatter && (fa.tile_order || fa.tile_cost);

@@ -7,7 +7,8 @@
 // "-denoise" writes the picture through prt_denoise (guides of "-guide-spp K" samples, default 4; with -adaptive the variance comes from
 // the stats plane); "-guides-out base" writes base_albedo.pfm, base_normal.pfm and base_depth.pfm.  "-orbit-frames F -orbit-yaw RAD"
 // renders F frames along a yaw orbit (InteractiveCamera::changeYaw by RAD between frames), each -spp fresh paths after a prt_reset, guides and
-// prt_denoise_temporal -- the loop of a moving camera -- and writes the last one.
+// prt_denoise_temporal -- the loop of a moving camera -- and writes the last one.  "-filter none|box|tent|gaussian|blackman-harris
+// [-filter-radius R]" renders through prt_set_pixel_filter (antialiasing; every mode above honours it).
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -101,6 +102,8 @@ int main(int argc, char** argv) {
     std::string guides_out;                                        // -guides-out base: base_{albedo,normal,depth}.pfm
     unsigned orbit_frames = 0;                                     // -orbit-frames F: F frames through prt_denoise_temporal ...
     float orbit_yaw = 0.0f;                                        // -orbit-yaw RAD: ... RAD of yaw apart
+    std::string filter = "none";                                   // -filter NAME: the pixel filter (prt_set_pixel_filter)
+    float filter_radius = PRT_FILTER_DEFAULT_RADIUS;               // -filter-radius R
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -126,6 +129,15 @@ int main(int argc, char** argv) {
         else if (a == "-guides-out") guides_out = next();
         else if (a == "-orbit-frames") orbit_frames = (unsigned)std::atoi(next());
         else if (a == "-orbit-yaw") orbit_yaw = (float)std::atof(next());
+        else if (a == "-filter") filter = next();
+        else if (a == "-filter-radius") filter_radius = (float)std::atof(next());
+    }
+    static const char* const filter_names[] = {"none", "box", "tent", "gaussian", "blackman-harris"};
+    uint32_t filter_kind = 5;
+    for (uint32_t k = 0; k < 5; ++k) if (filter == filter_names[k]) filter_kind = k;
+    if (filter_kind == 5) {
+        std::fprintf(stderr, "-filter: unknown filter \"%s\" (none, box, tent, gaussian, blackman-harris)\n", filter.c_str());
+        return 2;
     }
     prt_ctx* ctx = nullptr;
     try {
@@ -178,6 +190,7 @@ int main(int argc, char** argv) {
             CHECK(rc_env);
         }
         CHECK(prt_resize(ctx, window_width, window_height));       // cl_flattenI, :451
+        if (filter_kind != PRT_FILTER_NONE) CHECK(prt_set_pixel_filter(ctx, filter_kind, filter_radius));
 
         const unsigned max_frames = frames ? frames : spp * (unsigned)(cfg.max_bounces > 8 ? cfg.max_bounces : 8) + 64;
         std::vector<int32_t> seeds((size_t)max_frames * 2);

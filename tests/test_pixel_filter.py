@@ -1,0 +1,539 @@
+"""Pixel reconstruction filters of the primary rays (prt_set_pixel_filter, prt_pixel_filter_offsets; include/prt.h).
+The contract checked here: the offsets equal a numpy mirror of the prt.h formulas (box and tent bit for bit, the table kinds within 2 ulp of the
+radius with the table rebuilt in float64), their distribution is the filter's marginal; on the GPU the default is untouched, r = 0 through the
+filter instances equals the unfiltered kernels bit for bit in every mode, an emitter's edge pixels carry the filter-weighted coverage, the device
+offsets are the host's, splits, adaptive freezing, checkpoints and guides keep their invariants, refused configs and the CLI."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
+KINDS = {"box": 1, "tent": 2, "gaussian": 3, "blackman-harris": 4}
+DEFAULT_R = {"box": 0.5, "tent": 1.0, "gaussian": 1.5, "blackman-harris": 2.0}
+BH = (0.35875, 0.48829, 0.14128, 0.01168)
+
+
+def _pkg():
+    import importlib
+    return importlib.import_module("photorealistic-rendering-using-opencl_amd")
+
+
+# ---- prt.h in numpy ----------------------------------------------------------------------------------------------------------------------------
+
+def lowbias32(v):
+    v = np.asarray(v, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        v = v ^ (v >> np.uint32(16)); v = v * np.uint32(0x7FEB352D)
+        v = v ^ (v >> np.uint32(15)); v = v * np.uint32(0x846CA68B)
+        return v ^ (v >> np.uint32(16))
+
+
+def sample_u(gx, gy, k):
+    """(u, v) of paths k (uint32 array) of global pixel (gx, gy): float32, exact"""
+    k = np.asarray(k, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        s = np.uint32(gy) * np.uint32(0x9E3779B9) + np.uint32(gx)
+        ux = k * np.uint32(3242174889) + lowbias32(s)
+        uy = k * np.uint32(2447445414) + lowbias32(s ^ np.uint32(0x68E31DA4))
+    f = lambda x: (x >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return f(ux), f(uy)
+
+
+def marginal_cdf(kind, x, r):
+    """the normalised CDF of the kind's 1-D profile on [-r, r], float64, closed form"""
+    x = np.clip(np.asarray(x, dtype=np.float64), -r, r)
+    if kind == "box":
+        return (x + r) / (2 * r)
+    if kind == "tent":
+        return np.where(x < 0, (x + r) ** 2 / (2 * r * r), 1 - (r - x) ** 2 / (2 * r * r))
+    if kind == "gaussian":
+        s = r / 3.0
+        c = math.exp(-r * r / (2 * s * s))
+        erf = np.vectorize(math.erf)
+        G = lambda t: s * math.sqrt(math.pi / 2) * erf(t / (s * math.sqrt(2))) - c * t
+    else:
+        a0, a1, a2, a3 = BH
+        G = lambda t: (a0 * t + a1 * r / math.pi * np.sin(math.pi * t / r) + a2 * r / (2 * math.pi) * np.sin(2 * math.pi * t / r)
+                       + a3 * r / (3 * math.pi) * np.sin(3 * math.pi * t / r))
+    return (G(x) - G(-r)) / (G(r) - G(-r))
+
+
+def table(kind, r):
+    """T[0 .. 256] of prt.h: F^-1(i / 256) by bisection in float64, rounded to float32, antisymmetric"""
+    T = np.zeros(257, dtype=np.float64)
+    if r > 0:
+        p = np.arange(1, 128) / 256.0
+        lo, hi = np.full(127, -float(r)), np.zeros(127)
+        for _ in range(80):
+            mid = 0.5 * (lo + hi)
+            below = marginal_cdf(kind, mid, r) < p
+            lo, hi = np.where(below, mid, lo), np.where(below, hi, mid)
+        T[1:128] = 0.5 * (lo + hi)
+        T[0] = -r
+    T[129:] = -T[127::-1]
+    T[128] = 0.0
+    return T.astype(np.float32)
+
+
+def warp(kind, r, u, T=None):
+    f = np.float32
+    u = np.asarray(u, dtype=f)
+    r = f(r)
+    if kind == "box":
+        return (u - f(0.5)) * (f(2) * r)
+    if kind == "tent":
+        with np.errstate(invalid="ignore"):
+            lo = r * (np.sqrt(f(2) * u) - f(1))
+            hi = r * (f(1) - np.sqrt(f(2) - f(2) * u))
+        return np.where(u < f(0.5), lo, hi).astype(f)
+    t = u * f(256)
+    j = np.minimum(t.astype(np.int64), 255)
+    t = t - j.astype(f)
+    return (T[j] + t * (T[j + 1] - T[j])).astype(f)
+
+
+def offsets_ref(kind, r, gx, gy, k0, n):
+    k = (np.uint64(k0) + np.arange(n, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
+    u, v = sample_u(gx, gy, k.astype(np.uint32))
+    T = table(kind, r) if kind in ("gaussian", "blackman-harris") else None
+    return np.stack([warp(kind, r, u, T), warp(kind, r, v, T)], -1)
+
+
+# ---- no GPU ------------------------------------------------------------------------------------------------------------------------------------
+
+PIXELS = [(0, 0), (5, 7), (1919, 1079), (2 ** 31 + 5, 4000000000), (123456, 7)]
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_offsets_equal_the_mirror(kind):
+    prt = _pkg()
+    for r in (0.0, DEFAULT_R[kind], 0.3, 4.0):
+        for gx, gy in PIXELS:
+            for k0 in (0, 1000, 2 ** 32 - 50):
+                got = prt.pixel_filter_offsets(kind, r, gx, gy, k0, 100)
+                ref = offsets_ref(kind, r, gx, gy, k0, 100)
+                assert got.shape == (100, 2) and got.dtype == np.float32
+                if kind in ("box", "tent"):
+                    assert (got.view(np.uint32) == ref.view(np.uint32)).all() or (r == 0 and (got == ref).all()), (kind, r, gx, gy, k0)
+                else:
+                    tol = 2 * np.spacing(np.float32(r)) if r > 0 else 0.0
+                    assert np.abs(got - ref).max() <= tol, (kind, r, gx, gy, k0, np.abs(got - ref).max())
+                assert (np.abs(got) <= np.float32(r)).all()
+    d = prt.pixel_filter_offsets(kind, None, 3, 4, 0, 8)              # None = the kind's default radius
+    assert (d.view(np.uint32) == prt.pixel_filter_offsets(kind, DEFAULT_R[kind], 3, 4, 0, 8).view(np.uint32)).all()
+    assert (prt.pixel_filter_offsets("none", None, 3, 4, 0, 8) == 0).all()
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_offsets_follow_the_filter_and_the_centre_is_exact(kind):
+    prt = _pkg()
+    r = DEFAULT_R[kind]
+    for gx, gy in ((17, 3), (640, 480)):
+        d = prt.pixel_filter_offsets(kind, r, gx, gy, 0, 4096).astype(np.float64)
+        for axis in (0, 1):
+            x = np.sort(d[:, axis])
+            F = marginal_cdf(kind, x, r)
+            n = len(x)
+            ks = max(np.max(np.arange(1, n + 1) / n - F), np.max(F - np.arange(0, n) / n))
+            assert ks <= 0.01, (kind, gx, gy, axis, ks)
+    # w(0.5) = 0 exactly: the path k of pixel (gx, gy) whose ux is 2^31 (k = (2^31 - hx) / 3242174889 mod 2^32)
+    gx, gy = 29, 11
+    s = (gy * 0x9E3779B9 + gx) & 0xFFFFFFFF
+    hx = int(lowbias32(np.uint32(s)))
+    k = ((0x80000000 - hx) * pow(3242174889, -1, 2 ** 32)) & 0xFFFFFFFF
+    assert sample_u(gx, gy, np.uint32(k))[0] == np.float32(0.5)
+    for rr in (r, 0.3, 4.0):
+        assert prt.pixel_filter_offsets(kind, rr, gx, gy, k, 1)[0, 0] == 0.0
+
+
+def test_refusals_of_the_host_function():
+    prt = _pkg()
+    lib = prt._capi.load_library()
+    out = np.zeros(8, dtype=np.float32)
+    p = out.ctypes.data_as(C.c_void_p)
+    for kind, r in ((5, 1.0), (99, -1.0), (2, float("nan")), (2, -0.5), (1, 4.5), (3, float("inf")), (4, -float("inf")), (0, 7.0)):
+        assert lib.prt_pixel_filter_offsets(kind, C.c_float(r), 0, 0, 0, 4, p) == prt.PRT_ERR_INVALID_ARGUMENT, (kind, r)
+    for kind in range(5):
+        assert lib.prt_pixel_filter_offsets(kind, C.c_float(-1.0), 0, 0, 0, 4, p) == 0
+        assert lib.prt_pixel_filter_offsets(kind, C.c_float(0.0), 0, 0, 0, 4, p) == 0
+        assert lib.prt_pixel_filter_offsets(kind, C.c_float(4.0), 0, 0, 0, 4, p) == 0
+    with pytest.raises(ValueError):
+        prt.pixel_filter_offsets("bogus", None, 0, 0, 0, 1)
+
+
+def test_cli_refuses_an_unknown_filter():
+    _pkg().build()
+    r = subprocess.run([os.path.join(PKG, "prt_render"), "-filter", "bogus", "-spp", "1"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "bogus" in r.stderr, (r.returncode, r.stderr)
+
+
+# ---- on the GPU --------------------------------------------------------------------------------------------------------------------------------
+
+def _setup(prt, scene_json, W, H, pinhole=False, env=False, cfg_edit=None, text=False):
+    scene = prt.HostScene(scene_json, text=text)
+    cfg = scene.config()
+    if cfg_edit:
+        cfg_edit(cfg)
+    cam = prt.default_camera(W, H)
+    if pinhole:
+        cam.apertureRadius = 0.0
+    r = prt.Renderer(cfg, device=0)
+    r.upload_scene(scene)
+    if env:
+        r.upload_envmap(prt.make_sky(64, 32))
+    r.set_camera(cam)
+    r.resize(W, H)
+    return scene, cfg, cam, r
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _state_fb(r):
+    return np.ascontiguousarray(r.read_state()).view(np.uint8), _bits(r.read_framebuffer())
+
+
+def _same(a, b):
+    return (a[0] == b[0]).all() and (a[1] == b[1]).all()
+
+
+SEEDS_FRAMES = 16 * 16 + 64
+
+
+def _render(prt, r, mode, seeds):
+    r.reset()
+    if mode == "frames":
+        r.render_frames(seeds[:2 * 40])
+    elif mode == "spp":
+        r.render_spp(16, seeds)
+    else:
+        r.render_adaptive(seeds, 4, 16, 0.2)
+    return _state_fb(r)
+
+
+@pytest.mark.gpu
+def test_default_unchanged(prt):
+    W, H = 64, 48
+    seeds = prt.seed_pairs(SEEDS_FRAMES)
+    _, _, _, r = _setup(prt, "cornell_mixed.json", W, H, env=True)
+    base = _render(prt, r, "spp", seeds)
+    v0 = r.kernel_variant()
+    r.set_pixel_filter("none")
+    assert _same(_render(prt, r, "spp", seeds), base)
+    assert r.kernel_variant() == v0 and "filter" not in v0
+    r.set_pixel_filter("tent"); r.set_pixel_filter("none", 0.7)            # back to the default
+    assert _same(_render(prt, r, "spp", seeds), base)
+    r.close()
+
+
+SETS = [("cornell_diffuse.json", False, "LIGHT|DIFF"), ("cornell_coat.json", False, "COAT"), ("cornell_roughcond.json", True, "ROUGH_COND"),
+        ("cornell_roughdiel.json", True, "ROUGH_DIEL"), ("cornell_diffuse.json", False, "generic"), ("cornell_media.json", True, "medium"),
+        ("cornell_mixed.json", True, "generic")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_json,env,tag", SETS)
+def test_zero_radius_through_the_filter_instances_equals_none(prt, scene_json, env, tag):
+    W, H = 40, 24
+    seeds = prt.seed_pairs(SEEDS_FRAMES)
+    _, _, _, r = _setup(prt, scene_json, W, H, env=env)
+    generic = tag == "generic" and scene_json == "cornell_diffuse.json"
+    if generic:
+        r.set_option("generic", 1)
+    for mode in ("frames", "spp", "adaptive"):
+        r.set_pixel_filter("none")
+        base = _render(prt, r, mode, seeds)
+        plain = r.kernel_variant()
+        for kind in ("box", "tent"):
+            r.set_pixel_filter(kind, 0.0)
+            got = _render(prt, r, mode, seeds)
+            v = r.kernel_variant()
+            assert "filter=%s" % kind in v and tag in v, (mode, v)
+            assert v.split(",filter")[0] == plain.split(">")[0], (v, plain)       # the same set, its filter build
+            assert _same(got, base), (scene_json, tag, mode, kind)
+    r.close()
+
+
+def _quad_scene(prt, W, H):
+    """a quad emitter with slanted edges 5 units ahead of the default camera, its normal cross(e0, e1) pointing away from the camera (hit_quad
+    takes rays with dot(n, dir) > 0); black default environment, no OBJ"""
+    cam = prt.default_camera(W, H)
+    cam.apertureRadius = 0.0
+    P, view, up = (np.array(x[:3], dtype=np.float64) for x in (cam.position, cam.view, cam.up))
+    view, up = view / np.linalg.norm(view), up / np.linalg.norm(up)
+    h = np.cross(view, up); h /= np.linalg.norm(h)
+    v = np.cross(h, view); v /= np.linalg.norm(v)
+    c = P + 5.0 * view
+    e0 = -0.35 * h + 1.0 * v
+    e1 = 1.2 * h + 0.3 * v
+    q = [float(x) for x in np.concatenate([c, e0, e1])]
+    js = ('{"settings":{"MAX_BOUNCES":4,"MAX_DIFF_BOUNCES":4,"MAX_SPEC_BOUNCES":4,"MAX_TRANS_BOUNCES":4,"MAX_SCATTERING_EVENTS":4,'
+          '"MARCHING_STEPS":16,"SHADOW_MARCHING_STEPS":16},"scene":{"spheres":[],"quads":[{"vertices":%s,"material":{"color":[3.0,3.0,3.0],"type":0}}]}}'
+          % ("[" + ",".join("%.9g" % x for x in q) + "]"))
+    q = np.array(q, dtype=np.float32).astype(np.float64)
+    return js, cam, q[:3], q[3:6], q[6:9]
+
+
+def _coverage(prt, cam, W, H, c, e0, e1, kind, r, N=96):
+    """the filter-weighted coverage of each pixel by the quad through the pinhole camera model of prt.h (float64): an N x N grid over [-r, r]^2 per
+    pixel, each cell weighted by its exact filter mass.  The quad is hit_quad's region: 0 <= (X - anchor).e <= e.e for both edges, anchor =
+    c - (e0 + e1) / 2 (with edges that are not orthogonal not the parallelogram they span)"""
+    from test_temporal import camera_basis
+    Pc, M, Hz, Vt = camera_basis(cam)
+    edges = np.linspace(-r, r, N + 1)
+    w1 = np.diff(marginal_cdf(kind, edges, r))
+    mid = 0.5 * (edges[1:] + edges[:-1])
+    wgt = np.outer(w1, w1).ravel()                          # [dy, dx]
+    ddy, ddx = np.meshgrid(mid, mid, indexing="ij")
+    ddx, ddy = ddx.ravel(), ddy.ravel()
+    n = np.cross(e0, e1)
+    anchor = c - (e0 + e1) / 2
+    cov = np.zeros((H, W))
+    for y in range(H):
+        xs = np.arange(W, dtype=np.float64)[:, None] + ddx[None, :]
+        sy = (H - 1 - y - ddy[None, :]) / (H - 1.0)
+        sx = xs / (W - 1.0)
+        on = M + Hz * (2 * sx - 1)[..., None] + Vt * (2 * sy - 1)[..., None]
+        d = on - Pc
+        t = ((c - Pc) @ n) / (d @ n)
+        X = Pc + d * t[..., None] - anchor
+        b0, b1 = (X @ e0) / (e0 @ e0), (X @ e1) / (e1 @ e1)
+        hit = (b0 >= 0) & (b0 <= 1) & (b1 >= 0) & (b1 <= 1) & (t > 0)
+        cov[y] = hit.astype(np.float64) @ wgt
+    return cov
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_edge_pixels_carry_the_filter_weighted_coverage(prt, kind):
+    W, H, spp = 96, 64, 1024
+    js, cam, c, e0, e1 = _quad_scene(prt, W, H)
+    scene = prt.HostScene(js, text=True)
+    r = prt.Renderer(scene.config(), device=0)
+    r.upload_scene(scene); r.set_camera(cam); r.resize(W, H)
+    rad = DEFAULT_R[kind]
+    r.set_pixel_filter(kind, rad)
+    r.render_spp(spp, prt.seed_pairs(spp * 4 + 64))
+    img = r.read_framebuffer()[..., 0].astype(np.float64)
+    cov = _coverage(prt, cam, W, H, c, e0, e1, kind, rad)
+    full, empty = cov >= 1 - 1e-12, cov <= 1e-12
+    assert full.sum() > 100 and empty.sum() > 100
+    E = np.median(img[full])
+    assert E > 0 and np.allclose(img[full], E, rtol=1e-5, atol=0), (kind, img[full].min(), img[full].max())
+    assert (img[empty] == 0).all(), kind
+    edge = ~full & ~empty
+    assert edge.sum() > 50
+    se = np.sqrt(cov[edge] * (1 - cov[edge]) / spp)
+    err = np.abs(img[edge] / E - cov[edge])
+    assert (err <= 4 * se + 0.01).all(), (kind, float(err.max()), np.argwhere(edge)[np.argmax(err)].tolist())
+    # the unfiltered render's edge pixels are a centre sample: 0 or E, nothing in between
+    r.set_pixel_filter("none")
+    r.render_spp(spp, prt.seed_pairs(spp * 4 + 64))
+    plain = r.read_framebuffer()[..., 0].astype(np.float64)
+    assert np.isin(plain, [0.0]).sum() + np.isclose(plain, E, rtol=1e-5).sum() == W * H
+    r.close()
+
+
+@pytest.mark.gpu
+def test_device_offsets_equal_the_host(prt):
+    W, H = 16, 16
+    _, _, _, r = _setup(prt, "cornell_diffuse.json", W, H)
+    rng = np.random.default_rng(3)
+    n = 512
+    cases = np.zeros((n, 32), dtype=np.float32)
+    ints = cases.view(np.uint32)
+    ints[:, 0] = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    ints[:, 1] = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    ints[:, 2] = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    ints[:64, 0] %= 2048; ints[:64, 1] %= 2048; ints[:64, 2] %= 4096
+    for kind in KINDS:
+        for rad in (DEFAULT_R[kind], 0.3, 4.0, 0.0):
+            params = np.zeros(80, dtype=np.float32)
+            params.view(np.uint32)[0] = KINDS[kind]
+            params[1] = rad
+            out = r.selftest_fn(12, params, cases)
+            host = np.stack([prt.pixel_filter_offsets(kind, rad, int(a), int(b), int(k), 1)[0] for a, b, k in ints[:, :3]])
+            assert (_bits(out[:, :2]) == _bits(host)).all(), (kind, rad)
+    r.close()
+
+
+@pytest.mark.gpu
+def test_splits_equal_the_whole_frame(prt):
+    W, H = 64, 40
+    seeds = prt.seed_pairs(SEEDS_FRAMES)
+    _, _, _, r = _setup(prt, "cornell_mixed.json", W, H, env=True)
+    r.set_pixel_filter("tent", 1.0)
+    r.render_spp(16, seeds)
+    full = r.read_framebuffer()
+    for n_parts in (2, 3):
+        got = np.zeros_like(full)
+        rows = [[y for y in range(H) if (y // 8) % n_parts == part] for part in range(n_parts)]
+        for part in range(n_parts):
+            r.set_row_blocks(W, H, 8, n_parts, part)
+            r.render_spp(16, seeds)
+            got[rows[part]] = r.read_framebuffer()
+            assert "filter=tent" in r.kernel_variant()
+        assert (_bits(got) == _bits(full)).all(), n_parts
+    got = np.zeros_like(full)
+    for a, b in ((0, 13), (13, 30), (30, H)):
+        r.set_tile(W, H, a, b - a)
+        r.render_spp(16, seeds)
+        got[a:b] = r.read_framebuffer()
+    assert (_bits(got) == _bits(full)).all()
+    r.close()
+
+
+@pytest.mark.gpu
+def test_adaptive_pixels_equal_the_spp_render_of_their_count(prt):
+    W, H = 48, 32
+    seeds = prt.seed_pairs(64 * 16 + 64)
+    _, _, _, r = _setup(prt, "cornell_coat.json", W, H)
+    r.set_pixel_filter("blackman-harris")
+    r.reset()
+    r.render_adaptive(seeds, 8, 64, 0.2)
+    assert "filter=blackman-harris" in r.kernel_variant() and "adaptive" in r.kernel_variant()
+    state, img = np.ascontiguousarray(r.read_state()), r.read_framebuffer().reshape(-1, 4)
+    k = state["samples"]
+    ks = np.unique(k)
+    assert len(ks) >= 3, ks
+    for kk in ks[:6]:
+        r.reset()
+        r.render_spp(int(kk), seeds)
+        s2, i2 = np.ascontiguousarray(r.read_state()), r.read_framebuffer().reshape(-1, 4)
+        m = k == kk
+        assert (state.view(np.uint8).reshape(state.size, -1)[m] == s2.view(np.uint8).reshape(s2.size, -1)[m]).all(), kk
+        assert (_bits(img)[m] == _bits(i2)[m]).all(), kk
+    r.close()
+
+
+@pytest.mark.gpu
+def test_checkpoint_resume_and_determinism(prt):
+    W, H = 48, 32
+    seeds = prt.seed_pairs(200)
+    _, _, _, r = _setup(prt, "cornell_roughdiel.json", W, H, env=True)
+    r.set_pixel_filter("gaussian")
+    r.render_frames(seeds[:2 * 120])
+    whole = _state_fb(r)
+    r.reset()
+    r.render_frames(seeds[:2 * 120])
+    assert _same(_state_fb(r), whole)                       # two identical calls
+    r.reset()
+    r.render_frames(seeds[:2 * 50])
+    saved = r.read_state()
+    r.reset()
+    r.write_state(saved)
+    r.render_frames(seeds[2 * 50:2 * 120], first_frame=51)
+    assert _same(_state_fb(r), whole)
+    r.close()
+
+
+@pytest.mark.gpu
+def test_guides_under_a_filter(prt):
+    W, H = 64, 48
+    _, _, _, r = _setup(prt, "cornell_mixed.json", W, H, env=True)
+    r.render_guides(4)
+    g4 = r.read_guides()
+    r.render_guides(1)
+    g1 = r.read_guides()
+    r.set_pixel_filter("box", 0.5)
+    with pytest.raises(prt.PrtError):
+        r.read_guides()                                      # stale
+    r.render_guides(4)
+    assert (_bits(r.read_guides()) == _bits(g4)).all()
+    for kind in KINDS:
+        r.set_pixel_filter(kind)
+        r.render_guides(1)
+        assert (_bits(r.read_guides()) == _bits(g1)).all(), kind
+        r.render_guides(4)
+        g = r.read_guides()
+        assert np.isfinite(g).all()
+        if kind != "box":
+            assert not (_bits(g) == _bits(g4)).all(), kind
+    r.close()
+
+
+@pytest.mark.gpu
+def test_refused_configs_and_the_pool_option(prt):
+    W, H = 32, 24
+    scene = prt.HostScene("cornell_mixed.json")
+    edits = [lambda c: setattr(c, "view_option", 1), lambda c: setattr(c, "pick_random_light", 1),
+             lambda c: setattr(c, "env_importance_sampling", 1)]
+    for edit in edits:
+        cfg = scene.config()
+        edit(cfg)
+        rr = prt.Renderer(cfg, device=0)
+        with pytest.raises(prt.PrtError) as e:
+            rr.set_pixel_filter("tent")
+        assert e.value.code == prt.PRT_ERR_UNSUPPORTED
+        rr.set_pixel_filter("none")
+        rr.close()
+    sdf = prt.HostScene("cornell_sdf.json")
+    rs = prt.Renderer(sdf.config(), device=0)
+    with pytest.raises(prt.PrtError) as e:
+        rs.set_pixel_filter("box")
+    assert e.value.code == prt.PRT_ERR_UNSUPPORTED
+    rs.close()
+    _, _, _, r = _setup(prt, "cornell_diffuse.json", W, H)
+    for kind, rad in ((9, 1.0), ("tent", float("nan")), ("tent", -0.25), ("box", 4.01)):
+        with pytest.raises(prt.PrtError) as e:
+            r.set_pixel_filter(kind, rad)
+        assert e.value.code == prt.PRT_ERR_INVALID_ARGUMENT
+    seeds = prt.seed_pairs(SEEDS_FRAMES)
+    r.set_pixel_filter("tent")
+    a = _render(prt, r, "spp", seeds)
+    r.set_option("pool", 1)
+    b = _render(prt, r, "spp", seeds)
+    assert _same(a, b) and "pool" not in r.kernel_variant() and "filter=tent" in r.kernel_variant()
+    r.close()
+
+
+@pytest.mark.gpu
+def test_denoisers_on_a_filtered_render(prt):
+    W, H = 64, 48
+    _, _, cam, r = _setup(prt, "cornell_coat.json", W, H)
+    r.set_pixel_filter("tent")
+    r.render_spp(8, prt.seed_pairs(8 * 16 + 64))
+    r.render_guides(4)
+    assert np.isfinite(r.denoise()).all()
+    assert np.isfinite(r.denoise_temporal()).all()
+    r.set_camera(prt.orbit_camera(W, H, d_yaw=0.05))
+    r.reset()
+    r.render_spp(8, prt.seed_pairs(8 * 16 + 64, first_frame=1001))
+    r.render_guides(4)
+    assert np.isfinite(r.denoise_temporal()).all()
+    r.read_history()                                         # the history survived the camera move and the filter
+    r.close()
+
+
+@pytest.mark.gpu
+def test_cli_filter(prt, tmp_path):
+    W, H, spp = 48, 32, 16
+    exe = os.path.join(PKG, "prt_render")
+    base = [exe, "-scene", os.path.join(ROOT, "scenes", "cornell_coat.json"), "-models", os.path.join(ROOT, "scenes", "models") + "/",
+            "-width", str(W), "-height", str(H), "-spp", str(spp)]
+    out = tmp_path / "t.pfm"
+    r = subprocess.run(base + ["-filter", "tent", "-out", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    raw = open(out, "rb").read()
+    img = np.frombuffer(raw[raw.index(b"-1.0\n") + 5:], dtype=np.float32).reshape(H, W, 3)
+    scene = prt.HostScene("cornell_coat.json")
+    cfg = scene.config()
+    rr = prt.Renderer(cfg, device=0)
+    rr.upload_scene(scene); rr.set_camera(prt.default_camera(W, H)); rr.resize(W, H)
+    rr.set_pixel_filter("tent")
+    rr.render_spp(spp, prt.seed_pairs(spp * max(cfg.max_bounces, 8) + 64))
+    assert (_bits(img) == _bits(rr.read_framebuffer()[..., :3])).all()
+    rr.close()
+    for extra in (["-adaptive", "0.2", "-min-spp", "4", "-denoise"], ["-orbit-frames", "2", "-orbit-yaw", "0.05"]):
+        r = subprocess.run(base + ["-filter", "blackman-harris", "-filter-radius", "1.5", "-out", str(tmp_path / "x.png")] + extra,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and os.path.getsize(tmp_path / "x.png") > 0, (extra, r.stderr)
+    r = subprocess.run(base + ["-filter", "bogus", "-out", str(tmp_path / "y.png")], capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and "bogus" in r.stderr and not (tmp_path / "y.png").exists()
