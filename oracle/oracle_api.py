@@ -130,7 +130,8 @@ class _Job(C.Structure):
                 ("width", C.c_int), ("full_height", C.c_int), ("row0", C.c_int), ("rows", C.c_int),
                 ("block_rows", C.c_int), ("n_parts", C.c_int), ("part", C.c_int),
                 ("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("seed_pairs", C.c_void_p),
-                ("state", C.c_void_p), ("out_rgba", C.c_void_p), ("spp_limit", C.c_uint32), ("n_threads", C.c_int)]
+                ("state", C.c_void_p), ("out_rgba", C.c_void_p), ("spp_limit", C.c_uint32), ("n_threads", C.c_int),
+                ("pixel_offsets", C.c_void_p), ("offset_paths", C.c_uint32)]
 
 
 class _Diag(C.Structure):
@@ -151,8 +152,11 @@ class Restatement:
         self.last_diag = None
 
     def render(self, cfg, desc, camera, W, H, seed_pairs, first_frame=1, state=None, env=None,
-               spp_limit=0, threads=8, row0=0, rows=None, blocks=None):
-        """blocks = (block_rows, n_parts, part) selects interleaved row blocks (prt_set_row_blocks)"""
+               spp_limit=0, threads=8, row0=0, rows=None, blocks=None, offsets=None):
+        """blocks = (block_rows, n_parts, part) selects interleaved row blocks (prt_set_row_blocks).
+        offsets: None, or a float32 array (H, W, K, 2) of pixel-filter offsets {dx, dy} of the WHOLE frame (global row, column, path index
+        since the last reset; include/prt.h prt_set_pixel_filter): path k of a pixel starts through (x + dx, y + dy).  A path beyond K
+        is an error (pto_render returns -6), not a clamp"""
         if blocks is not None:
             rows = sum(1 for r in range(H) if (r // blocks[0]) % blocks[1] == blocks[2])
         rows = H if rows is None else rows
@@ -177,6 +181,12 @@ class Restatement:
         job.out_rgba = _ptr(img)
         job.spp_limit = spp_limit
         job.n_threads = threads
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.float32)
+            if offsets.ndim != 4 or offsets.shape[0] != H or offsets.shape[1] != W or offsets.shape[3] != 2:
+                raise ValueError("offsets must be (H, W, K, 2), got %s" % (offsets.shape,))
+            job.pixel_offsets = _ptr(offsets)
+            job.offset_paths = offsets.shape[2]
         diag = _Diag()
         rc = self.lib.pto_render(C.byref(job), C.byref(diag))
         if rc != 0:

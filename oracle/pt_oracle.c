@@ -148,7 +148,8 @@ static inline int checkRefractionConstraint(v3 wi, v3 wo, float eta, float cosTh
 }
 
 /* ---- kernels/camera.cl:17-66 ---- */
-static Ray createCamRay(int cx, int cy, int width, int height, const prt_camera* cam, Rng* rng) {
+/* off: NULL, or the path's {dx, dy} (pto_job::pixel_offsets): include/prt.h, prt_set_pixel_filter "Camera ray" */
+static Ray createCamRay(int cx, int cy, int width, int height, const prt_camera* cam, Rng* rng, const float* off) {
     v3 view = vnormalize(vload(cam->view));
     v3 up = vnormalize(vload(cam->up));
     v3 horizontalAxis = vnormalize(vcross(view, up));
@@ -161,6 +162,10 @@ static Ray createCamRay(int cx, int cy, int width, int height, const prt_camera*
     int pixely = height - cy - 1;
     float sx = (float)pixelx / (width - 1.0f);
     float sy = (float)pixely / (height - 1.0f);
+    if (off) {                  /* sx = (x + dx) / (W-1), sy = (H-1-y - dy) / (H-1), f32 */
+        sx = ((float)cx + off[0]) / (width - 1.0f);
+        sy = ((float)(height - 1 - cy) - off[1]) / (height - 1.0f);
+    }
     v3 pointOnPlane = vadd(vadd(middle, vscale(horizontal, (2 * sx) - 1)), vscale(vertical, (2 * sy) - 1));
     v3 pointOnImagePlane = vadd(position, vscale(vsub(pointOnPlane, position), cam->focalDistance));
     v3 aperturePoint;
@@ -1241,8 +1246,12 @@ done:
 }
 
 /* ---- kernels/main.cl:66-163 render_kernel, one work-item ---- */
-static void render_pixel(Scene* sc, const prt_camera* cam, int width, int height, int gx, int gy,
-                         uint32_t framenumber, int32_t random0, int32_t random1, prt_path_state* st, float* pixel_rgba) {
+/* offsets: NULL, or the pixel's row of pto_job::pixel_offsets (offset_paths entries).  Returns 0, or -6 when a path starts beyond the table
+ * (the state is then left as it was before this segment) */
+static int render_pixel(Scene* sc, const prt_camera* cam, int width, int height, int gx, int gy,
+                        uint32_t framenumber, int32_t random0, int32_t random1, prt_path_state* st, float* pixel_rgba,
+                        const float* offsets, uint32_t offset_paths) {
+    if (offsets && (st->reset || st->samples == 0) && st->samples >= offset_paths) return -6;
     Rng rng;
     rng.s0 = (uint32_t)gx * framenumber % 1000u + ((uint32_t)random0 * 100u);     /* main.cl:108-109 (Q14) */
     rng.s1 = (uint32_t)gy * framenumber % 1000u + ((uint32_t)random1 * 100u);
@@ -1262,7 +1271,7 @@ static void render_pixel(Scene* sc, const prt_camera* cam, int width, int height
         st->was_specular = 1;
         st->reset = 0;
         st->mask[0] = st->mask[1] = st->mask[2] = 1.0f;
-        ray = createCamRay(gx, gy, width, height, cam, &rng);
+        ray = createCamRay(gx, gy, width, height, cam, &rng, offsets ? offsets + 2 * (size_t)(st->samples - 1u) : NULL);
     }
     float r[4];
     radiance(sc, &ray, st, &rng, r);
@@ -1287,6 +1296,7 @@ static void render_pixel(Scene* sc, const prt_camera* cam, int width, int height
     st->dist = ray.time;
     const float ns = view ? 1.0f : (float)st->samples;         /* main.cl:158-162: a debug view writes the accumulator as it is */
     pixel_rgba[0] = st->acc[0] / ns; pixel_rgba[1] = st->acc[1] / ns; pixel_rgba[2] = st->acc[2] / ns; pixel_rgba[3] = st->acc[3] / ns;
+    return 0;
 }
 
 /* Q8: the padding lane of the `const Medium` float3 members.  The reference build (clang, x86-64)
@@ -1299,6 +1309,7 @@ typedef struct {
     const pto_job* job;
     Scene scene;
     size_t lo, hi;
+    int err;
 } Worker;
 
 static void* worker_main(void* arg) {
@@ -1319,8 +1330,10 @@ static void* worker_main(void* arg) {
 #ifdef PTO_TRACE
             pto_tr_cur = pto_trace_buf ? pto_trace_buf + ((size_t)id * j->n_frames + f) * 4 : 0;
 #endif
-            render_pixel(&w->scene, j->camera, j->width, j->full_height, gx, gy, j->first_frame + f,
-                         j->seed_pairs[2 * f], j->seed_pairs[2 * f + 1], st, px);
+            const float* offs = j->pixel_offsets ? j->pixel_offsets + ((size_t)gy * (size_t)j->width + (size_t)gx) * j->offset_paths * 2 : NULL;
+            const int rc = render_pixel(&w->scene, j->camera, j->width, j->full_height, gx, gy, j->first_frame + f,
+                                        j->seed_pairs[2 * f], j->seed_pairs[2 * f + 1], st, px, offs, j->offset_paths);
+            if (rc) { w->err = rc; return NULL; }
         }
     }
     return NULL;
@@ -1371,6 +1384,8 @@ int pto_render(const pto_job* j, pto_diag* diag) {
         ++started;
     }
     if (nt > 1) for (int t = 0; t < started; ++t) pthread_join(th[t], NULL);
+    int err = 0;
+    for (int t = 0; t < started; ++t) if (ws[t].err && !err) err = ws[t].err;
     if (diag) {
         diag->max_stack = 0; diag->max_shadow_stack = 0;
         for (int t = 0; t < started; ++t) {
@@ -1379,5 +1394,5 @@ int pto_render(const pto_job* j, pto_diag* diag) {
         }
     }
     free(ws); free(th); free(guarded);
-    return 0;
+    return err;
 }

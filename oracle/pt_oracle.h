@@ -19,6 +19,12 @@ typedef struct pto_job {
     float* out_rgba;                            /* width*rows*4, out */
     uint32_t spp_limit;                         /* 0 = progressive; N = freeze after the N-th path */
     int n_threads;
+    /* optional pixel-filter offsets (include/prt.h, prt_set_pixel_filter "Camera ray"): NULL = every path starts through the pixel
+     * centre.  Else float[2] entries {dx, dy} indexed by (global row gy, column gx, path index k):
+     * pixel_offsets[((gy * width + gx) * offset_paths + k) * 2], gy over full_height; path k = samples - 1 of its pixel.  The table
+     * comes from outside: the oracle knows neither the warps nor the hash.  A path index >= offset_paths makes pto_render return -6. */
+    const float* pixel_offsets;
+    uint32_t offset_paths;
 } pto_job;
 
 typedef struct pto_diag { int max_stack, max_shadow_stack; } pto_diag;

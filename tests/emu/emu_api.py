@@ -15,7 +15,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 def build():
     srcs = [os.path.join(HERE, "pt_emu.cpp"), os.path.join(PKG, "csrc", "hip", "pt_pack.cpp")]
-    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_device.h", "pt_layout.h", "pt_pack.h", "pt_selftest.h")] + \
+    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_device.h", "pt_filter.h", "pt_layout.h", "pt_pack.h", "pt_selftest.h")] + \
         [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
     if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
         return LIB
@@ -37,7 +37,8 @@ def lib():
         _lib.emu_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_void_p]
+                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_void_p,
+                                    C.c_uint32, C.c_float, C.c_void_p]
         _lib.emu_selftest_fn.restype = None
         _lib.emu_selftest_fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     return _lib
@@ -52,8 +53,9 @@ def selftest_fn(fn, params, cases):
 
 
 def render(state_dtype, cfg, desc, camera, W, H, seed_pairs, first_frame=1, state=None, env=None, spp_limit=0,
-           walk_min_lanes=8, sched_seed=0, row0=0, rows=None, blocks=None, img=None, window=None, ahead=None):
-    """same call shape as oracle_api.Restatement.render.  `window` / `ahead`: the launch covers the first `window` frames of
+           walk_min_lanes=8, sched_seed=0, row0=0, rows=None, blocks=None, img=None, window=None, ahead=None, pixel_filter=None):
+    """same call shape as oracle_api.Restatement.render.  pixel_filter = (kind 1 .. 4, radius, table): prt_set_pixel_filter's state, run
+    through the PT_MATS_FILTER builds; table = the 257 float32 entries T[0 .. 256] of the Gaussian and Blackman-Harris kinds, None otherwise.  `window` / `ahead`: the launch covers the first `window` frames of
     seed_pairs only, but (FrameArgs::run_ahead, "N spp" launches) a lane may go on into the rest while its wave waits for
     others; `ahead` (uint32 per pixel, in / out) is how far each pixel is into the NEXT launch."""
     if blocks is not None:
@@ -71,12 +73,21 @@ def render(state_dtype, cfg, desc, camera, W, H, seed_pairs, first_frame=1, stat
         env = np.ascontiguousarray(env, dtype=np.float32)
         envp, eh, ew = env.ctypes.data_as(C.c_void_p), env.shape[0], env.shape[1]
     b = blocks if blocks is not None else (1, 1, 0)
+    fkind, frad, ftab = 0, 0.0, None
+    if pixel_filter is not None:
+        fkind, frad, ftab = pixel_filter
+        if ftab is not None:
+            ftab = np.ascontiguousarray(ftab, dtype=np.float32)
+            assert ftab.shape == (257,)
     err = C.create_string_buffer(256)
     rc = lib().emu_render(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(desc), C.c_void_p), C.cast(C.pointer(camera), C.c_void_p),
                           envp, ew, eh, W, H, row0, rows, b[0], b[1], b[2], first_frame, n_frames,
                           seeds.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p), img.ctypes.data_as(C.c_void_p),
                           spp_limit, walk_min_lanes, sched_seed, err, 256, seed_frames,
-                          ahead.ctypes.data_as(C.c_void_p) if ahead is not None else None)
+                          ahead.ctypes.data_as(C.c_void_p) if ahead is not None else None,
+                          int(fkind), float(frad), ftab.ctypes.data_as(C.c_void_p) if ftab is not None else None)
     if rc:
-        raise RuntimeError("emu_render failed (%d): %s" % (rc, err.value.decode()))
+        e = RuntimeError("emu_render failed (%d): %s" % (rc, err.value.decode()))
+        e.code = rc
+        raise e
     return state, img

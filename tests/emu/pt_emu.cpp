@@ -155,11 +155,15 @@ void run_tile(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, int
 }  // namespace
 
 // same arguments as oracle/pt_oracle.h's pto_job, plus the schedule.  Returns 0, or the prt error code of pack_scene.
+// filter_kind / filter_r / filter_tab: prt_set_pixel_filter's state as prt_api.cpp puts it into FrameArgs (tab: T[0 .. 256] of the Gaussian and
+// Blackman-Harris kinds, else null).  A kind other than PRT_FILTER_NONE runs the PT_MATS_FILTER builds launch_render picks
+// (pt_inst_filter_*.hip), and is refused (PRT_ERR_UNSUPPORTED) for the configs prt_set_pixel_filter refuses.
 extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, const prt_camera* camera, const float* env_rgb, int env_w, int env_h,
                           int width, int full_height, int row0, int rows, int block_rows, int n_parts, int part,
                           uint32_t first_frame, uint32_t n_frames, const int32_t* seed_pairs, prt_path_state* state, float* out_rgba,
                           uint32_t spp_limit, uint32_t walk_min_lanes, uint32_t sched_seed, char* err, int err_len,
-                          uint32_t seed_frames, uint32_t* ahead) {   // ahead != null: FrameArgs::run_ahead, per-pixel frames ahead in / out
+                          uint32_t seed_frames, uint32_t* ahead,     // ahead != null: FrameArgs::run_ahead, per-pixel frames ahead in / out
+                          uint32_t filter_kind, float filter_r, const float* filter_tab) {
     PackedScene ps;
     std::string perr;
     const int rc = pack_scene(*cfg, desc, ps, perr);
@@ -187,6 +191,22 @@ extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, con
     fa.unfinished = nullptr; fa.unfinished_host = nullptr; fa.tile_first = 0; fa.tile_stride = 1;
     fa.walk_min_lanes = walk_min_lanes ? walk_min_lanes : 8;
     fa.tri_sixteenths = 4;
+    fa.filter_kind = filter_kind; fa.filter_r = filter_r; fa.filter_tab = filter_tab;
+    const bool filtered = filter_kind != PRT_FILTER_NONE;
+    if (filtered) {
+        const char* why = nullptr;
+        if (filter_kind > PRT_FILTER_BLACKMAN_HARRIS || !(filter_r >= 0.0f && filter_r <= 4.0f)) why = "pixel filter: unknown kind or radius outside [0, 4]";
+        else if ((filter_kind == PRT_FILTER_GAUSSIAN || filter_kind == PRT_FILTER_BLACKMAN_HARRIS) && !filter_tab) why = "pixel filter: the kind needs its table";
+        if (why) {
+            if (err && err_len > 0) { std::strncpy(err, why, (size_t)err_len - 1); err[err_len - 1] = 0; }
+            return PRT_ERR_INVALID_ARGUMENT;
+        }
+        // no filter instances of these sets (prt.h prt_set_pixel_filter)
+        if (sc.env_is || sc.pick_random_light || sc.view || sc.n_sdfs) {
+            if (err && err_len > 0) { std::strncpy(err, "pixel filter: refused with a debug view, SDF primitives, the light pick or environment sampling", (size_t)err_len - 1); err[err_len - 1] = 0; }
+            return PRT_ERR_UNSUPPORTED;
+        }
+    }
     constexpr unsigned LD = PRT_MAT_LIGHT | PRT_MAT_DIFF;
     const char* e_generic = std::getenv("PT_EMU_GENERIC");
     const bool generic = e_generic && e_generic[0] == '1';
@@ -195,7 +215,29 @@ extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, con
     for (int ty = 0; ty < tiles_y; ++ty)
         for (int tx = 0; tx < tiles_x; ++tx) {
             // the variant launch_render (pt_kernels.hip) picks
-            if (sc.env_is) {
+            if (filtered) {
+                // the PT_MATS_FILTER builds (pt_inst_filter_*.hip): the compiled sets with the distribution bits their files give them (any
+                // other scene of a set, and every set with a medium but LIGHT|DIFF, takes the filtered generic dispatch)
+                constexpr unsigned F = PT_MATS_FILTER;
+                constexpr unsigned CO = LD | PRT_MAT_COAT | F | ((unsigned)PRT_DIST_BECKMANN << PT_MATS_DIST_SHIFT);
+                constexpr unsigned RC = LD | PRT_MAT_ROUGH_COND | F | ((unsigned)PRT_DIST_GGX << PT_MATS_DIST_SHIFT);
+                constexpr unsigned RD = LD | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL | F | ((unsigned)PRT_DIST_GGX << PT_MATS_DIST_SHIFT);
+                const unsigned am = generic ? 0u : sc.active_mats;
+                const bool med = sc.has_medium != 0;
+                if (am == LD) {
+                    if (!med) run_tile<LD | F, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                    else run_tile<LD | F, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                } else if (!med && am == (LD | PRT_MAT_COAT) && sc.dist_mask == (unsigned)PRT_DIST_BECKMANN) {
+                    run_tile<CO, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                } else if (!med && am == (LD | PRT_MAT_ROUGH_COND) && sc.dist_mask == (unsigned)PRT_DIST_GGX) {
+                    run_tile<RC, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                } else if (!med && am == (LD | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL) && sc.dist_mask == (unsigned)PRT_DIST_GGX) {
+                    run_tile<RD, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                } else {
+                    if (!med) run_tile<F, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                    else run_tile<F, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
+                }
+            } else if (sc.env_is) {
                 run_tile<PT_MATS_ENVIS, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
             } else if (sc.pick_random_light) {
                 if (!sc.has_medium) run_tile<PT_MATS_PICK, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
