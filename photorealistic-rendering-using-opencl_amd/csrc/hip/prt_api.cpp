@@ -18,6 +18,7 @@
 #include "pt_launch.h"
 #include "pt_layout.h"
 #include "pt_pack.h"
+#include "pt_variant.h"
 
 using namespace prt;
 
@@ -985,8 +986,7 @@ extern "C" int prt_set_pixel_filter(prt_ctx* c, uint32_t kind, float radius) {
     if (!filter_radius(kind, radius, r))
         return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_pixel_filter: unknown kind, or a radius outside 0 .. 4 (PRT_FILTER_DEFAULT_RADIUS: the kind's default)");
     if (kind != PRT_FILTER_NONE) {
-        const char* no = c->cfg.view_option != PRT_VIEW_RESULTS ? "a debug view" : (c->cfg.geom_flags & PRT_GEOM_SDF) ? "SDF primitives"
-                       : c->cfg.pick_random_light ? "pick_random_light" : c->cfg.env_importance_sampling ? "env_importance_sampling" : nullptr;
+        const char* no = filter_unsupported(c->cfg);
         if (no) return fail(c, PRT_ERR_UNSUPPORTED, std::string("prt_set_pixel_filter: no filter instances are built for ") + no);
     }
     HIPCHK(c, hipSetDevice(c->device));

@@ -1,12 +1,3 @@
-// pt_inst_envis.hip -- render_kernel with environment-map importance sampling (prt_config::env_importance_sampling; not in the
-// reference): the run-time-dispatched material set, surfaces only
+// pt_inst_envis.hip -- render_kernel for environment-map importance sampling (prt_config::env_importance_sampling), surfaces only (rows: pt_variant.h)
 #include "pt_render.h"
-
-namespace prt {
-
-PT_DECLARE_SET(launch_set_envis) {
-    (void)medium;                                        // pack_scene refuses the combination
-    return launch_variant<PT_MATS_ENVIS, false>("render_kernel<generic,env_importance_sampling>", sc, cam, S, fa, fb, stream, lo);
-}
-
-}  // namespace prt
+namespace prt { PT_VARIANTS_ENVIS(PT_INSTANTIATE_VARIANT) }

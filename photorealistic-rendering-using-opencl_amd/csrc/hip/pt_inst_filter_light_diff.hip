@@ -1,13 +1,3 @@
-// pt_inst_filter_light_diff.hip -- render_kernel compiled for the material set LIGHT|DIFF under a pixel filter (PT_MATS_FILTER, prt_set_pixel_filter),
-// medium off / on
+// pt_inst_filter_light_diff.hip -- render_kernel for the set LIGHT|DIFF under a pixel filter (prt_set_pixel_filter), medium off / on (rows: pt_variant.h)
 #include "pt_render.h"
-
-namespace prt {
-
-PT_DECLARE_SET(launch_set_filter_light_diff) {
-    constexpr unsigned M = PRT_MAT_LIGHT | PRT_MAT_DIFF | PT_MATS_FILTER;
-    if (medium) return launch_variant<M, true>("render_kernel<LIGHT|DIFF,medium,filter>", sc, cam, S, fa, fb, stream, lo);
-    return launch_variant<M, false>("render_kernel<LIGHT|DIFF,filter>", sc, cam, S, fa, fb, stream, lo);
-}
-
-}  // namespace prt
+namespace prt { PT_VARIANTS_FILTER_LIGHT_DIFF(PT_INSTANTIATE_VARIANT) }

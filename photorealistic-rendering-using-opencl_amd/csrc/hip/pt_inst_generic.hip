@@ -1,12 +1,3 @@
-// pt_inst_generic.hip -- render_kernel compiled for the material set generic (any other ACTIVE_MATS: the materials dispatched at run time), medium off / on
+// pt_inst_generic.hip -- render_kernel for any other ACTIVE_MATS (the materials dispatched at run time), medium off / on (rows: pt_variant.h)
 #include "pt_render.h"
-
-namespace prt {
-
-PT_DECLARE_SET(launch_set_generic) {
-    constexpr unsigned M = 0u;
-    if (medium) return launch_variant<M, true>("render_kernel<generic,medium>", sc, cam, S, fa, fb, stream, lo);
-    return launch_variant<M, false>("render_kernel<generic>", sc, cam, S, fa, fb, stream, lo);
-}
-
-}  // namespace prt
+namespace prt { PT_VARIANTS_GENERIC(PT_INSTANTIATE_VARIANT) }

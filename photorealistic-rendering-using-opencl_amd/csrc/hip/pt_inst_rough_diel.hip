@@ -1,15 +1,3 @@
-// pt_inst_rough_diel.hip -- render_kernel compiled for the material set LIGHT|DIFF|DIEL|ROUGH_DIEL (config 3b), without a medium
+// pt_inst_rough_diel.hip -- render_kernel for the material set LIGHT|DIFF|DIEL|ROUGH_DIEL (config 3b), without a medium: every microfacet distribution, and GGX alone (rows: pt_variant.h)
 #include "pt_render.h"
-
-namespace prt {
-
-PT_DECLARE_SET(launch_set_rough_diel) {
-    constexpr unsigned M = PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL;
-    if (medium) return launch_set_generic(true, sc, cam, S, fa, fb, stream, lo);      // (not compiled with a medium: no BASELINE config has both)
-    // the set once more for scenes whose microfacet lobes are all GGX (the BASELINE config's): PT_MATS_DISTS, pt_device.h
-    if (!lo.any_dist && sc.dist_mask == (unsigned)PRT_DIST_GGX)
-        return launch_variant<M | ((unsigned)PRT_DIST_GGX << PT_MATS_DIST_SHIFT), false>("render_kernel<LIGHT|DIFF|DIEL|ROUGH_DIEL; GGX>", sc, cam, S, fa, fb, stream, lo);
-    return launch_variant<M, false>("render_kernel<LIGHT|DIFF|DIEL|ROUGH_DIEL>", sc, cam, S, fa, fb, stream, lo);
-}
-
-}  // namespace prt
+namespace prt { PT_VARIANTS_ROUGH_DIEL(PT_INSTANTIATE_VARIANT) }

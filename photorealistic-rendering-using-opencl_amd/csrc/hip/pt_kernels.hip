@@ -1,6 +1,6 @@
-// pt_kernels.hip -- the small kernels of libprt and the dispatch to the render kernel's compiled material sets.
+// pt_kernels.hip -- the small kernels of libprt and launch_render: the row of the variant table a launch takes (pt_variant.h), launched.
 //
-//   render_kernel<MATS, MEDIUM, WAVES>   pt_render.h, instantiated by pt_inst_*.hip (one file per material set: they compile in parallel)
+//   render_kernel<MATS, MEDIUM, WAVES>   pt_render.h, instantiated by pt_inst_*.hip (one file per group of table rows: they compile in parallel)
 //   state_to_rtd / rtd_to_state          80 B/px SoA planes <-> the reference's 112 B RTD records
 //   count_kernel                         sum of samples / segments / frozen pixels (Msamples/s accounting)
 //   live_count / live_scan / live_write  the live-pixel list of prt_render_adaptive's list launches
@@ -275,39 +275,21 @@ void dump_phase_clocks() {
 }
 #endif
 
-// Variant choice = the AOT analogue of the reference's per-scene program build (include/CL/cl_kernel.h:226-345 compiles exactly the
-// scene's ACTIVE_MATS): the material sets of the BASELINE configs are compiled (LIGHT|DIFF, +COAT, +ROUGH_COND, +DIEL|ROUGH_DIEL),
-// any other set runs the generic variant, which dispatches on the material's type bits at run time -- the same code, the same bits
-// (LaunchOpts::generic forces it: the tests run every golden through both).
+// the rule is select_variant's (pt_variant.h); here the row it names is launched
 RenderLaunch launch_render(const DevScene& sc, const DevCamera& cam, const DevState& S, const FrameArgs& fa, float4* fb,
                            hipStream_t stream, const LaunchOpts& lo) {
-    const unsigned am = sc.active_mats;
-    const bool medium = sc.has_medium != 0;
 #ifdef PT_DEV_ONE_VARIANT                 // development builds (tools/): only the headline variant, compiles in seconds
-    if (sc.n_sdfs || medium || sc.view || am != (PRT_MAT_LIGHT | PRT_MAT_DIFF)) return RenderLaunch{};
-    return launch_set_light_diff(false, sc, cam, S, fa, fb, stream, lo);
+    if (sc.n_sdfs || sc.has_medium || sc.view || sc.active_mats != PT_SET_LIGHT_DIFF) return RenderLaunch{};
+    const Variant* v = &k_variants[0];
 #else
-    if (fa.filter_kind != PRT_FILTER_NONE) {       // prt_set_pixel_filter (which refuses the env-sampling, light-pick, view and SDF configs)
-        if (!lo.generic) {
-            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF)) return launch_set_filter_light_diff(medium, sc, cam, S, fa, fb, stream, lo);
-            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_COAT)) return launch_set_filter_coat(medium, sc, cam, S, fa, fb, stream, lo);
-            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_ROUGH_COND)) return launch_set_filter_rough_cond(medium, sc, cam, S, fa, fb, stream, lo);
-            if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL)) return launch_set_filter_rough_diel(medium, sc, cam, S, fa, fb, stream, lo);
-        }
-        return launch_set_filter_generic(medium, sc, cam, S, fa, fb, stream, lo);
-    }
-    if (sc.env_is) return launch_set_envis(medium, sc, cam, S, fa, fb, stream, lo);              // (pack_scene refuses it with a medium, SDFs, views, the light pick)
-    if (sc.pick_random_light) return launch_set_pick(medium, sc, cam, S, fa, fb, stream, lo);     // PICK_RANDOM_LIGHT: the generic set (pack_scene refuses it with SDFs / views)
-    if (sc.view) return sc.n_sdfs ? launch_set_view_sdf(medium, sc, cam, S, fa, fb, stream, lo) : launch_set_view(medium, sc, cam, S, fa, fb, stream, lo);
-    if (sc.n_sdfs) return launch_set_sdf(medium, sc, cam, S, fa, fb, stream, lo);      // H_SDF scenes: the generic set with the raymarcher
-    if (!lo.generic) {
-        if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF)) return launch_set_light_diff(medium, sc, cam, S, fa, fb, stream, lo);
-        if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_COAT)) return launch_set_coat(medium, sc, cam, S, fa, fb, stream, lo);
-        if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_ROUGH_COND)) return launch_set_rough_cond(medium, sc, cam, S, fa, fb, stream, lo);
-        if (am == (PRT_MAT_LIGHT | PRT_MAT_DIFF | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL)) return launch_set_rough_diel(medium, sc, cam, S, fa, fb, stream, lo);
-    }
-    return launch_set_generic(medium, sc, cam, S, fa, fb, stream, lo);
+    const VariantKey key = {sc.active_mats, sc.dist_mask, sc.n_sdfs, fa.filter_kind, sc.has_medium != 0, sc.view != 0, sc.pick_random_light != 0, sc.env_is != 0};
+    const Variant* v = select_variant(key, lo);
+    if (!v) return RenderLaunch{};
 #endif
+#define PT_LAUNCH_VARIANT(file, M, MED, name) if (v->mats == (M) && v->medium == (MED)) return launch_variant<(M), (MED)>(*v, sc, cam, S, fa, fb, stream, lo);
+    PT_VARIANTS(PT_LAUNCH_VARIANT)
+#undef PT_LAUNCH_VARIANT
+    return RenderLaunch{};
 }
 
 unsigned render_tile_count(int width, int rows) {

@@ -20,29 +20,9 @@ struct LaunchOpts {
 // what a launch ran: kernel variant, wave-count build, pixel-to-wave mapping (prt_kernel_variant)
 struct RenderLaunch { const char* name = ""; int waves = 0; int scatter = 0; int ordered = 0; int pool = 0; int pix_per_wave = 64; int adaptive = 0; int list = 0; };   // ordered: the tiles were taken in the launcher's order; adaptive: the PT_MATS_ADAPT build, list: over a live-pixel list
 
-// launches the scene-specialised variant (the AOT analogue of the reference's per-scene program
-// build, include/CL/cl_kernel.h:226-345)
+// launches the row of the variant table the scene and the options select (pt_variant.h select_variant)
 RenderLaunch launch_render(const DevScene& sc, const DevCamera& cam, const DevState& S, const FrameArgs& fa, float4* fb,
                            hipStream_t stream, const LaunchOpts& lo);
-// one per compile-time material set (pt_inst_*.hip; each covers medium off / on)
-#define PT_DECLARE_SET(fn) RenderLaunch fn(bool medium, const DevScene& sc, const DevCamera& cam, const DevState& S, const FrameArgs& fa, float4* fb, \
-                                           hipStream_t stream, const LaunchOpts& lo)
-PT_DECLARE_SET(launch_set_light_diff);
-PT_DECLARE_SET(launch_set_coat);
-PT_DECLARE_SET(launch_set_rough_cond);
-PT_DECLARE_SET(launch_set_rough_diel);
-PT_DECLARE_SET(launch_set_generic);
-PT_DECLARE_SET(launch_set_sdf);
-PT_DECLARE_SET(launch_set_view);
-PT_DECLARE_SET(launch_set_view_sdf);
-PT_DECLARE_SET(launch_set_pick);
-PT_DECLARE_SET(launch_set_envis);
-// the PT_MATS_FILTER builds (prt_set_pixel_filter; pt_inst_filter_*.hip): the same sets with the filter's path start
-PT_DECLARE_SET(launch_set_filter_light_diff);
-PT_DECLARE_SET(launch_set_filter_coat);
-PT_DECLARE_SET(launch_set_filter_rough_cond);
-PT_DECLARE_SET(launch_set_filter_rough_diel);
-PT_DECLARE_SET(launch_set_filter_generic);
 
 // workgroups (tiles) launch_render uses for a width x rows frame part
 unsigned render_tile_count(int width, int rows);

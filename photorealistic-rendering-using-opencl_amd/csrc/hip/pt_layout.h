@@ -171,4 +171,28 @@ struct FrameArgs {
     uint32_t filter_kind;                   // PRT_FILTER_*
 };
 
+// ---- the MATS template argument of render_kernel and of the lane machine (pt_device.h): the compile-time ACTIVE_MATS (PRT_MAT_* bits, 0 = dispatched
+// at run time) plus the bits below.  Which (MATS, MEDIUM) pairs are compiled, and which of them a launch takes: pt_variant.h.
+// PT_MATS_SDF bit marks the variants that carry the raymarched primitives (H_SDF scenes only)
+#define PT_MATS_SDF 0x80000000u
+// PT_MATS_VIEW bit: the debug views VIEW_NORMAL / VIEW_BVH_HIT of kernels/main.cl:6-15,143-152 (prt_config::view_option)
+#define PT_MATS_VIEW 0x40000000u
+// PT_MATS_PICK bit: PICK_RANDOM_LIGHT of kernels/integrators/base.cl:9 (prt_config::pick_random_light)
+#define PT_MATS_PICK 0x20000000u
+// PT_MATS_ENVIS bit: prt_config::env_importance_sampling (not in the reference)
+#define PT_MATS_ENVIS 0x10000000u
+// PT_MATS_DISTS bits (3, at PT_MATS_DIST_SHIFT): the only microfacet distributions the scene's materials use, 0 = any -- the analogue for
+// `mat->dist` (kernels/bxdf/microfacet.cl:6-9, a run-time field) of compiling the scene's ACTIVE_MATS: a GGX scene carries no Beckmann
+// exponential and no Phong power (whose binary64 polynomials alone are 40 - 80 B of scratch per lane)
+#define PT_MATS_DIST_SHIFT 24
+#define PT_MATS_DISTS (7u << PT_MATS_DIST_SHIFT)
+// PT_MATS_ADAPT bit: the adaptive-sampling build of a set (prt_render_adaptive): the freeze rule of lane_frozen, the {l, s2} plane updated at
+// every path end, and the live-pixel list mapping of render_kernel.  A bit of MATS rather than a template parameter of its own: the
+// pre-existing instances keep their names and their code
+#define PT_MATS_ADAPT 0x08000000u
+// PT_MATS_FILTER bit: the pixel-filter build of a set (prt_set_pixel_filter, pt_filter.h): a path starts through its filter offset
+// (create_cam_ray_at) instead of the pixel centre.  A bit of MATS for the reason PT_MATS_ADAPT is one
+#define PT_MATS_FILTER 0x00800000u
+#define PT_MATS_FLAGS (PT_MATS_SDF | PT_MATS_VIEW | PT_MATS_PICK | PT_MATS_ENVIS | PT_MATS_DISTS | PT_MATS_ADAPT | PT_MATS_FILTER)
+
 }  // namespace prt

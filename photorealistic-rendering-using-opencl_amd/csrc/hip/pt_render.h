@@ -1,7 +1,7 @@
 // pt_render.h -- render_kernel (the hot kernel of libprt) and its launcher templates.  Included by the instance files
-// pt_inst_*.hip, one per compile-time material set, so that the sets compile in parallel (build.py) -- the AOT analogue of the
-// reference's per-scene program build (include/CL/cl_kernel.h:226-345 compiles exactly the scene's ACTIVE_MATS).  See pt_device.h
-// for the arithmetic contract and the lane machine.
+// pt_inst_*.hip, each of which instantiates launch_variant for its group of rows of the variant table (pt_variant.h: which builds exist
+// and which one a launch takes), so that the sets compile in parallel (build.py).  See pt_device.h for the arithmetic contract and the
+// lane machine.
 //
 // Launch geometry: one wave per workgroup, owning an 8x8 pixel tile (primary rays of one wave walk the same BVH nodes), or 64
 // pixels of 64 tiles in launches with few rounds of waves; dynamic LDS (DevScene::stack_levels x 256 B per workgroup) holds the
@@ -17,6 +17,7 @@
 #include "pt_device.h"
 #include "pt_launch.h"
 #include "pt_pool.h"
+#include "pt_variant.h"
 
 namespace prt {
 
@@ -151,10 +152,11 @@ static void launch_variant_w(const DevScene& sc, const DevCamera& cam, const Dev
     else
         hipLaunchKernelGGL((render_kernel<MATS, MEDIUM, WAVES>), dim3(grid), dim3(PT_BLOCK), lds, stream, sc, cam, S, fb_args, fb);
 }
-// one material set x medium: picks the wave-count build and the pixel-to-wave mapping; reports both (RenderLaunch)
+// one row of the variant table (v: the row of <MATS, MEDIUM>): picks the wave-count build and the pixel-to-wave mapping; reports both (RenderLaunch).
+// Not inline: the explicit instantiation declarations below keep every translation unit but the row's instance file from compiling its kernels
 template <unsigned MATS, bool MEDIUM>
-static RenderLaunch launch_variant(const char* name, const DevScene& sc, const DevCamera& cam, const DevState& S, const FrameArgs& fa, float4* fb,
-                                   hipStream_t stream, const LaunchOpts& lo) {
+RenderLaunch launch_variant(const Variant& v, const DevScene& sc, const DevCamera& cam, const DevState& S, const FrameArgs& fa, float4* fb,
+                            hipStream_t stream, const LaunchOpts& lo) {
     bool scatter;
     const unsigned grid = launch_grid(sc, fa, lo, scatter);
     // Waves per SIMD = which register budget the set runs best at.  6 (80 registers) for the light sets, with a medium, for the raymarched
@@ -169,7 +171,7 @@ static RenderLaunch launch_variant(const char* name, const DevScene& sc, const D
     constexpr bool five = !(MATS & PT_MATS_SDF) && ((MATS & ~PT_MATS_FLAGS) == 0u || (!MEDIUM && (MATS & PRT_MAT_COAT) != 0u));
     const int waves = lo.waves ? lo.waves : (sc.n_pairs > 65536u ? PT_BIG_WAVES : ((scatter || five) ? PT_WAVES : PT_BIG_WAVES));
     RenderLaunch r;
-    r.name = name; r.scatter = scatter ? 1 : 0;
+    r.name = v.name; r.scatter = scatter ? 1 : 0;
     if (fa.adapt) {
         // prt_render_adaptive: ONE build per set (the wave count the set's tile launches take), 64 pixels per wave, no ray pool, no tile order;
         // list launches cover ceil(live_count / 64) waves.  (The debug views are refused by the caller: no adaptive build of them.)
@@ -208,5 +210,10 @@ static RenderLaunch launch_variant(const char* name, const DevScene& sc, const D
 #endif
     return r;
 }
+// every row is instantiated in its instance file and nowhere else: pt_inst_<file>.hip is PT_VARIANTS_<FILE>(PT_INSTANTIATE_VARIANT)
+#define PT_VARIANT_ARGS const Variant&, const DevScene&, const DevCamera&, const DevState&, const FrameArgs&, float4*, hipStream_t, const LaunchOpts&
+#define PT_EXTERN_VARIANT(file, M, MED, name) extern template RenderLaunch launch_variant<(M), (MED)>(PT_VARIANT_ARGS);
+#define PT_INSTANTIATE_VARIANT(file, M, MED, name) template RenderLaunch launch_variant<(M), (MED)>(PT_VARIANT_ARGS);
+PT_VARIANTS(PT_EXTERN_VARIANT)
 
 }  // namespace prt

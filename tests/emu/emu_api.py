@@ -15,7 +15,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 def build():
     srcs = [os.path.join(HERE, "pt_emu.cpp"), os.path.join(PKG, "csrc", "hip", "pt_pack.cpp")]
-    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_device.h", "pt_filter.h", "pt_layout.h", "pt_pack.h", "pt_selftest.h")] + \
+    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_device.h", "pt_filter.h", "pt_layout.h", "pt_launch.h", "pt_pack.h", "pt_selftest.h", "pt_variant.h")] + \
         [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
     if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
         return LIB
@@ -39,9 +39,38 @@ def lib():
                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_void_p,
                                     C.c_uint32, C.c_float, C.c_void_p]
+        _lib.emu_select_variant.restype = C.c_int
+        _lib.emu_select_variant.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+        _lib.emu_last_variant.restype = C.c_char_p
+        _lib.emu_variant_row.restype = C.c_int
+        _lib.emu_variant_row.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         _lib.emu_selftest_fn.restype = None
         _lib.emu_selftest_fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     return _lib
+
+
+def select_variant(active_mats, has_medium, n_sdfs, view, pick_random_light, env_is, dist_mask, filter_kind, generic, any_dist):
+    """the row of the variant table (csrc/hip/pt_variant.h) launch_render takes: (MATS, MEDIUM, name), or None if select_variant names no row"""
+    mats, medium, name = C.c_uint32(), C.c_int(), C.c_char_p()
+    i = lib().emu_select_variant(active_mats, has_medium, n_sdfs, view, pick_random_light, env_is, dist_mask, filter_kind, generic, any_dist,
+                                 C.byref(mats), C.byref(medium), C.byref(name))
+    return None if i < 0 else (mats.value, bool(medium.value), name.value.decode())
+
+
+def last_variant():
+    """the name of the row the last render() ran (what prt_kernel_variant reports of a launch, without its wave count and mapping)"""
+    return lib().emu_last_variant().decode()
+
+
+def variant_table():
+    """every row of the variant table: [(MATS, MEDIUM, name, instance file)]"""
+    mats, medium, name, file = C.c_uint32(), C.c_int(), C.c_char_p(), C.c_char_p()
+    rows = []
+    for i in range(lib().emu_variant_row(-1, C.byref(mats), C.byref(medium), C.byref(name), C.byref(file))):
+        lib().emu_variant_row(i, C.byref(mats), C.byref(medium), C.byref(name), C.byref(file))
+        rows.append((mats.value, bool(medium.value), name.value.decode(), file.value.decode()))
+    return rows
 
 
 def selftest_fn(fn, params, cases):

@@ -2,7 +2,9 @@
 //
 // The device functions of the product (csrc/hip/pt_device.h: the lane machine, BVH steps, BSDFs, ...) compiled for the
 // HOST (-DPT_EMU turns __device__ into __host__ __device__; hipcc --cuda-host-only) and driven by a wave emulator that
-// mirrors render_kernel's schedule (pt_kernels.hip) over 64 Lane records.  Two uses, both on the CPU (-m "not gpu"):
+// mirrors render_kernel's schedule (pt_render_body.h) over 64 Lane records.  Which <MATS, MEDIUM> instance of the lane machine a render runs
+// is the launcher's own choice: select_variant over the variant table of csrc/hip/pt_variant.h, the code launch_render calls.  Two uses, both on
+// the CPU (-m "not gpu"):
 //   * the refactored per-lane phases == oracle/pt_oracle.c, bit for bit, without a GPU;
 //   * schedule independence: with `sched_seed` != 0 the length of every walk phase is drawn at random, which must not
 //     change a bit of any pixel (lanes drift in frame number; pixels are independent).
@@ -19,6 +21,7 @@
 #include "pt_device.h"
 #include "pt_pack.h"
 #include "pt_selftest.h"
+#include "pt_variant.h"
 
 using namespace prt;
 using namespace prt::dev;
@@ -152,12 +155,22 @@ void run_tile(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, int
     }
 }
 
+// the launcher-level choices the emulator has: PT_EMU_GENERIC=1 / PT_EMU_ANY_DIST=1 (prt_set_option "generic" / "any_dist")
+const char* g_last_variant = "";           // the row emu_render ran last (emu_last_variant)
+
+LaunchOpts env_launch_opts() {
+    const auto on = [](const char* name) { const char* e = std::getenv(name); return (e && e[0] == '1') ? 1 : 0; };
+    LaunchOpts lo;
+    lo.generic = on("PT_EMU_GENERIC"); lo.any_dist = on("PT_EMU_ANY_DIST");
+    return lo;
+}
+
 }  // namespace
 
 // same arguments as oracle/pt_oracle.h's pto_job, plus the schedule.  Returns 0, or the prt error code of pack_scene.
 // filter_kind / filter_r / filter_tab: prt_set_pixel_filter's state as prt_api.cpp puts it into FrameArgs (tab: T[0 .. 256] of the Gaussian and
-// Blackman-Harris kinds, else null).  A kind other than PRT_FILTER_NONE runs the PT_MATS_FILTER builds launch_render picks
-// (pt_inst_filter_*.hip), and is refused (PRT_ERR_UNSUPPORTED) for the configs prt_set_pixel_filter refuses.
+// Blackman-Harris kinds, else null).  A kind other than PRT_FILTER_NONE runs the PT_MATS_FILTER rows, and is refused (PRT_ERR_UNSUPPORTED) for
+// the configs prt_set_pixel_filter refuses (filter_unsupported).  PT_EMU_GENERIC=1 / PT_EMU_ANY_DIST=1: LaunchOpts::generic / any_dist.
 extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, const prt_camera* camera, const float* env_rgb, int env_w, int env_h,
                           int width, int full_height, int row0, int rows, int block_rows, int n_parts, int part,
                           uint32_t first_frame, uint32_t n_frames, const int32_t* seed_pairs, prt_path_state* state, float* out_rgba,
@@ -192,8 +205,7 @@ extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, con
     fa.walk_min_lanes = walk_min_lanes ? walk_min_lanes : 8;
     fa.tri_sixteenths = 4;
     fa.filter_kind = filter_kind; fa.filter_r = filter_r; fa.filter_tab = filter_tab;
-    const bool filtered = filter_kind != PRT_FILTER_NONE;
-    if (filtered) {
+    if (filter_kind != PRT_FILTER_NONE) {
         const char* why = nullptr;
         if (filter_kind > PRT_FILTER_BLACKMAN_HARRIS || !(filter_r >= 0.0f && filter_r <= 4.0f)) why = "pixel filter: unknown kind or radius outside [0, 4]";
         else if ((filter_kind == PRT_FILTER_GAUSSIAN || filter_kind == PRT_FILTER_BLACKMAN_HARRIS) && !filter_tab) why = "pixel filter: the kind needs its table";
@@ -201,74 +213,46 @@ extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, con
             if (err && err_len > 0) { std::strncpy(err, why, (size_t)err_len - 1); err[err_len - 1] = 0; }
             return PRT_ERR_INVALID_ARGUMENT;
         }
-        // no filter instances of these sets (prt.h prt_set_pixel_filter)
-        if (sc.env_is || sc.pick_random_light || sc.view || sc.n_sdfs) {
-            if (err && err_len > 0) { std::strncpy(err, "pixel filter: refused with a debug view, SDF primitives, the light pick or environment sampling", (size_t)err_len - 1); err[err_len - 1] = 0; }
+        if (const char* no = filter_unsupported(*cfg)) {
+            const std::string msg = std::string("pixel filter: no filter instances are built for ") + no;
+            if (err && err_len > 0) { std::strncpy(err, msg.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
             return PRT_ERR_UNSUPPORTED;
         }
     }
-    constexpr unsigned LD = PRT_MAT_LIGHT | PRT_MAT_DIFF;
-    const char* e_generic = std::getenv("PT_EMU_GENERIC");
-    const bool generic = e_generic && e_generic[0] == '1';
+    const VariantKey key = {sc.active_mats, sc.dist_mask, sc.n_sdfs, filter_kind, sc.has_medium != 0, sc.view != 0, sc.pick_random_light != 0, sc.env_is != 0};
+    const Variant* v = select_variant(key, env_launch_opts());
+    g_last_variant = v ? v->name : "";
+    decltype(&run_tile<0u, false>) run = nullptr;
+#define PT_EMU_VARIANT(file, M, MED, name) if (v && v->mats == (M) && v->medium == (MED)) run = &run_tile<(M), (MED)>;
+    PT_VARIANTS(PT_EMU_VARIANT)
+#undef PT_EMU_VARIANT
+    if (!run) {
+        if (err && err_len > 0) { std::strncpy(err, "no row of the variant table for this scene", (size_t)err_len - 1); err[err_len - 1] = 0; }
+        return PRT_ERR_UNSUPPORTED;
+    }
     std::vector<unsigned> stack_mem;
     const int tiles_x = (width + 7) / 8, tiles_y = (rows + 7) / 8;
     for (int ty = 0; ty < tiles_y; ++ty)
-        for (int tx = 0; tx < tiles_x; ++tx) {
-            // the variant launch_render (pt_kernels.hip) picks
-            if (filtered) {
-                // the PT_MATS_FILTER builds (pt_inst_filter_*.hip): the compiled sets with the distribution bits their files give them (any
-                // other scene of a set, and every set with a medium but LIGHT|DIFF, takes the filtered generic dispatch)
-                constexpr unsigned F = PT_MATS_FILTER;
-                constexpr unsigned CO = LD | PRT_MAT_COAT | F | ((unsigned)PRT_DIST_BECKMANN << PT_MATS_DIST_SHIFT);
-                constexpr unsigned RC = LD | PRT_MAT_ROUGH_COND | F | ((unsigned)PRT_DIST_GGX << PT_MATS_DIST_SHIFT);
-                constexpr unsigned RD = LD | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL | F | ((unsigned)PRT_DIST_GGX << PT_MATS_DIST_SHIFT);
-                const unsigned am = generic ? 0u : sc.active_mats;
-                const bool med = sc.has_medium != 0;
-                if (am == LD) {
-                    if (!med) run_tile<LD | F, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                    else run_tile<LD | F, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                } else if (!med && am == (LD | PRT_MAT_COAT) && sc.dist_mask == (unsigned)PRT_DIST_BECKMANN) {
-                    run_tile<CO, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                } else if (!med && am == (LD | PRT_MAT_ROUGH_COND) && sc.dist_mask == (unsigned)PRT_DIST_GGX) {
-                    run_tile<RC, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                } else if (!med && am == (LD | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL) && sc.dist_mask == (unsigned)PRT_DIST_GGX) {
-                    run_tile<RD, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                } else {
-                    if (!med) run_tile<F, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                    else run_tile<F, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                }
-            } else if (sc.env_is) {
-                run_tile<PT_MATS_ENVIS, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-            } else if (sc.pick_random_light) {
-                if (!sc.has_medium) run_tile<PT_MATS_PICK, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else run_tile<PT_MATS_PICK, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-            } else if (sc.view) {
-                constexpr unsigned V = PT_MATS_VIEW, VS = PT_MATS_VIEW | PT_MATS_SDF;
-                if (sc.n_sdfs) {
-                    if (!sc.has_medium) run_tile<VS, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                    else run_tile<VS, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                } else {
-                    if (!sc.has_medium) run_tile<V, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                    else run_tile<V, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                }
-            } else if (sc.n_sdfs) {
-                if (!sc.has_medium) run_tile<PT_MATS_SDF, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else run_tile<PT_MATS_SDF, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-            } else if (!sc.has_medium) {
-                // the compiled material sets of launch_render (pt_kernels.hip); PT_EMU_GENERIC=1: the run-time dispatch instead
-                constexpr unsigned CO = LD | PRT_MAT_COAT, RC = LD | PRT_MAT_ROUGH_COND, RD = LD | PRT_MAT_DIEL | PRT_MAT_ROUGH_DIEL;
-                const unsigned am = generic ? 0u : sc.active_mats;
-                if (am == LD) run_tile<LD, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else if (am == CO) run_tile<CO, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else if (am == RC) run_tile<RC, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else if (am == RD) run_tile<RD, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else run_tile<0u, false>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-            } else {
-                if (!generic && sc.active_mats == LD) run_tile<LD, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-                else run_tile<0u, true>(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
-            }
-        }
+        for (int tx = 0; tx < tiles_x; ++tx) run(sc, cam, fa, tx, ty, state, out_rgba, sched_seed, stack_mem, ahead);
     return 0;
+}
+
+// select_variant (csrc/hip/pt_variant.h) for tests/test_variant_select.py: the index of the row it picks (its MATS, MEDIUM and name out), or -1
+extern "C" int emu_select_variant(uint32_t active_mats, int has_medium, uint32_t n_sdfs, int view, int pick_random_light, int env_is, uint32_t dist_mask,
+                                  uint32_t filter_kind, int generic, int any_dist, uint32_t* mats, int* medium, const char** name) {
+    const VariantKey key = {active_mats, dist_mask, n_sdfs, filter_kind, has_medium != 0, view != 0, pick_random_light != 0, env_is != 0};
+    LaunchOpts lo;
+    lo.generic = generic; lo.any_dist = any_dist;
+    const Variant* v = select_variant(key, lo);
+    if (!v) return -1;
+    *mats = v->mats; *medium = v->medium ? 1 : 0; *name = v->name;
+    return (int)(v - k_variants);
+}
+extern "C" const char* emu_last_variant() { return g_last_variant; }
+// row i of the variant table; returns the number of rows
+extern "C" int emu_variant_row(int i, uint32_t* mats, int* medium, const char** name, const char** file) {
+    if (i >= 0 && i < k_n_variants) { *mats = k_variants[i].mats; *medium = k_variants[i].medium ? 1 : 0; *name = k_variants[i].name; *file = k_variants[i].file; }
+    return k_n_variants;
 }
 
 // prt_selftest_fn on the host: the same dispatcher (csrc/hip/pt_selftest.h) compiled for x86-64

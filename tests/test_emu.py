@@ -46,6 +46,8 @@ def test_device_code_on_host_matches_reference_golden(prt, oracle, emu, variant,
                             walk_min_lanes=sched[0], sched_seed=sched[1])
     gstate = np.ascontiguousarray(g["state"]).view(oracle.PATH_STATE_DTYPE).reshape(-1)
     _same(oracle, gstate, g["image"], state, img, "%s schedule %s" % (variant, sched))
+    if variant in _SET_OF:          # what the product launches for these scenes: the instance of the scene's one microfacet distribution
+        assert emu.last_variant() == "render_kernel<%s; %s>" % _SET_OF[variant]
 
 
 @pytest.mark.parametrize("variant", ["cornell_diffuse", "cornell_coat", "cornell_roughcond", "cornell_roughdiel", "cornell_media"])
@@ -58,6 +60,27 @@ def test_generic_material_dispatch_on_host_matches_reference_golden(prt, oracle,
     state, img = emu.render(oracle.PATH_STATE_DTYPE, cfg, scene.desc, cam, W, H, prt.seed_pairs(frames), env=env, sched_seed=4711)
     gstate = np.ascontiguousarray(g["state"]).view(oracle.PATH_STATE_DTYPE).reshape(-1)
     _same(oracle, gstate, g["image"], state, img, "%s generic set" % variant)
+
+
+@pytest.mark.parametrize("variant", ["cornell_coat", "cornell_roughcond", "cornell_roughdiel"])
+@pytest.mark.parametrize("sched", [(8, 0), (8, 2718)])
+def test_every_distribution_instances_on_host_match_reference_golden(prt, oracle, emu, variant, sched, monkeypatch):
+    """the sets with a microfacet lobe run, by default, the instance compiled for the one distribution of their scene (PT_MATS_DISTS: what
+    test_device_code_on_host_matches_reference_golden covers, the launcher's choice being the emulator's); LaunchOpts::any_dist takes the
+    instance that carries every distribution -- another build of the same arithmetic, the same goldens bit for bit"""
+    g = np.load(os.path.join(GOLDEN, variant + ".npz"))
+    W, H, frames = int(g["width"]), int(g["height"]), int(g["frames"])
+    scene, cfg, cam, env = _scene(prt, variant, W, H)
+    monkeypatch.setenv("PT_EMU_ANY_DIST", "1")
+    state, img = emu.render(oracle.PATH_STATE_DTYPE, cfg, scene.desc, cam, W, H, prt.seed_pairs(frames), env=env,
+                            walk_min_lanes=sched[0], sched_seed=sched[1])
+    gstate = np.ascontiguousarray(g["state"]).view(oracle.PATH_STATE_DTYPE).reshape(-1)
+    _same(oracle, gstate, g["image"], state, img, "%s any_dist schedule %s" % (variant, sched))
+    assert emu.last_variant() == "render_kernel<%s>" % _SET_OF[variant][0]
+
+
+_SET_OF = {"cornell_coat": ("LIGHT|DIFF|COAT", "Beckmann"), "cornell_roughcond": ("LIGHT|DIFF|ROUGH_COND", "GGX"),
+           "cornell_roughdiel": ("LIGHT|DIFF|DIEL|ROUGH_DIEL", "GGX")}
 
 
 @pytest.mark.parametrize("fixture", list(VIEW_VARIANTS))

@@ -1,12 +1,12 @@
 #!/bin/bash
-# development helper: registers / scratch / occupancy of every render_kernel instance of the product build
+# development helper: registers (SGPRs, VGPRs) / scratch / occupancy / LDS of every render_kernel instance of the product build
 #   tools/kernel_resources.sh [inst names...]     (default: all pt_inst_*.hip)
 H="$(cd "$(dirname "$0")/.." && pwd)/photorealistic-rendering-using-opencl_amd/csrc/hip"
 names="$@"; [ -z "$names" ] && names=$(cd $H && ls pt_inst_*.hip | sed 's/pt_inst_//; s/.hip//')
 for n in $names; do
   ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -c --cuda-device-only \
     -I$H/../../../include -I$H -Rpass-analysis=kernel-resource-usage -o /dev/null $H/pt_inst_$n.hip 2>&1 \
-    | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy" | sed 's/.*remark: *//' | paste - - - - \
+    | grep -E "Function Name|TotalSGPRs:|VGPRs:|ScratchSize|Occupancy|LDS Size" | sed 's/.*remark: *//' | paste - - - - - - \
     | sed 's/\[-Rpass-analysis=kernel-resource-usage\]//g; s/Function Name: //' | while read l; do echo "$n: $(echo $l | sed 's/_ZN3prt13render_kernel//')"; done ) &
 done
 wait
