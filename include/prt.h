@@ -333,6 +333,42 @@ int prt_denoise_temporal(prt_ctx* ctx, const prt_denoise_params* spatial, const 
 int prt_read_history(prt_ctx* ctx, float* out8);
 int prt_reset_history(prt_ctx* ctx);
 
+/* Denoising a frame that was rendered in parts (tiles, row blocks, several devices): every part exports what the filter reads as records,
+ * the caller puts the records of the whole frame together (parallel.py: one gather to rank 0) and the filter runs on them.  Moving records
+ * is lossless, renders and guides are the same bits for every split of the frame and the filter is deterministic: the result is
+ * prt_denoise's of a whole-frame context, bit for bit.
+ * One record = PRT_DENOISE_RECORD_FLOATS floats (64 bytes) per pixel, framebuffer order:
+ *   { c.r, c.g, c.b, alpha,   a.r, a.g, a.b, cov,   n.x, n.y, n.z, z,   v, has_stats, 0, 0 }
+ * floats 0-3 the words of prt_read_framebuffer, 4-11 those of prt_read_guides, v the PRT_DENOISE_VAR_STATS variance above (the same f32
+ * operations in the same order, 0 for n < 2) and has_stats = 1.0f when the last render since the reset was prt_render_adaptive; else v = 0 and
+ * has_stats = 0.0f.
+ * prt_export_denoise_inputs writes the records of the context's frame part (whole frame, tile or row blocks) to device memory of the caller
+ * (width * rows records), ordered on the context's stream like prt_copy_framebuffer_to_device (complete on return unless the stream is a
+ * caller's: prt_set_stream).  It reads the framebuffer, the state, the stats plane and the guides and writes none of them.  Refused as
+ * prt_denoise, except that every frame part is served: PRT_ERR_NOT_READY without valid guides or without a render since the reset,
+ * PRT_ERR_UNSUPPORTED with a debug view, PRT_ERR_INVALID_ARGUMENT for a null pointer or a context without a frame size.
+ * prt_denoise_records runs prt_denoise's filter over a width x height frame given as width * height records in device memory, on the
+ * context's device and stream.  It needs no scene, camera, frame size or render and uses scratch buffers of its own (grown on demand,
+ * freed by prt_destroy): the context's frame, state, guides, stats plane and history are not touched, whatever size or part that frame is.
+ *   Variance: PRT_DENOISE_VAR_SPATIAL the 5x5 moments of the records' colours; PRT_DENOISE_VAR_STATS the records' v (PRT_ERR_NOT_READY
+ *   when any record has has_stats != 1); PRT_DENOISE_VAR_AUTO the records' v when every record has stats, else spatial.
+ *   Output: `device_rgba` (may be NULL) width * height * 4 floats in device memory, `rgba` and `rgba8` (may be NULL) as prt_denoise's, in
+ *   host memory; all complete on return.
+ *   Refused: PRT_ERR_INVALID_ARGUMENT for width < 1, height < 1, null records, or parameters prt_denoise refuses.
+ * prt_denoise_records_temporal is the same with prt_denoise_temporal's step in front.  `cam` is the camera the records were rendered with
+ * (its basis as prt_set_camera derives it).  The record history (96 bytes per pixel, allocated on first use) is the context's second history:
+ * prt_denoise_temporal's is another one, and nothing but prt_reset_records_history and a call with another width or height empties it (the
+ * scene is the caller's here: reset it when the scene or the environment map changes).  A sequence of calls gives the bits of the same sequence
+ * of prt_denoise_temporal on a whole-frame context.  Refused as prt_denoise_records and for parameters prt_denoise_temporal refuses;
+ * PRT_ERR_INVALID_ARGUMENT for a null camera. */
+#define PRT_DENOISE_RECORD_FLOATS 16
+int prt_export_denoise_inputs(prt_ctx* ctx, void* device_records);
+int prt_denoise_records(prt_ctx* ctx, const prt_denoise_params* params, int width, int height, const void* device_records, void* device_rgba,
+                        float* rgba, uint8_t* rgba8);
+int prt_denoise_records_temporal(prt_ctx* ctx, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
+                                 int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8);
+int prt_reset_records_history(prt_ctx* ctx);
+
 /* Pixel reconstruction filter of the primary rays: antialiasing (no counterpart in the reference, whose every path starts through the exact
  * pixel centre; opt-in, the default is that centre ray, bit for bit).  Filter importance sampling (Ernst et al. 2006): path k of pixel (x, y)
  * starts through (x + dx, y + dy), (dx, dy) drawn from a separable non-negative filter F(dx, dy) = f(dx) f(dy), every sample with weight 1 --

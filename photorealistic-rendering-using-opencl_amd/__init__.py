@@ -369,6 +369,59 @@ class Renderer:
     def reset_history(self):
         self._chk(self.lib.prt_reset_history(self.ctx), "prt_reset_history")
 
+    @staticmethod
+    def _device_ptr(t, floats, what):
+        """the device address of `t`: an integer, or a tensor (anything with data_ptr(): it must be contiguous float32 of at least `floats`
+        elements -- the library writes or reads that many without seeing the tensor)"""
+        if not hasattr(t, "data_ptr"):
+            return C.c_void_p(int(t))
+        if not t.is_contiguous() or t.element_size() != 4 or not t.is_floating_point() or t.numel() < floats:
+            raise ValueError("%s: needs a contiguous float32 tensor of at least %d elements" % (what, floats))
+        return C.c_void_p(t.data_ptr())
+
+    def export_denoise_inputs(self, ptr_or_tensor):
+        """prt_export_denoise_inputs: the denoiser's inputs of this context's frame part as records (16 floats per pixel, prt.h) into device
+        memory: a [rows, width, 16] float32 tensor on this device (more rows are left alone) or a device address"""
+        p = self._device_ptr(ptr_or_tensor, self.rows * self.width * _capi.DENOISE_RECORD_FLOATS, "export_denoise_inputs")
+        self._chk(self.lib.prt_export_denoise_inputs(self.ctx, p), "prt_export_denoise_inputs")
+
+    def _records_call(self, name, head, records, width, height, tonemap, out):
+        width, height = int(width), int(height)
+        rec = self._device_ptr(records, width * height * _capi.DENOISE_RECORD_FLOATS, name)
+        fn = getattr(self.lib, name)
+        if out is not None:
+            self._chk(fn(self.ctx, *head, width, height, rec, self._device_ptr(out, width * height * 4, name), None, None), name)
+            return out
+        host = np.zeros((max(height, 0), max(width, 0), 4), dtype=np.uint8 if tonemap else np.float32)   # a size below 1 is the library's to refuse
+        ptr = host.ctypes.data_as(C.c_void_p)
+        self._chk(fn(self.ctx, *head, width, height, rec, None, None if tonemap else ptr, ptr if tonemap else None), name)
+        return host
+
+    def denoise_records(self, records, width, height, passes=DENOISE_DEFAULTS["passes"], var_source="auto", sigma_l=DENOISE_DEFAULTS["sigma_l"],
+                        sigma_n=DENOISE_DEFAULTS["sigma_n"], sigma_z=DENOISE_DEFAULTS["sigma_z"], sigma_a=DENOISE_DEFAULTS["sigma_a"],
+                        tonemap=False, out=None):
+        """prt_denoise_records: denoise()'s filter over a width x height frame given as records in device memory (a [height, width, 16] float32
+        tensor on this device, or a device address): the gathered export_denoise_inputs() of every part of the frame.  The context needs no
+        scene or frame of its own.  Returns what denoise() returns; with `out` (a [height, width, 4] float32 tensor on this device, or a device
+        address) the picture stays on the device: it is written there and `out` is returned"""
+        p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
+        return self._records_call("prt_denoise_records", (C.byref(p),), records, width, height, tonemap, out)
+
+    def denoise_records_temporal(self, records, width, height, cam, passes=DENOISE_DEFAULTS["passes"], var_source="auto",
+                                 sigma_l=DENOISE_DEFAULTS["sigma_l"], sigma_n=DENOISE_DEFAULTS["sigma_n"], sigma_z=DENOISE_DEFAULTS["sigma_z"],
+                                 sigma_a=DENOISE_DEFAULTS["sigma_a"], alpha_color=TEMPORAL_DEFAULTS["alpha_color"],
+                                 alpha_moments=TEMPORAL_DEFAULTS["alpha_moments"], tau_z=TEMPORAL_DEFAULTS["tau_z"], cos_n=TEMPORAL_DEFAULTS["cos_n"],
+                                 history_cap=TEMPORAL_DEFAULTS["history_cap"], feedback=TEMPORAL_DEFAULTS["feedback"], tonemap=False, out=None):
+        """prt_denoise_records_temporal: denoise_records() with denoise_temporal()'s step in front.  `cam`: the camera the records were rendered
+        with.  The record history is this context's second one (reset_records_history(); a call with another size empties it too)"""
+        p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
+        t = TemporalParams(float(alpha_color), float(alpha_moments), float(tau_z), float(cos_n), int(history_cap), self._FEEDBACK[feedback])
+        return self._records_call("prt_denoise_records_temporal", (C.byref(p), C.byref(t), C.byref(cam) if cam is not None else None),
+                                  records, width, height, tonemap, out)
+
+    def reset_records_history(self):
+        self._chk(self.lib.prt_reset_records_history(self.ctx), "prt_reset_records_history")
+
     def set_pixel_filter(self, kind="tent", radius=None):
         """prt_set_pixel_filter: antialiasing by filter importance sampling (prt.h).  kind: a name of PIXEL_FILTERS ("none", "box", "tent",
         "gaussian", "blackman-harris") or its number; radius None = the kind's default.  Resets the frame and makes the guides stale"""

@@ -78,6 +78,7 @@ class DenoiseParams(C.Structure):
 # prt_denoise_params::var_source and the defaults of a NULL params pointer (include/prt.h)
 PRT_DENOISE_VAR_AUTO, PRT_DENOISE_VAR_STATS, PRT_DENOISE_VAR_SPATIAL = 0, 1, 2
 DENOISE_DEFAULTS = dict(passes=5, sigma_l=3.0, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1)
+DENOISE_RECORD_FLOATS = 16      # PRT_DENOISE_RECORD_FLOATS: one record of prt_export_denoise_inputs / prt_denoise_records
 
 
 class TemporalParams(C.Structure):
@@ -125,6 +126,11 @@ PRT_API = [
     ("prt_denoise_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]),
     ("prt_read_history", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_reset_history", C.c_int, [C.c_void_p]),
+    ("prt_export_denoise_inputs", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_denoise_records", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_denoise_records_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(Camera), C.c_int, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_reset_records_history", C.c_int, [C.c_void_p]),
     ("prt_set_pixel_filter", C.c_int, [C.c_void_p, C.c_uint32, C.c_float]),
     ("prt_pixel_filter_offsets", C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),

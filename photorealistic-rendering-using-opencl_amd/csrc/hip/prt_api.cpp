@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -123,6 +124,18 @@ struct prt_ctx {
     uint32_t filter_kind = PRT_FILTER_NONE;
     float filter_r = 0.0f;
     float* d_filter_tab = nullptr;
+    // prt_denoise_records (pt_records.hip): one block for a frame of rec_cap pixels given as records -- its framebuffer plane, guide planes (2),
+    // the filter's buffers (3), the Gaussian of v and the "a record without stats" word.  Not the context's frame: grown on demand, freed by
+    // prt_destroy alone
+    float4* d_rec = nullptr;
+    size_t rec_cap = 0;
+    // prt_denoise_records_temporal: the record history (laid out as d_hist / d_hist_guides) of a rec_hist_w x rec_hist_h frame, allocated on
+    // first use and with every new size, emptied by prt_reset_records_history, freed by prt_destroy
+    float4* d_rec_hist = nullptr;
+    float4* d_rec_hist_guides = nullptr;
+    int rec_hist_w = 0, rec_hist_h = 0, rec_hist_cur = 0;
+    bool rec_hist_valid = false;
+    DevCamera rec_hist_cam{};
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -251,6 +264,9 @@ extern "C" void prt_destroy(prt_ctx* c) {
     void* p = c->d_seeds; free_dev(p);
     p = c->d_counters; free_dev(p);
     p = c->d_filter_tab; free_dev(p);
+    p = c->d_rec; free_dev(p);
+    p = c->d_rec_hist; free_dev(p);
+    p = c->d_rec_hist_guides; free_dev(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -844,14 +860,33 @@ extern "C" int prt_read_guides(prt_ctx* c, float* out8) {
     return PRT_OK;
 }
 
-// the checks prt_denoise and prt_denoise_temporal share; *spatial: the variance source the call resolves to
-static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* who, bool* spatial) {
+// the parameter checks of every denoise call ...
+static int denoise_param_checks(prt_ctx* c, const prt_denoise_params& p, const char* who) {
     const std::string w(who);
     if (p.passes < 1 || p.passes > 8) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": passes must be 1 .. 8");
     if (!(p.sigma_l > 0.0f) || !(p.sigma_n > 0.0f) || !(p.sigma_z > 0.0f) || !(p.sigma_a > 0.0f))
         return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": every sigma must be > 0 (and not NaN)");
     if (p.var_source > PRT_DENOISE_VAR_SPATIAL) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown var_source");
-    int rc = ready(c, who);
+    return PRT_OK;
+}
+// ... and of the temporal ones
+static int temporal_param_checks(prt_ctx* c, const prt_temporal_params& t, const char* who) {
+    const std::string w(who);
+    if (!(t.alpha_color >= 0.0f && t.alpha_color <= 1.0f) || !(t.alpha_moments >= 0.0f && t.alpha_moments <= 1.0f))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": alpha_color and alpha_moments must be in [0, 1]");
+    if (!(t.tau_z > 0.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": tau_z must be > 0 (and not NaN)");
+    if (!(t.cos_n >= -1.0f && t.cos_n <= 1.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": cos_n must be in [-1, 1]");
+    if (t.history_cap < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": history_cap must be >= 1");
+    if (t.feedback > PRT_TEMPORAL_FEEDBACK_ATROUS) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown feedback");
+    return PRT_OK;
+}
+
+// the checks prt_denoise and prt_denoise_temporal share; *spatial: the variance source the call resolves to
+static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* who, bool* spatial) {
+    const std::string w(who);
+    int rc = denoise_param_checks(c, p, who);
+    if (rc) return rc;
+    rc = ready(c, who);
     if (rc) return rc;
     if (c->row0 != 0 || c->rows != c->full_height || c->n_parts != 1)
         return fail(c, PRT_ERR_UNSUPPORTED, w + ": the filter needs the whole frame (tile and row-block contexts are refused)");
@@ -906,14 +941,10 @@ extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatia
     prt_temporal_params t{PRT_TEMPORAL_DEFAULT_ALPHA_COLOR, PRT_TEMPORAL_DEFAULT_ALPHA_MOMENTS, PRT_TEMPORAL_DEFAULT_TAU_Z, PRT_TEMPORAL_DEFAULT_COS_N,
                           PRT_TEMPORAL_DEFAULT_HISTORY_CAP, PRT_TEMPORAL_FEEDBACK_ATROUS};
     if (temporal) t = *temporal;
-    if (!(t.alpha_color >= 0.0f && t.alpha_color <= 1.0f) || !(t.alpha_moments >= 0.0f && t.alpha_moments <= 1.0f))
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: alpha_color and alpha_moments must be in [0, 1]");
-    if (!(t.tau_z > 0.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: tau_z must be > 0 (and not NaN)");
-    if (!(t.cos_n >= -1.0f && t.cos_n <= 1.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: cos_n must be in [-1, 1]");
-    if (t.history_cap < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: history_cap must be >= 1");
-    if (t.feedback > PRT_TEMPORAL_FEEDBACK_ATROUS) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_temporal: unknown feedback");
+    int rc = temporal_param_checks(c, t, "prt_denoise_temporal");
+    if (rc) return rc;
     bool spatial_var = false;
-    int rc = denoise_checks(c, p, "prt_denoise_temporal", &spatial_var);
+    rc = denoise_checks(c, p, "prt_denoise_temporal", &spatial_var);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
@@ -963,6 +994,151 @@ extern "C" int prt_read_history(prt_ctx* c, float* out8) {
 extern "C" int prt_reset_history(prt_ctx* c) {
     CTX_CHECK(c);
     c->hist_valid = false;
+    return PRT_OK;
+}
+
+// ---- denoiser inputs as records (prt.h prt_export_denoise_inputs, prt_denoise_records; pt_records.hip) ---------------------------------------
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+extern "C" int prt_export_denoise_inputs(prt_ctx* c, void* device_records) {
+    CTX_CHECK(c);
+    if (!device_records || !aligned16(device_records) || !c->have_size)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_export_denoise_inputs: bad arguments (a 16-byte aligned device pointer, a context with a frame size)");
+    if (c->state_undefined) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: an earlier render call failed half-way; prt_reset or prt_write_state first");
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_export_denoise_inputs: a debug view is not a picture to filter");
+    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: nothing rendered since the reset");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool stats = c->stats_valid && c->d_adapt;
+    launch_records_export(c->fb, c->S.q4, stats ? c->d_adapt : nullptr, c->d_guides, c->width, c->rows, static_cast<float4*>(device_records), c->stream);
+    HIPCHK(c, hipGetLastError());
+    // (prt_copy_framebuffer_to_device: on a caller's stream the records are ordered like the caller's other work; the context's own stream is
+    // private: finish before returning)
+    if (c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+// the filtered W x H plane `out` to the caller: device_rgba (device memory), rgba and rgba8 (host, as denoise_output's); any may be NULL
+static int records_output(prt_ctx* c, const float4* out, int W, int H, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    const size_t npix = (size_t)W * (size_t)H;
+    if (device_rgba) HIPCHK(c, hipMemcpyAsync(device_rgba, out, npix * 16, hipMemcpyDeviceToDevice, c->stream));
+    if (rgba8) {
+        FrameArgs fa = frame_args(c, 1, 0, nullptr, 0, false);
+        fa.width = W; fa.full_height = H; fa.row0 = 0; fa.rows = H; fa.block_rows = 1; fa.n_parts = 1; fa.part = 0;
+        unsigned char* d = nullptr;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), npix * 4));
+        launch_tonemap(out, d, fa, c->stream);
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(rgba8, d, npix * 4, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rgba) HIPCHK(c, hipMemcpy(rgba, out, npix * 16, hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+// prt_denoise_records (t, cam null) and prt_denoise_records_temporal
+static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params& p, const prt_temporal_params* t, const prt_camera* cam, int W,
+                           int H, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    const std::string w(who);
+    if (W < 1 || H < 1 || !device_records || !aligned16(device_records) || (device_rgba && !aligned16(device_rgba)))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": needs width >= 1, height >= 1 and 16-byte aligned device pointers (records not null)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)W * (size_t)H;
+    if (c->rec_cap < npix) {
+        void* q = c->d_rec; free_dev(q); c->d_rec = nullptr; c->rec_cap = 0;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_rec), npix * (6 * sizeof(float4) + sizeof(float)) + sizeof(unsigned)));
+        c->rec_cap = npix;
+    }
+    float4* fb = c->d_rec;
+    float4* guides = fb + npix;
+    float4* buf0 = fb + 3 * npix;
+    float4* buf1 = fb + 4 * npix;
+    float4* out = fb + 5 * npix;
+    float* g = reinterpret_cast<float*>(fb + 6 * npix);
+    unsigned* d_flag = reinterpret_cast<unsigned*>(g + npix);
+    float4* var = t ? buf1 : buf0;                   // (where the variance step of launch_denoise_temporal / launch_denoise leaves {rgb, v})
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), c->stream));
+    launch_records_import(static_cast<const float4*>(device_records), W, H, fb, guides, var, d_flag, c->stream);
+    HIPCHK(c, hipGetLastError());
+    bool spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL;
+    if (!spatial) {
+        unsigned no_stats = 0;
+        HIPCHK(c, hipMemcpyAsync(&no_stats, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (no_stats && p.var_source == PRT_DENOISE_VAR_STATS)
+            return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs stats in every record (rendered by prt_render_adaptive)");
+        spatial = no_stats != 0;
+    }
+    if (spatial) launch_denoise_var(fb, nullptr, nullptr, true, W, H, var, c->stream);       // the 5x5 moments of the gathered colours
+    if (!t) {
+        float4* cur = buf0;
+        float4* nxt = buf1;
+        for (unsigned i = 0; i < p.passes; ++i) {
+            const bool last = i + 1 == p.passes;
+            launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, last ? out : nxt, c->stream);
+            float4* tmp = cur; cur = nxt; nxt = tmp;
+        }
+        HIPCHK(c, hipGetLastError());
+        return records_output(c, out, W, H, device_rgba, rgba, rgba8);
+    }
+    if (!c->d_rec_hist || !c->d_rec_hist_guides || c->rec_hist_w != W || c->rec_hist_h != H) {
+        c->rec_hist_valid = false;
+        void* q = c->d_rec_hist; free_dev(q); c->d_rec_hist = nullptr;
+        q = c->d_rec_hist_guides; free_dev(q); c->d_rec_hist_guides = nullptr;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_rec_hist), npix * 4 * sizeof(float4)));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_rec_hist_guides), npix * 2 * sizeof(float4)));
+        c->rec_hist_w = W; c->rec_hist_h = H;
+    }
+    DevCamera dc;
+    make_dev_camera(*cam, dc);
+    float4* half_prev = c->d_rec_hist + 2 * npix * (size_t)c->rec_hist_cur;
+    float4* half_next = c->d_rec_hist + 2 * npix * (size_t)(c->rec_hist_cur ^ 1);
+    TemporalHistory h;
+    h.cn_prev = half_prev; h.m_prev = half_prev + npix; h.guides_prev = c->d_rec_hist_guides; h.cam_prev = c->rec_hist_cam; h.valid = c->rec_hist_valid;
+    h.cn = half_next; h.m = half_next + npix;
+    c->rec_hist_valid = false;                     // (until the call has run: a failure leaves the history empty)
+    launch_denoise_temporal_var(fb, guides, W, H, p, *t, dc, h, buf0, buf1, g, out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->d_rec_hist_guides, guides, npix * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->rec_hist_cur ^= 1;
+    c->rec_hist_cam = dc;
+    c->rec_hist_valid = true;
+    return records_output(c, out, W, H, device_rgba, rgba, rgba8);
+}
+
+extern "C" int prt_denoise_records(prt_ctx* c, const prt_denoise_params* params, int width, int height, const void* device_records,
+                                   void* device_rgba, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
+                         PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
+    if (params) p = *params;
+    int rc = denoise_param_checks(c, p, "prt_denoise_records");
+    if (rc) return rc;
+    return denoise_records(c, "prt_denoise_records", p, nullptr, nullptr, width, height, device_records, device_rgba, rgba, rgba8);
+}
+
+extern "C" int prt_denoise_records_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
+                                            int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
+                         PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
+    if (spatial) p = *spatial;
+    prt_temporal_params t{PRT_TEMPORAL_DEFAULT_ALPHA_COLOR, PRT_TEMPORAL_DEFAULT_ALPHA_MOMENTS, PRT_TEMPORAL_DEFAULT_TAU_Z, PRT_TEMPORAL_DEFAULT_COS_N,
+                          PRT_TEMPORAL_DEFAULT_HISTORY_CAP, PRT_TEMPORAL_FEEDBACK_ATROUS};
+    if (temporal) t = *temporal;
+    int rc = temporal_param_checks(c, t, "prt_denoise_records_temporal");
+    if (!rc) rc = denoise_param_checks(c, p, "prt_denoise_records_temporal");
+    if (rc) return rc;
+    if (!cam) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_records_temporal: null camera");
+    return denoise_records(c, "prt_denoise_records_temporal", p, &t, cam, width, height, device_records, device_rgba, rgba, rgba8);
+}
+
+extern "C" int prt_reset_records_history(prt_ctx* c) {
+    CTX_CHECK(c);
+    c->rec_hist_valid = false;
     return PRT_OK;
 }
 

@@ -72,5 +72,15 @@ struct TemporalHistory {
 void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                              const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
                              float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
+// ... everything behind its variance step: buf1 holds the frame's {rgb, v} (dn_var_kernel's output, or a caller's) on entry
+void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, int H, const prt_denoise_params& p, const prt_temporal_params& t,
+                                 const DevCamera& cam, const TemporalHistory& h, float4* buf0, float4* buf1, float* g, float4* out,
+                                 hipStream_t stream);
+// pt_records.hip.  prt_export_denoise_inputs: the records (prt.h: 4 float4 per pixel) of a W x rows frame part; adapt null = no stats
+// (v = 0, has_stats = 0).  prt_denoise_records: W x H records into the planes the filter reads -- fb {c, alpha}, guides (2 float4 per
+// pixel), var {c, v of the record} -- and 1 into *no_stats if any record has has_stats != 1 (the caller zeroes the word first)
+void launch_records_export(const float4* fb, const uint4* q4, const float2* adapt, const float4* guides, int W, int rows, float4* records,
+                           hipStream_t stream);
+void launch_records_import(const float4* records, int W, int H, float4* fb, float4* guides, float4* var, unsigned* no_stats, hipStream_t stream);
 
 }  // namespace prt

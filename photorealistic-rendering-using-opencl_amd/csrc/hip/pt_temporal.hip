@@ -127,8 +127,14 @@ __global__ __launch_bounds__(256) void tm_feedback_kernel(const float4* __restri
 void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                              const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
                              float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
     launch_denoise_var(fb, q4, adapt, spatial, W, H, buf1, stream);
+    launch_denoise_temporal_var(fb, guides, W, H, p, t, cam, h, buf0, buf1, g, out, stream);
+}
+
+void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, int H, const prt_denoise_params& p, const prt_temporal_params& t,
+                                 const DevCamera& cam, const TemporalHistory& h, float4* buf0, float4* buf1, float* g, float4* out,
+                                 hipStream_t stream) {
+    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
     TmParams P;
     P.alpha_color = t.alpha_color; P.alpha_moments = t.alpha_moments; P.tau_z = t.tau_z; P.cos_n = t.cos_n; P.cap = (float)t.history_cap;
     P.has_hist = h.valid ? 1 : 0;

@@ -24,10 +24,10 @@ def max_rows_per_rank(height, world, block=BLOCK_ROWS):
     return max(len(rows_of_rank(height, world, r, block)) for r in range(world))
 
 
-def merge_on_rank0(tile, height, width, world, dist):
-    """tile: (max_rows_per_rank, width, 4) float32 torch tensor, this rank's rows first (padding rows are ignored).
-    ONE collective: a gather to rank 0 (every pixel crosses a link once).  Returns the full (height, width, 4) tensor on rank 0,
-    None on the other ranks."""
+def gather_rows_on_rank0(tile, height, width, world, dist, block=BLOCK_ROWS):
+    """tile: (max_rows_per_rank, width, ...) torch tensor of any trailing shape and dtype, this rank's rows first (padding rows are ignored).
+    ONE collective: a gather to rank 0 (every pixel crosses a link once; the rows themselves travel: every bit pattern survives).  Returns
+    the full (height, width, ...) tensor on rank 0, None on the other ranks; with one rank the tile's rows."""
     import torch
     if world == 1 or dist is None or not dist.is_initialized():
         return tile[:height]
@@ -36,9 +36,46 @@ def merge_on_rank0(tile, height, width, world, dist):
     dist.gather(tile.contiguous(), gather_list=pieces, dst=0)
     if rank != 0:
         return None
-    full = torch.empty((height, width, 4), dtype=torch.float32, device=tile.device)
+    full = torch.empty((height, width) + tuple(tile.shape[2:]), dtype=tile.dtype, device=tile.device)
     for r in range(world):
-        rows = rows_of_rank(height, world, r)
+        rows = rows_of_rank(height, world, r, block)
         idx = torch.as_tensor(np.asarray(rows), dtype=torch.long, device=tile.device)
         full.index_copy_(0, idx, pieces[r][:len(rows)])
     return full
+
+
+def merge_on_rank0(tile, height, width, world, dist):
+    """tile: (max_rows_per_rank, width, 4) float32 torch tensor, this rank's rows first (padding rows are ignored).
+    ONE collective: a gather to rank 0 (every pixel crosses a link once).  Returns the full (height, width, 4) tensor on rank 0,
+    None on the other ranks."""
+    return gather_rows_on_rank0(tile, height, width, world, dist)
+
+
+def denoise_on_rank0(renderer, height, width, world, dist, cam=None, temporal=False, **params):
+    """The denoised frame of a render dealt over `world` ranks in row blocks (prt_set_row_blocks(width, height, BLOCK_ROWS, world, rank) on
+    every rank, rendered, guides rendered): every rank exports its records (Renderer.export_denoise_inputs) into a
+    (max_rows_per_rank, width, 16) tensor, ONE collective gathers them to rank 0 -- instead of the framebuffer's gather, not on top of it -- and
+    rank 0's context filters the whole frame (Renderer.denoise_records, or with temporal=True denoise_records_temporal with `cam`, the frame's
+    camera).  params: the keywords of Renderer.denoise / denoise_temporal.  Returns the (height, width, 4) float32 tensor on rank 0's device,
+    None on the other ranks.  The bits are those of prt_denoise on one whole-frame context."""
+    import torch
+    if temporal and cam is None:
+        raise ValueError("denoise_on_rank0: temporal=True needs the frame's camera")
+    rank = dist.get_rank() if (world > 1 and dist is not None and dist.is_initialized()) else 0
+    device = torch.device("cuda", torch.cuda.current_device())
+    tile = torch.zeros((max_rows_per_rank(height, world), width, 16), dtype=torch.float32, device=device)
+    assert renderer.rows == len(rows_of_rank(height, world, rank)) and renderer.width == width, "the renderer's frame part is not this rank's"
+    # torch's work runs on torch's current stream, the library's on the context's (its own unless Renderer.set_stream made them one): each
+    # side starts behind the other's finished work
+    torch.cuda.current_stream().synchronize()
+    renderer.export_denoise_inputs(tile)
+    renderer.synchronize()
+    records = gather_rows_on_rank0(tile, height, width, world, dist)
+    if rank != 0:
+        return None
+    records = records.contiguous()
+    torch.cuda.current_stream().synchronize()
+    out = torch.empty((height, width, 4), dtype=torch.float32, device=device)
+    if temporal:
+        return renderer.denoise_records_temporal(records, width, height, cam, out=out, **params)
+    return renderer.denoise_records(records, width, height, out=out, **params)
