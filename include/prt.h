@@ -360,7 +360,10 @@ int prt_reset_history(prt_ctx* ctx);
  * prt_denoise_temporal's is another one, and nothing but prt_reset_records_history and a call with another width or height empties it (the
  * scene is the caller's here: reset it when the scene or the environment map changes).  A sequence of calls gives the bits of the same sequence
  * of prt_denoise_temporal on a whole-frame context.  Refused as prt_denoise_records and for parameters prt_denoise_temporal refuses;
- * PRT_ERR_INVALID_ARGUMENT for a null camera. */
+ * PRT_ERR_INVALID_ARGUMENT for a null camera.
+ * prt_read_records_history is prt_read_history's twin for the record history: after a synchronise, per pixel 8 floats {c.rgb, n, m1, m2, v, 0},
+ * framebuffer order, of the width x height frame of the last prt_denoise_records_temporal call.  It writes nothing of the context.
+ * PRT_ERR_NOT_READY while the record history is empty; PRT_ERR_INVALID_ARGUMENT for a null pointer or a size other than the history's. */
 #define PRT_DENOISE_RECORD_FLOATS 16
 int prt_export_denoise_inputs(prt_ctx* ctx, void* device_records);
 int prt_denoise_records(prt_ctx* ctx, const prt_denoise_params* params, int width, int height, const void* device_records, void* device_rgba,
@@ -368,6 +371,7 @@ int prt_denoise_records(prt_ctx* ctx, const prt_denoise_params* params, int widt
 int prt_denoise_records_temporal(prt_ctx* ctx, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
                                  int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8);
 int prt_reset_records_history(prt_ctx* ctx);
+int prt_read_records_history(prt_ctx* ctx, int width, int height, float* out8);
 
 /* Pixel reconstruction filter of the primary rays: antialiasing (no counterpart in the reference, whose every path starts through the exact
  * pixel centre; opt-in, the default is that centre ray, bit for bit).  Filter importance sampling (Ernst et al. 2006): path k of pixel (x, y)

@@ -422,6 +422,14 @@ class Renderer:
     def reset_records_history(self):
         self._chk(self.lib.prt_reset_records_history(self.ctx), "prt_reset_records_history")
 
+    def read_records_history(self, width, height):
+        """the record history of denoise_records_temporal()'s width x height frame: float32 [height, width, 8] = {c.rgb, n, m1, m2, v, 0} per
+        pixel, framebuffer order (read_history()'s twin)"""
+        width, height = int(width), int(height)
+        out = np.zeros((max(height, 0), max(width, 0), 8), dtype=np.float32)      # a size below 1 is the library's to refuse
+        self._chk(self.lib.prt_read_records_history(self.ctx, width, height, out.ctypes.data_as(C.c_void_p)), "prt_read_records_history")
+        return out
+
     def set_pixel_filter(self, kind="tent", radius=None):
         """prt_set_pixel_filter: antialiasing by filter importance sampling (prt.h).  kind: a name of PIXEL_FILTERS ("none", "box", "tent",
         "gaussian", "blackman-harris") or its number; radius None = the kind's default.  Resets the frame and makes the guides stale"""

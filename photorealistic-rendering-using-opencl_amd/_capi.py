@@ -131,6 +131,7 @@ PRT_API = [
     ("prt_denoise_records_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(Camera), C.c_int, C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_reset_records_history", C.c_int, [C.c_void_p]),
+    ("prt_read_records_history", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("prt_set_pixel_filter", C.c_int, [C.c_void_p, C.c_uint32, C.c_float]),
     ("prt_pixel_filter_offsets", C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),

@@ -1142,6 +1142,26 @@ extern "C" int prt_reset_records_history(prt_ctx* c) {
     return PRT_OK;
 }
 
+extern "C" int prt_read_records_history(prt_ctx* c, int width, int height, float* out8) {
+    CTX_CHECK(c);
+    if (!out8 || width < 1 || height < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: bad arguments");
+    if (!c->rec_hist_valid || !c->d_rec_hist)
+        return fail(c, PRT_ERR_NOT_READY, "prt_read_records_history: the record history is empty (prt_denoise_records_temporal)");
+    if (width != c->rec_hist_w || height != c->rec_hist_h)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: the record history has another size");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float4> h(2 * npix);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_rec_hist + 2 * npix * (size_t)c->rec_hist_cur, 2 * npix * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < npix; ++k) {
+        const float4 a = h[k], b = h[npix + k];
+        float* o = out8 + 8 * k;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    }
+    return PRT_OK;
+}
+
 // ---- the pixel filter (prt.h prt_set_pixel_filter) ------------------------------------------------------------------------------------------
 static const char* const k_filter_names[] = {"none", "box", "tent", "gaussian", "blackman-harris"};
 

@@ -274,6 +274,7 @@ def test_temporal_split_equals_whole(prt, feedback, adaptive):
         want = rw.denoise_temporal(**kw)
         got = rc.denoise_records_temporal(records, W, H, cam, **kw)
         assert (_bits(got) == _bits(want)).all(), k
+        assert (_bits(rc.read_records_history(W, H)) == _bits(rw.read_history())).all(), k
     # an emptied history: the next frame is a fresh context's
     cam, records = frame(F)
     first = fresh.denoise_records_temporal(records, W, H, cam, **kw)

@@ -138,7 +138,8 @@ def temporal_ref(fb, g, g_prev, hist_prev, cam, cam_prev, v_frame, alpha_color=0
     """prt.h's reprojection and accumulation in float64.  fb [H, W, 4], g / g_prev [H, W, 8] (guides now / at the previous call),
     hist_prev [H, W, 8] (None: empty history), v_frame [H, W] (prt_denoise's v of this frame).  Returns a dict of c_i [H, W, 3], n, m1,
     m2, v, hist (had history), margin (every decision of the pixel is clear of its threshold) and the per-pixel scales of the inputs
-    blended (for relative comparisons)."""
+    blended (for relative comparisons).  For test_temporal_records.py, which checks the n >= 4 switch itself: margin_other (margin without
+    the n = 4 term), near4 (|n - 4| <= 1e-3) and sw (the sum of the valid taps' weights)."""
     old = np.seterr(all="ignore")
     H, W = fb.shape[:2]
     c = fb[..., :3].astype(np.float64)
@@ -192,10 +193,13 @@ def temporal_ref(fb, g, g_prev, hist_prev, cam, cam_prev, v_frame, alpha_color=0
     ci = np.where(hist[..., None], ch + ac[..., None] * (c - ch), c)
     m1 = np.where(hist, m1h + am * (L - m1h), L)
     m2 = np.where(hist, m2h + am * (L * L - m2h), L * L)
-    margin &= np.abs(n - 4) > 1e-3
+    margin_other = margin.copy()
+    near4 = np.abs(n - 4) <= 1e-3
+    margin &= ~near4
     v = np.where(n >= 4, np.maximum(m2 - m1 * m1, 0.0), v_frame)
     np.seterr(**old)
-    return dict(ci=ci, n=n, m1=m1, m2=m2, v=v, hist=hist, margin=margin, cscale=cmax, m1scale=m1max, m2scale=m2max)
+    return dict(ci=ci, n=n, m1=m1, m2=m2, v=v, hist=hist, margin=margin, cscale=cmax, m1scale=m1max, m2scale=m2max,
+                margin_other=margin_other, near4=near4, sw=sw)
 
 
 def _close(got, ref, scale, rel=1e-4):
