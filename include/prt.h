@@ -495,7 +495,11 @@ int prt_query_counts(prt_ctx* ctx, uint32_t spp, prt_stats* stats);
 /* Diagnostics: evaluates one function of include/prt_detmath.h ON THE DEVICE for n inputs
  * (fn: 0 sin, 1 cos, 2 tan, 3 exp, 4 log, 5 acos, 6 atan2(a,b), 7 pow(a,b), 8 sqrt, 9 a/b,
  * 10 fma(a,b,a), 11 fmin(a,b), 12 fmax(a,b), 13 round, 14 floor, 15 1/a, 16 cbrt).  Host arrays in and out.
- * The numerics contract says the result must equal the host evaluation bit for bit. */
+ * The numerics contract says the result must equal the host evaluation bit for bit.
+ * fn 17 - 19: the exhaustive checks of the kernels' exact fast paths (1/x, the quad's range test, sqrt; out = mismatches per lane).
+ * fn 20 / 21: sin / cos of a through the kernels' one-evaluation pair helper; fn 22 / 23: the kernels' 1/a and sqrt(a) on the
+ * caller's values (a wave = 64 consecutive inputs takes the IEEE expression as soon as one of them is outside the fast range);
+ * fn 24: the quad's range test of x = a against the divisor c = b, 1.0 = outside [0, 1], with u = c * 2^-24 for 2^-40 <= c <= 2^40, NaN otherwise. */
 int prt_selftest_math(prt_ctx* ctx, int fn, const float* a, const float* b, float* out, int n);
 /* test hook: one device FUNCTION of the radiance loop on `n` cases (BSDF sampling / evaluation, microfacet terms,
  * Fresnel, light sampling, medium and phase sampling, camera ray, primitive tests, environment lookup -- fn 1..11, layouts in

@@ -38,9 +38,22 @@ namespace dev {
 #endif
 #define PT_HD __host__ __device__ __forceinline__      // the few helpers the host shares (camera basis)
 
+// The exact fast paths below (hw_recip, hw_sqrt, out_of_unit_range) each have a range in which a short expression equals the IEEE one bit
+// for bit, and the IEEE expression for the rest.  On the device the choice is made per WAVE: the fast expression only when no active
+// lane is outside its range, the IEEE one for every lane otherwise (on its range the fast expression IS the IEEE result, so a lane
+// inside it loses nothing but time).  A lane-wise choice compiles to a two-sided exec-masked region -- saveexec, xor, an exec branch, the
+// expansion, andn2 saveexec, the fast path, or exec: 5 scalar instructions and 1 - 2 branches per execution for a side that only
+// zeros, subnormals, infinities and NaNs take -- the vote to one compare and one scalar branch over a block that nothing masks.  A vote
+// has no memory effect: the uniform loads stay scalar loads (tests/test_codegen.py).  Host and emulator builds choose per value.
+#if defined(__HIP_DEVICE_COMPILE__)
+// (a macro: the hint has to stand in the branch condition itself to survive until the branch is laid out; with it the compiler neither
+// evaluates the IEEE expression ahead of the branch nor puts it in the way of the fast one)
+#define PT_WAVE_ANY(p) __builtin_expect(__builtin_amdgcn_ballot_w64(p) != 0ull, 0)
+#endif
+
 // 1/x, correctly rounded (= prt_recip, the IEEE divide the CPU side does), in 6 vector instructions instead of the
 // 11 of the compiler's divide expansion: hardware estimate + one fma Newton step is exact whenever neither x nor
-// 1/x is subnormal (checked over all 2^32 inputs by prt_selftest_math fn 17, tests/test_gpu_parity.py); the rest
+// 1/x is subnormal (checked over all 2^32 inputs by prt_selftest_math fn 17, tests/test_gpu_parity.py); a wave with a lane of the rest
 // (zero, subnormal, huge, inf, nan) takes the divide.
 #ifndef PT_RECIP_STEPS
 #define PT_RECIP_STEPS 1
@@ -48,28 +61,29 @@ namespace dev {
 PT_HD float hw_recip(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const unsigned e = (prt_f2u(x) >> 23) & 0xffu;
-    if (e - 2u < 251u) {                                        // 2^-125 <= |x| < 2^126
-        float r = __builtin_amdgcn_rcpf(x);
-        for (int k = 0; k < PT_RECIP_STEPS; ++k) r = __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
-        return r;
-    }
-#endif
+    float r = __builtin_amdgcn_rcpf(x);
+    for (int k = 0; k < PT_RECIP_STEPS; ++k) r = __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
+    if (PT_WAVE_ANY(!(e - 2u < 251u))) r = 1.0f / x;              // a lane outside 2^-125 <= |x| < 2^126
+    return r;
+#else
     return 1.0f / x;
+#endif
 }
 // sqrt(x), correctly rounded (= prt_sqrt, the IEEE square root the CPU side computes), without the 17 vector instructions of the
 // compiler's expansion (scaling for subnormals, two neighbour tests, class fix-up): hardware estimate of 1/sqrt(x), s0 = x * r and one
-// fma correction step s0 + (x - s0 * s0) * r / 2 in the range where none of it needs care (5 instructions + the range test); everything else takes the IEEE one.  Checked over all 2^32 inputs by prt_selftest_math
-// fn 19 (tests/test_gpu_parity.py).
+// fma correction step s0 + (x - s0 * s0) * r / 2 in the range where none of it needs care (5 instructions + the range test); a wave with a
+// lane outside it takes the IEEE one.  Checked over all 2^32 inputs by prt_selftest_math fn 19 (tests/test_gpu_parity.py).
 PT_HD float hw_sqrt(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const unsigned e = (prt_f2u(x) >> 23) & 0x1ffu;              // sign and exponent
-    if (e - 27u < 200u) {                                        // positive, 2^-100 <= x < 2^100
-        const float r = __builtin_amdgcn_rsqf(x);
-        const float s0 = x * r, hh = 0.5f * r;
-        return __builtin_fmaf(__builtin_fmaf(-s0, s0, x), hh, s0);
-    }
-#endif
+    const float r = __builtin_amdgcn_rsqf(x);
+    const float s0 = x * r, hh = 0.5f * r;
+    float s = __builtin_fmaf(__builtin_fmaf(-s0, s0, x), hh, s0);
+    if (PT_WAVE_ANY(!(e - 27u < 200u))) s = __builtin_sqrtf(x);     // a lane that is not positive in 2^-100 <= x < 2^100
+    return s;
+#else
     return __builtin_sqrtf(x);
+#endif
 }
 struct f3 { float x, y, z; };
 PT_HD f3 F3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
@@ -197,17 +211,37 @@ PT_DEV Mat load_mat(const DevMaterial* m) {
 
 PT_DEV unsigned mat_bits(const DevMaterial* m) { return const_u32(reinterpret_cast<const uint32_t*>(m), 7u); }   // DevMaterial::bits
 
+// sin(x) and cos(x) of one argument from ONE evaluation of prt_sincos_kernel: the reduction and both polynomials are the same in prt_sin and
+// prt_cos (include/prt_detmath.h), only the quadrant selects differ, and a caller that takes both used to evaluate them twice (about 30
+// vector instructions).  Same operations, same order, same bits as prt_sin(x) / prt_cos(x); the `!(|x| < 1e9) -> x - x` exit is a select
+// and such an x never reaches the kernel, whose quadrant `(int)k` is only defined on the supported domain -- it is given 0 instead, another
+// select: no branch at all.  prt_selftest_math fn 20 / 21, tests/test_sincos_pair.py.
+PT_DEV void sincos_pair(float x, float& sin_out, float& cos_out) {
+    const bool unsupported = !(prt_fabs(x) < 1.0e9f);             // inf, NaN, unsupported magnitude -> NaN / 0
+    float s, c; int q;
+    prt_sincos_kernel(unsupported ? 0.0f : x, &s, &c, &q);
+    const float vs = (q & 1) ? c : s, vc = (q & 1) ? s : c;
+    const float sn = (q & 2) ? -vs : vs, cs = ((q + 1) & 2) ? -vc : vc;
+    const float z = x - x;
+    sin_out = unsupported ? z : sn;
+    cos_out = unsupported ? z : cs;
+}
+
 // ---- sampling warps, kernels/utils.cl:92-152 ------------------------------------------------
 PT_DEV f3 uniform_sphere(float xi_x, float xi_y) {
     float phi = xi_x * PT_TWO_PI;
     float z = xi_y * 2.0f - 1.0f;
     float r = hw_sqrt(prt_fmax(1.0f - z * z, 0.0f));
-    return F3(prt_cos(phi) * r, prt_sin(phi) * r, z);
+    float sn, cs;
+    sincos_pair(phi, sn, cs);
+    return F3(cs * r, sn * r, z);
 }
 PT_DEV f3 cosine_hemisphere(float xi_x, float xi_y) {
     float phi = xi_x * PT_TWO_PI;
     float r = hw_sqrt(xi_y);
-    return F3(prt_cos(phi) * r, prt_sin(phi) * r, hw_sqrt(prt_fmax(1.0f - xi_y, 0.0f)));
+    float sn, cs;
+    sincos_pair(phi, sn, cs);
+    return F3(cs * r, sn * r, hw_sqrt(prt_fmax(1.0f - xi_y, 0.0f)));
 }
 PT_DEV bool check_reflection(f3 wi, f3 wo) {                     // utils.cl:50-52
     return prt_fabs(wi.z * wo.z - wi.x * wo.x - wi.y * wo.y - 1.0f) < 1e-3f;
@@ -255,8 +289,10 @@ PT_DEV Ray create_cam_ray(int cx, int cy, int width, int height, const DevCamera
         float random2 = next1D(rng);
         float angle = 2 * PT_PI * random1;
         float distance = cam.apertureRadius * hw_sqrt(random2);
-        float apertureX = prt_cos(angle) * distance;
-        float apertureY = prt_sin(angle) * distance;
+        float sn, cs;
+        sincos_pair(angle, sn, cs);
+        float apertureX = cs * distance;
+        float apertureY = sn * distance;
         aperturePoint = position + (hAxis * apertureX) + (vAxis * apertureY);
     } else {
         aperturePoint = position;
@@ -287,8 +323,10 @@ PT_DEV Ray create_cam_ray_at(int cx, int cy, float dx, float dy, int width, int 
         const float random2 = next1D(rng);
         const float angle = 2 * PT_PI * random1;
         const float distance = cam.apertureRadius * hw_sqrt(random2);
-        const float apertureX = prt_cos(angle) * distance;
-        const float apertureY = prt_sin(angle) * distance;
+        float sn, cs;
+        sincos_pair(angle, sn, cs);
+        const float apertureX = cs * distance;
+        const float apertureY = sn * distance;
         aperturePoint = position + (hAxis * apertureX) + (vAxis * apertureY);
     } else {
         aperturePoint = position;
@@ -539,11 +577,21 @@ PT_DEV bool hit_sphere(const DevSphere& s, const Ray& ray, float& best_t) {
 //                     the divide, as does a divisor outside [2^-40, 2^40] (u is NaN then).  NaN / inf in x behave as in
 //                     the divide.  Checked against the divide on all 2^32 values of x by prt_selftest_math fn 18.
 PT_DEV bool out_of_unit_range(float x, float c, float u) {
-    if (!(prt_fabs(x) >= 7.888609052210118e-31f) || u != u) {     // |x| < 2^-100 (or NaN), or no valid u: the reference expression
+    const bool divide = !(prt_fabs(x) >= 7.888609052210118e-31f) || u != u;     // |x| < 2^-100 (or NaN), or no valid u: the reference expression
+#if defined(__HIP_DEVICE_COMPILE__)
+    bool out = x < 0.0f || (x - c) > u;
+    if (PT_WAVE_ANY(divide)) {                                      // ... for the whole wave (it is the definition: exact for every lane)
+        const float l = x / c;
+        out = l < 0.0f || l > 1.0f;
+    }
+    return out;
+#else
+    if (divide) {
         const float l = x / c;
         return l < 0.0f || l > 1.0f;
     }
     return x < 0.0f || (x - c) > u;
+#endif
 }
 // The reference's four exits (quad.cl:15, 19, 29) taken as two: a wave skips the code behind an exit only when ALL its lanes
 // leave, so the values behind the first and the third exit are computed by the wave anyway; evaluating them ahead of the
@@ -838,7 +886,9 @@ PT_DEV f3 mf_sample(unsigned dist, float alpha, float xi_x, float xi_y) {
         cosTheta = hw_recip(hw_sqrt(1.0f + tanThetaSq));
     }
     float r = hw_sqrt(prt_fmax(1.0f - cosTheta * cosTheta, 0.0f));
-    return F3(prt_cos(phi) * r, prt_sin(phi) * r, cosTheta);
+    float sn, cs;
+    sincos_pair(phi, sn, cs);
+    return F3(cs * r, sn * r, cosTheta);
 }
 
 // ---- materials ------------------------------------------------------------------------------------------
@@ -1181,7 +1231,9 @@ PT_DEV void phase_sample(const DevScene& sc, f3 wi, PhaseSample& ps, Rng& rng) {
         float cosTheta = u - hw_recip(u);
         float sinTheta = hw_sqrt(prt_fmax(1.0f - cosTheta * cosTheta, 0.0f));
         Frame tf = make_frame(wi);
-        ps.w = to_global(tf, F3(prt_cos(phi) * sinTheta, prt_sin(phi) * sinTheta, cosTheta));
+        float sn, cs;
+        sincos_pair(phi, sn, cs);
+        ps.w = to_global(tf, F3(cs * sinTheta, sn * sinTheta, cosTheta));
         ps.pdf = rayleigh(cosTheta);
     } else if (sc.phase_function == 1 && sc.phase_g != 0.0f) {
         const float g = sc.phase_g;
@@ -1190,7 +1242,9 @@ PT_DEV void phase_sample(const DevScene& sc, f3 wi, PhaseSample& ps, Rng& rng) {
         float cosTheta = (1.0f + g * g - q * q) / (2.0f * g);
         float sinTheta = hw_sqrt(prt_fmax(1.0f - cosTheta * cosTheta, 0.0f));
         Frame tf = make_frame(wi);
-        ps.w = to_global(tf, F3(prt_cos(phi) * sinTheta, prt_sin(phi) * sinTheta, cosTheta));
+        float sn, cs;
+        sincos_pair(phi, sn, cs);
+        ps.w = to_global(tf, F3(cs * sinTheta, sn * sinTheta, cosTheta));
         ps.pdf = hg(g, cosTheta);
     } else {
         ps.w = uniform_sphere(xi_x, xi_y);
@@ -1270,9 +1324,11 @@ PT_DEV EnvSample env_sample(const DevScene& sc, float xi0, float xi1) {
     const float fv = r1 > r0 ? (xi0 - r0) / (r1 - r0) : 0.5f, fu = c1 > c0 ? (xi1 - c0) / (c1 - c0) : 0.5f;
     const float u = ((float)i + fu) / (float)sc.env_w, v = ((float)j + fv) / (float)sc.env_h;
     const float phi = (u - 0.5f) * PT_TWO_PI, theta = v * PT_PI;
-    const float st = prt_sin(theta);
+    float st, ct, sp, cp;
+    sincos_pair(theta, st, ct);
+    sincos_pair(phi, sp, cp);
     EnvSample es;
-    es.d = F3(st * prt_cos(phi), prt_cos(theta), st * prt_sin(phi));                   // the inverse of envMapEquirect
+    es.d = F3(st * cp, ct, st * sp);                                                   // the inverse of envMapEquirect
     es.pdf = env_texel_pdf(sc, i, j, v);
     return es;
 }

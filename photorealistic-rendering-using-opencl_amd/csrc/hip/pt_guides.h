@@ -37,7 +37,9 @@ PT_DEV Ray guide_cam_ray_at(int cx, int cy, int width, int height, const DevCame
     if (cam.apertureRadius > 0.00001f) {
         const float angle = 2 * PT_PI * lx;
         const float distance = cam.apertureRadius * hw_sqrt(ly);
-        aperturePoint = position + (hAxis * (prt_cos(angle) * distance)) + (vAxis * (prt_sin(angle) * distance));
+        float sn, cs;
+        sincos_pair(angle, sn, cs);
+        aperturePoint = position + (hAxis * (cs * distance)) + (vAxis * (sn * distance));
     }
     Ray ray;
     ray.backside = false;

@@ -166,7 +166,8 @@ __global__ void tonemap_kernel(const float4* __restrict__ fb, uchar4* __restrict
     out[id] = make_uchar4(o[0], o[1], o[2], 255);
 }
 
-// the same switch is evaluated on the host by oracle/detmath_probe.c
+// fn 0 - 16: the same switch is evaluated on the host by oracle/detmath_probe.c.  fn 17 - 19 (exhaustive) and 20 - 24 exist on the device only:
+// 20 / 21 are compared with the host's fn 0 / 1, 22 - 24 with numpy's float32 1/x, sqrt(x) and x / c (tests/test_sincos_pair.py, test_uniform_slow_paths.py)
 __global__ void selftest_math_kernel(int fn, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
@@ -221,6 +222,15 @@ __global__ void selftest_math_kernel(int fn, const float* __restrict__ a, const 
         case 13: r = prt_round(x); break;
         case 14: r = prt_floor(x); break;
         case 16: r = prt_cbrt(x); break;
+        case 20: { float sn, cs; sincos_pair(x, sn, cs); r = sn; break; }          // the pair helper of pt_device.h against prt_sin / prt_cos
+        case 21: { float sn, cs; sincos_pair(x, sn, cs); r = cs; break; }
+        case 22: r = hw_recip(x); break;                                                 // the wave-uniform fast paths on the caller's values
+        case 23: r = hw_sqrt(x); break;
+        case 24: {
+            const float u = (y >= 9.094947017729282e-13f && y <= 1099511627776.0f) ? y * 5.9604644775390625e-08f : prt_u2f(0x7fc00000u);
+            r = out_of_unit_range(x, y, u) ? 1.0f : 0.0f;
+            break;
+        }
         default: r = prt_recip(x); break;
     }
     out[i] = r;
