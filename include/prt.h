@@ -136,6 +136,50 @@ void prt_destroy(prt_ctx* ctx);
 /* clw::buffer::create x5 + mBufMaterial, src/main.cpp:401-418,93-122.  Copies and re-packs. */
 int prt_upload_scene(prt_ctx* ctx, const prt_scene_desc* scene);
 
+/* Deforming geometry: new vertices into the uploaded scene, the tree REFITTED on the device (no counterpart in the reference, whose scene is
+ * static: moving a triangle there means rebuilding the tree and creating every buffer again, as prt_upload_scene does here).  The tree's
+ * topology is kept -- which node is whose child, which triangles a leaf holds --; the triangle records and every box are recomputed from the
+ * new vertices, bottom-up.  T, primitive_indices and bvh_nodes are those of the last prt_upload_scene; `vertices` and `normals` have the layout
+ * of prt_scene_desc: float4[3*T], de-indexed, xyz used.  normals == NULL keeps the uploaded normals (they are not read).
+ *   prt_update_vertices          host memory: staged through a device buffer of the context (allocated on first use), then the device path.
+ *   prt_update_vertices_device   device memory of the context's device, 16-byte aligned; ordered on the context's stream, complete on return
+ *                                (the caller's buffers may be reused then).
+ * All operations f32, no contraction.  A "slot" is one triangle reference of a leaf: the leaves' triangles in the order the library stores
+ * them, slot_src[s] = the position in primitive_indices that slot s came from (a leaf's slots are consecutive and in the leaf's order).
+ *   Triangle record of slot s: fv = (uint32)primitive_indices[slot_src[s]] * 3 (kernels/geometry/triangle.cl:7);  p0 = v[fv],
+ *     e1 = p0 - v[fv+1], e2 = v[fv+2] - p0 (triangle.cl:12-13), n = cross(e1, e2) with the component expressions of triangle.cl:15:
+ *     n.x = e1.y*e2.z - e1.z*e2.y, n.y = e1.z*e2.x - e1.x*e2.z, n.z = e1.x*e2.y - e1.y*e2.x.  With normals: the three normals of fv, fv+1, fv+2
+ *     copied, lane 3 = 0.  These are prt_upload_scene's own expressions: the records equal those of an upload of the new vertices.
+ *   Leaf box: per axis lo = hi = the coordinate of vertex 0 of the leaf's first slot; every further vertex follows in slot order, vertices
+ *     0, 1, 2 of each slot:  lo = c < lo ? c : lo;  hi = c > hi ? c : hi  (std::min(lo, c) / std::max(hi, c) as the host builder calls them,
+ *     csrc/host/bvh.cpp).  The comparison form is part of the contract: it fixes the sign of a zero bound (of +0.0 and -0.0 the one that came
+ *     first stays).  A leaf with primitive_count == 0 keeps the box it was uploaded with.
+ *   Inner box: the box of child 0 of the node (first_child_or_primitive), then child 1's box merged per axis by the same two comparisons
+ *     (c = child 1's lo for lo, its hi for hi).  Children before parents.
+ *   Root box: the same union over the root's two children, or the leaf rule when the root is a leaf.
+ *   A caller's tree with loose boxes comes out tight.
+ * The result is deterministic: tile, row-block and multi-rank contexts each call it on their own context and the union of their renders
+ * stays bit-identical to one whole-frame context's; a render after an update equals a render after prt_upload_scene of the same vertices,
+ * normals and the refitted nodes, bit for bit.
+ * Lifetime: an update makes the guides stale and forgets measured tile orders, as prt_set_camera does.  It keeps the path state, the
+ * framebuffer (unchanged until the next render) and both temporal histories.  The loop per displayed frame: update, prt_reset, render,
+ * prt_render_guides, prt_denoise_temporal.  The reprojection's depth and normal tests are what reject surfaces that moved; where they happen
+ * to pass on a moved surface the history GHOSTS (there are no motion vectors of animated geometry) -- prt_reset_history empties it.  Spheres,
+ * quads, SDF primitives and materials are not touched: moving them stays prt_upload_scene's job.  The tables a refit needs (4 bytes per slot
+ * and per inner node) go to the device with the first update: a static scene costs no device memory.
+ * Refused, each leaving the scene exactly as it was: PRT_ERR_NOT_READY without a scene or with T == 0; PRT_ERR_INVALID_ARGUMENT for null
+ * `vertices`, a misaligned device pointer, or any non-finite x, y or z among the 3T vertices (the loaders refuse those too: a NaN box hides
+ * its subtree); PRT_ERR_UNSUPPORTED for a tree whose inner nodes are nested more than 256 deep (the boxes take one launch per level; the
+ * traversal-stack bound of prt_upload_scene counts only nodes with two inner children, so a caller's chain can be deeper: such a tree still
+ * uploads and renders).
+ * prt_read_bvh_bounds: 6 floats per node of the uploaded tree, in ITS node numbering: min_x max_x min_y max_y min_z max_z (the layout of
+ * prt_bvh_node::bounds).  Before any update the uploaded bounds, after one the refitted ones; the root (stored nowhere on the device before
+ * an update) by the rule above, a leaf root before any update as uploaded.  A node that no inner node names as a child reads as six zeros.
+ * PRT_ERR_NOT_READY without a scene. */
+int prt_update_vertices(prt_ctx* ctx, const float* vertices, const float* normals);
+int prt_update_vertices_device(prt_ctx* ctx, const void* d_vertices, const void* d_normals);
+int prt_read_bvh_bounds(prt_ctx* ctx, float* bounds6);
+
 /* enqueueWriteBuffer(cl_camera), src/main.cpp:294-297 (every frame in the reference). */
 int prt_set_camera(prt_ctx* ctx, const prt_camera* cam);
 

@@ -22,7 +22,7 @@ REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["PIXEL_FILTERS", "PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["PIXEL_FILTERS", "PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -197,6 +197,44 @@ def pixel_filter_offsets(kind, radius, gx, gy, k0, n):
     return out
 
 
+def scene_arrays(desc):
+    """numpy views (no copies: `desc`'s owner must stay alive) of a SceneDesc's triangle buffers: vertices and normals float32 [3T, 4],
+    primitive_indices uint64 [T], nodes [bvh_node_count] of _capi.BVH_NODE_DTYPE"""
+    T, N = int(desc.triangle_count), int(desc.bvh_node_count)
+
+    def view(addr, nbytes, dtype):
+        if not addr or not nbytes:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * nbytes).from_address(addr), dtype=dtype)
+    return {"vertices": view(desc.vertices, 48 * T, np.float32).reshape(-1, 4), "normals": view(desc.normals, 48 * T, np.float32).reshape(-1, 4),
+            "primitive_indices": view(desc.primitive_indices, 8 * T, np.uint64), "nodes": view(desc.bvh_nodes, 36 * N, np.dtype(_capi.BVH_NODE_DTYPE))}
+
+
+def bvh_cost(nodes, bounds=None):
+    """SAH cost of a tree in the reference's node layout (a [N] array of _capi.BVH_NODE_DTYPE), with `bounds` ([N, 6]: min_x max_x min_y max_y
+    min_z max_z, e.g. Renderer.read_bvh_bounds() after a refit) in place of the nodes' own: (sum over inner nodes of area + sum over leaves
+    of area x primitive_count) / area of the root, over the nodes the root reaches.  float64, pure numpy, summed in node order: the same
+    inputs give the same number anywhere.  For deciding when a refitted tree has degraded enough to rebuild it; needs no device"""
+    nodes = np.asarray(nodes)
+    if nodes.dtype.names is None:
+        nodes = nodes.view(np.dtype(_capi.BVH_NODE_DTYPE)).reshape(-1)
+    b = np.asarray(nodes["bounds"] if bounds is None else bounds, dtype=np.float64).reshape(len(nodes), 6)
+    leaf = nodes["leaf"] != 0
+    reached = np.zeros(len(nodes), dtype=bool)
+    front = np.array([0], dtype=np.int64)
+    while front.size:                                   # level by level: the nodes the root reaches
+        reached[front] = True
+        inner = front[~leaf[front]]
+        first = nodes["first"][inner].astype(np.int64)
+        front = np.concatenate([first, first + 1])
+        front = front[~reached[front]]
+    d = np.maximum(b[:, 1::2] - b[:, 0::2], 0.0)
+    area = 2.0 * (d[:, 0] * d[:, 1] + d[:, 1] * d[:, 2] + d[:, 2] * d[:, 0])
+    weight = np.where(leaf, nodes["count"].astype(np.float64), 1.0)
+    terms = np.where(reached, area * weight, 0.0)
+    return float(np.cumsum(terms)[-1] / area[0])        # (cumsum: strictly in node order)
+
+
 def seed_pairs(n_frames, first_frame=1):
     """(random0, random1) per frame: the un-seeded glibc rand() stream of the reference host,
     two values consumed by initCLKernel first (src/main.cpp:226-227,301-302)."""
@@ -259,6 +297,34 @@ class Renderer:
     def upload_scene(self, scene):
         desc = scene.desc if isinstance(scene, HostScene) else scene
         self._chk(self.lib.prt_upload_scene(self.ctx, C.byref(desc)), "prt_upload_scene")
+        self.triangle_count = int(desc.triangle_count)
+        self.bvh_node_count = int(desc.bvh_node_count) if desc.triangle_count else 0
+
+    def update_vertices(self, vertices, normals=None):
+        """prt_update_vertices / prt_update_vertices_device: new vertices (and normals; None keeps the uploaded ones) for the uploaded scene,
+        the tree refitted on the device (prt.h).  Both float32 [3T, 4] in the layout of SceneDesc.  numpy arrays take the host entry point;
+        torch tensors on this context's device (work queued on torch's current stream is waited for) or device addresses the device one"""
+        floats = 12 * getattr(self, "triangle_count", 0)
+        if isinstance(vertices, np.ndarray) or vertices is None:
+            v = None if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32)
+            n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32)
+            if (v is not None and v.size < floats) or (n is not None and n.size < floats):
+                raise ValueError("update_vertices: needs float32 arrays of at least %d elements" % floats)
+            self._chk(self.lib.prt_update_vertices(self.ctx, None if v is None else v.ctypes.data_as(C.c_void_p),
+                                                   None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_update_vertices")
+            return
+        if hasattr(vertices, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(vertices.device).synchronize()
+        pv = self._device_ptr(vertices, floats, "update_vertices")
+        pn = None if normals is None else self._device_ptr(normals, floats, "update_vertices")
+        self._chk(self.lib.prt_update_vertices_device(self.ctx, pv, pn), "prt_update_vertices_device")
+
+    def read_bvh_bounds(self):
+        """prt_read_bvh_bounds: float32 [bvh_node_count, 6] = min_x max_x min_y max_y min_z max_z per node of the uploaded tree, in its numbering"""
+        out = np.zeros((getattr(self, "bvh_node_count", 0), 6), dtype=np.float32)
+        self._chk(self.lib.prt_read_bvh_bounds(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_bvh_bounds")
+        return out
 
     def set_camera(self, cam):
         self._chk(self.lib.prt_set_camera(self.ctx, C.byref(cam)), "prt_set_camera")

@@ -104,11 +104,17 @@ PATH_STATE_DTYPE = [("origin", "<f4", 4), ("dir", "<f4", 4), ("time", "<f4"), ("
                     ("was_specular", "u1"), ("_p1", "u1", 3), ("reset", "u1"), ("_p2", "u1", 3),
                     ("samples", "<u4"), ("_p3", "u1", 8)]
 
+# numpy view of the 36-byte prt_bvh_node (BvhNode above)
+BVH_NODE_DTYPE = [("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)]
+
 # (name, restype, argtypes) of every symbol include/prt.h declares
 PRT_API = [
     ("prt_create", C.c_int, [C.c_int, C.POINTER(Config), C.POINTER(C.c_void_p)]),
     ("prt_destroy", None, [C.c_void_p]),
     ("prt_upload_scene", C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
+    ("prt_update_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_update_vertices_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_read_bvh_bounds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_set_camera", C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     ("prt_upload_envmap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("prt_resize", C.c_int, [C.c_void_p, C.c_int, C.c_int]),

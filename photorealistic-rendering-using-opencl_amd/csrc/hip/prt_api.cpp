@@ -19,6 +19,7 @@
 #include "pt_launch.h"
 #include "pt_layout.h"
 #include "pt_pack.h"
+#include "pt_refit.h"
 #include "pt_variant.h"
 
 using namespace prt;
@@ -136,6 +137,16 @@ struct prt_ctx {
     int rec_hist_w = 0, rec_hist_h = 0, rec_hist_cur = 0;
     bool rec_hist_valid = false;
     DevCamera rec_hist_cam{};
+    // prt_update_vertices (pt_refit.hip): the topology tables of the uploaded tree (host, PackedScene's), their device copies and the
+    // root's box + flag word (d_refit_root: 6 floats, then the check kernel's flag at word 6), uploaded with the first update; the host
+    // variant's staging buffers (3 T float4 each), allocated on first use.  All freed with the scene
+    std::vector<uint32_t> slot_vtx, level_pairs, level_first, node_box;
+    float root_bounds[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t n_tris = 0, n_nodes = 0;
+    void* d_slot_vtx = nullptr; void* d_level_pairs = nullptr; void* d_refit_root = nullptr;
+    void* d_stage_vtx = nullptr; void* d_stage_nrm = nullptr;
+    bool refit_ready = false;                      // the device tables are there
+    bool refitted = false;                         // an update has run since the upload: d_refit_root holds the root's box
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -237,6 +248,8 @@ static void free_frame(prt_ctx* c) {
 static void free_scene(prt_ctx* c) {
     free_dev(c->d_pairs); free_dev(c->d_tri_geom); free_dev(c->d_tri_nrm);
     free_dev(c->d_spheres); free_dev(c->d_quads); free_dev(c->d_sdfs); free_dev(c->d_mats); free_dev(c->d_light_tab);
+    free_dev(c->d_slot_vtx); free_dev(c->d_level_pairs); free_dev(c->d_refit_root); free_dev(c->d_stage_vtx); free_dev(c->d_stage_nrm);
+    c->refit_ready = c->refitted = false;
 }
 
 extern "C" void prt_destroy(prt_ctx* c) {
@@ -295,6 +308,12 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     c->have_scene = false;
     c->guides_valid = false;
     c->hist_valid = false;
+    // (the refit tables and staging buffers are the old tree's: a static scene holds none on the device)
+    free_dev(c->d_slot_vtx); free_dev(c->d_level_pairs); free_dev(c->d_refit_root); free_dev(c->d_stage_vtx); free_dev(c->d_stage_nrm);
+    c->refit_ready = c->refitted = false;
+    c->slot_vtx.swap(ps.slot_vtx); c->level_pairs.swap(ps.level_pairs); c->level_first.swap(ps.level_first); c->node_box.swap(ps.node_box);
+    std::memcpy(c->root_bounds, ps.root_bounds, sizeof(c->root_bounds));
+    c->n_tris = s->triangle_count; c->n_nodes = s->triangle_count ? s->bvh_node_count : 0u;
     const float* env = c->sc.env; const int env_w = c->sc.env_w, env_h = c->sc.env_h;    // the environment map survives scene uploads
     const float* env_rows = c->sc.env_cdf_rows; const float* env_cols = c->sc.env_cdf_cols;
     c->sc = DevScene{};
@@ -321,6 +340,103 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     }
     c->have_scene = true;
     for (int j = 0; j < prt_ctx::MAX_SUB; ++j) c->have_order[j] = false;
+    return PRT_OK;
+}
+
+// ---- deforming geometry: new vertices into the uploaded tree (prt.h prt_update_vertices; pt_refit.hip) ----------------------------------------
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// the checks both variants share, and the device tables on the first update
+static int refit_prepare(prt_ctx* c, const void* vertices, const char* who) {
+    const std::string w(who);
+    if (!c->have_scene || c->n_tris == 0) return fail(c, PRT_ERR_NOT_READY, w + ": no scene with triangles uploaded");
+    if (!vertices) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null vertices");
+    if (!c->sc.root_is_leaf && c->level_first.size() > 257u)
+        return fail(c, PRT_ERR_UNSUPPORTED, w + ": the tree has more than 256 levels of pairs (one launch per level)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->refit_ready) {
+        int rc;
+        if ((rc = upload(c, c->d_slot_vtx, c->slot_vtx)) || (rc = upload(c, c->d_level_pairs, c->level_pairs))) return rc;
+        free_dev(c->d_refit_root);
+        HIPCHK(c, hipMalloc(&c->d_refit_root, 32));
+        float init[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        std::memcpy(init, c->root_bounds, sizeof(c->root_bounds));      // (an empty leaf root keeps the box it was uploaded with)
+        HIPCHK(c, hipMemcpy(c->d_refit_root, init, sizeof(init), hipMemcpyHostToDevice));
+        c->refit_ready = true;
+    }
+    return PRT_OK;
+}
+
+extern "C" int prt_update_vertices_device(prt_ctx* c, const void* d_vertices, const void* d_normals) {
+    CTX_CHECK(c);
+    int rc = refit_prepare(c, d_vertices, "prt_update_vertices_device");
+    if (rc) return rc;
+    if (!aligned16(d_vertices) || !aligned16(d_normals))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_update_vertices_device: the device buffers must be 16-byte aligned");
+    const float* v = static_cast<const float*>(d_vertices);
+    const float* n = static_cast<const float*>(d_normals);
+    uint32_t* flag = static_cast<uint32_t*>(c->d_refit_root) + 6;
+    // the check first: its flag is read before anything of the scene is overwritten
+    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    launch_refit_check(v, 3 * (size_t)c->n_tris, flag, c->stream);
+    HIPCHK(c, hipGetLastError());
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_update_vertices: a vertex with a non-finite x, y or z (the scene is unchanged)");
+    RefitTables t;
+    t.slot_vtx = static_cast<const uint32_t*>(c->d_slot_vtx); t.n_slots = c->slot_vtx.size();
+    t.level_pairs = static_cast<const uint32_t*>(c->d_level_pairs);
+    t.level_first = c->level_first.data(); t.n_levels = c->level_first.empty() ? 0u : (uint32_t)c->level_first.size() - 1u;
+    t.root_is_leaf = c->sc.root_is_leaf; t.root_leaf_first = c->sc.root_leaf_first; t.root_leaf_count = c->sc.root_leaf_count;
+    // what a primary ray sees changes: the guides go stale and measured tile orders are forgotten, as with prt_set_camera; the path state,
+    // the framebuffer and both histories stay (prt.h)
+    c->guides_valid = false;
+    for (int j = 0; j < prt_ctx::MAX_SUB; ++j) c->have_order[j] = false;
+    c->refitted = true;
+    launch_refit(t, v, n, static_cast<NodePair*>(c->d_pairs), static_cast<TriGeom*>(c->d_tri_geom), static_cast<TriNrm*>(c->d_tri_nrm),
+                 static_cast<float*>(c->d_refit_root), c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // the caller's buffers may be reused on return
+    return PRT_OK;
+}
+
+extern "C" int prt_update_vertices(prt_ctx* c, const float* vertices, const float* normals) {
+    CTX_CHECK(c);
+    int rc = refit_prepare(c, vertices, "prt_update_vertices");
+    if (rc) return rc;
+    const size_t bytes = 3 * (size_t)c->n_tris * 16;
+    if (!c->d_stage_vtx) HIPCHK(c, hipMalloc(&c->d_stage_vtx, bytes));
+    if (normals && !c->d_stage_nrm) HIPCHK(c, hipMalloc(&c->d_stage_nrm, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->d_stage_vtx, vertices, bytes, hipMemcpyHostToDevice, c->stream));
+    if (normals) HIPCHK(c, hipMemcpyAsync(c->d_stage_nrm, normals, bytes, hipMemcpyHostToDevice, c->stream));
+    return prt_update_vertices_device(c, c->d_stage_vtx, normals ? c->d_stage_nrm : nullptr);
+}
+
+extern "C" int prt_read_bvh_bounds(prt_ctx* c, float* bounds6) {
+    CTX_CHECK(c);
+    if (!c->have_scene) return fail(c, PRT_ERR_NOT_READY, "prt_read_bvh_bounds: no scene uploaded");
+    if (!bounds6) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_bvh_bounds: null pointer");
+    if (!c->n_nodes) return PRT_OK;
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    std::vector<NodePair> pairs(c->sc.n_pairs);
+    if (!pairs.empty()) HIPCHK(c, hipMemcpy(pairs.data(), c->d_pairs, pairs.size() * sizeof(NodePair), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < c->n_nodes; ++i) {
+        float* o = bounds6 + 6 * (size_t)i;
+        const uint32_t at = c->node_box[i];
+        if (at == 0xFFFFFFFFu) { for (int j = 0; j < 6; ++j) o[j] = 0.0f; continue; }      // (a node no pair reaches)
+        std::memcpy(o, pairs[at >> 1].b + 6 * (at & 1u), 6 * sizeof(float));
+    }
+    // the root: stored in no pair.  After an update the device's; before, the same union over the uploaded pair 0 (a leaf root: as uploaded)
+    if (c->refitted) HIPCHK(c, hipMemcpy(bounds6, c->d_refit_root, 6 * sizeof(float), hipMemcpyDeviceToHost));
+    else if (c->sc.root_is_leaf) std::memcpy(bounds6, c->root_bounds, 6 * sizeof(float));
+    else {
+        RefitQuad q[3];
+        std::memcpy(q, pairs[0].b, sizeof(q));
+        const RefitBox r = refit_union(q);
+        std::memcpy(bounds6, r.b, 6 * sizeof(float));
+    }
     return PRT_OK;
 }
 
@@ -998,8 +1114,6 @@ extern "C" int prt_reset_history(prt_ctx* c) {
 }
 
 // ---- denoiser inputs as records (prt.h prt_export_denoise_inputs, prt_denoise_records; pt_records.hip) ---------------------------------------
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 extern "C" int prt_export_denoise_inputs(prt_ctx* c, void* device_records) {
     CTX_CHECK(c);
     if (!device_records || !aligned16(device_records) || !c->have_size)

@@ -82,5 +82,21 @@ void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, 
 void launch_records_export(const float4* fb, const uint4* q4, const float2* adapt, const float4* guides, int W, int rows, float4* records,
                            hipStream_t stream);
 void launch_records_import(const float4* records, int W, int H, float4* fb, float4* guides, float4* var, unsigned* no_stats, hipStream_t stream);
+// pt_refit.hip.  prt_update_vertices: the tables of the uploaded tree (PackedScene::slot_vtx, level_pairs: device; level_first: host)
+struct RefitTables {
+    const uint32_t* slot_vtx;       // device, n_slots
+    size_t n_slots;
+    const uint32_t* level_pairs;    // device, the pairs sorted by level
+    const uint32_t* level_first;    // HOST, n_levels + 1: level l is level_pairs[level_first[l] .. level_first[l + 1])
+    uint32_t n_levels;
+    int root_is_leaf;
+    uint32_t root_leaf_first, root_leaf_count;
+};
+// 1 into *flag (device; the caller zeroes it first) if x, y or z of any of the n_vertices float4 vertices is not finite
+void launch_refit_check(const float* vertices, size_t n_vertices, uint32_t* flag, hipStream_t stream);
+// the triangle records of every slot (normals null: tri_nrm is left alone), then the boxes level by level, deepest first, and the root's box
+// into root6 (device, 6 floats)
+void launch_refit(const RefitTables& t, const float* vertices, const float* normals, NodePair* pairs, TriGeom* tri_geom, TriNrm* tri_nrm,
+                  float* root6, hipStream_t stream);
 
 }  // namespace prt

@@ -125,8 +125,11 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
         for (uint32_t j = 0; j < nd.primitive_count; ++j) slot_src.push_back(nd.first_child_or_primitive + j);
         return true;
     };
+    out.slot_vtx.clear(); out.level_pairs.clear(); out.level_first.clear(); out.node_box.clear();
     if (T) {
         const prt_bvh_node* nodes = s->bvh_nodes;
+        out.node_box.assign(N, 0xFFFFFFFFu);
+        for (int j = 0; j < 6; ++j) out.root_bounds[j] = nodes[0].bounds[j];
         auto leaf_ok = [&](const prt_bvh_node& nd) { return (uint64_t)nd.first_child_or_primitive + nd.primitive_count <= T; };
         if (nodes[0].is_leaf) {
             if (!leaf_ok(nodes[0])) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: root leaf range out of bounds");
@@ -212,6 +215,7 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
                 for (int ch = 0; ch < 2; ++ch) {
                     const prt_bvh_node& cn = nodes[nd.first_child_or_primitive + ch];
                     for (int j = 0; j < 6; ++j) p.b[6 * ch + j] = cn.bounds[j];
+                    out.node_box[nd.first_child_or_primitive + ch] = (uint32_t)(2 * k + ch);
                     if (cn.is_leaf) {
                         if (!leaf_ok(cn)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: leaf range out of bounds");
                         if (cn.primitive_count == 0xFFFFFFFFu) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: bad leaf");
@@ -241,6 +245,29 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
             }
             if (max_sp > 64u) return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_scene: BVH needs more than the 64 traversal-stack entries of the reference (bvh.cl:131)");
             sc.stack_levels = max_sp + 1;
+            // The pairs by level, for the bottom-up box pass of a refit (pt_refit.hip: one launch per level, deepest first).  A level is a
+            // contiguous range of pairs in breadth-first order only; the table serves every order.  (stack_levels bounds the pairs with two
+            // inner children on a path, not the levels: a chain of pairs can be arbitrarily deep)
+            std::vector<uint32_t> level(pairs.size(), 0u);
+            std::vector<uint32_t> walk{0u};
+            uint32_t deepest = 0;
+            while (!walk.empty()) {
+                const uint32_t k = walk.back();
+                walk.pop_back();
+                const NodePair& p = pairs[k];
+                for (int ch = 0; ch < 2; ++ch)
+                    if (p.meta[2 * ch + 1] == 0xFFFFFFFFu) {
+                        level[p.meta[2 * ch]] = level[k] + 1u;
+                        if (level[k] + 1u > deepest) deepest = level[k] + 1u;
+                        walk.push_back(p.meta[2 * ch]);
+                    }
+            }
+            out.level_first.assign((size_t)deepest + 2, 0u);
+            for (size_t k = 0; k < pairs.size(); ++k) ++out.level_first[level[k] + 1];
+            for (size_t l = 1; l < out.level_first.size(); ++l) out.level_first[l] += out.level_first[l - 1];
+            std::vector<uint32_t> at(out.level_first.begin(), out.level_first.end() - 1);
+            out.level_pairs.resize(pairs.size());
+            for (size_t k = 0; k < pairs.size(); ++k) out.level_pairs[at[level[k]]++] = (uint32_t)k;
         }
     } else {
         sc.root_leaf_first = 0; sc.root_leaf_count = 0;        // "no OBJ" = empty leaf root
@@ -252,8 +279,10 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
     for (uint32_t i = 0; i < T; ++i)
         if ((uint64_t)((uint32_t)s->primitive_indices[i] * 3u) + 2 >= (uint64_t)T * 3) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: primitive index out of range");
     tg.assign(S, TriGeom{}); tn.assign(S, TriNrm{});
+    out.slot_vtx.resize(S);
     for (size_t i = 0; i < S; ++i) {
         const uint32_t fv = (uint32_t)s->primitive_indices[slot_src[i]] * 3u;        // triangle.cl:7 (uint arithmetic)
+        out.slot_vtx[i] = fv;
         const float* p0 = s->vertices + 4 * (size_t)fv;
         const float* p1 = p0 + 4; const float* p2 = p0 + 8;
         TriGeom& g = tg[i];

@@ -1,0 +1,244 @@
+#!/usr/bin/env python3
+"""prt_update_vertices (the device refit of a deforming mesh) against what the same change cost before it existed, on the MI355X.
+
+Per scene (the teapot of cornell_coat and the 871 k-triangle stand-in of BASELINE config 5): the mesh is deformed by a sine wave of 1, 5 and
+20 % of its extent (float32 numpy), and timed, wall clock, each call complete on return:
+  update_device      prt_update_vertices_device from device buffers (vertices + normals)
+  update_host        prt_update_vertices from host arrays (PCIe included)
+  rebuild_upload     the parent's path: a host build over the deformed mesh (HostScene on a mesh file written for it: reading the file, the
+                     SAH build) plus prt_upload_scene
+  refit_upload       the parent's cheaper path: the caller's nodes refitted in numpy (vectorised, by value) plus prt_upload_scene alone
+and bvh_cost (SAH, package helper) of the refitted tree against the rebuilt one per deformation.
+Kernel times: from `rocprofv3 --kernel-trace --stats` in a run of its own (this script with --phase kernels).  One JSON document on stdout
+(and into --out).
+
+    python tools/refit_rate.py [--scenes cornell_coat,cornell_dragon] [--out profiles/r12_refit.json]
+"""
+import argparse
+import csv
+import glob
+import importlib
+import json
+import os
+import struct
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+KERNEL_CALLS = 5
+f32 = np.float32
+
+
+def deform(v0, amount, phase=0.0):
+    """a sine wave across y that pushes x and z by `amount` x the mesh's largest extent"""
+    v = v0.copy()
+    lo, hi = v0[:, :3].min(axis=0), v0[:, :3].max(axis=0)
+    ext = f32((hi - lo).max())
+    t = ((v0[:, 1] - lo[1]) / f32(max(hi[1] - lo[1], 1e-6))).astype(f32)
+    w = np.sin(f32(6.2831853) * (f32(3.0) * t + f32(phase))).astype(f32)
+    v[:, 0] += f32(amount) * ext * w
+    v[:, 2] += f32(amount) * ext * np.cos(f32(6.2831853) * (f32(2.0) * t + f32(phase))).astype(f32)
+    return v
+
+
+def numpy_refit(nodes, pi, v):
+    """the caller's nodes refitted in numpy, vectorised: leaf boxes by reduceat over the leaves' vertices, inner boxes level by level from
+    the deepest (by value: np.minimum does not pin the sign of a zero, which a timing baseline does not need)"""
+    out = nodes.copy()
+    leaf = nodes["leaf"] != 0
+    first, count = nodes["first"].astype(np.int64), nodes["count"].astype(np.int64)
+    levels, front = [], np.array([0], dtype=np.int64)
+    while front.size:
+        levels.append(front)
+        inner = front[~leaf[front]]
+        nxt = np.concatenate([first[inner], first[inner] + 1])
+        front = nxt
+    lv = np.nonzero(leaf & (count > 0))[0]
+    if lv.size:
+        starts = np.concatenate([[0], np.cumsum(count[lv])[:-1]])
+        which = np.repeat(np.arange(lv.size), count[lv])
+        tri = pi[(first[lv][which] + (np.arange(which.size) - starts[which]))].astype(np.int64)
+        pts = v[(3 * tri[:, None] + np.arange(3)[None, :]).reshape(-1), :3]
+        b = out["bounds"]
+        b[lv, 0::2] = np.minimum.reduceat(pts, 3 * starts, axis=0)
+        b[lv, 1::2] = np.maximum.reduceat(pts, 3 * starts, axis=0)
+    for members in reversed(levels):
+        inner = members[~leaf[members]]
+        b = out["bounds"]
+        b[inner, 0::2] = np.minimum(b[first[inner], 0::2], b[first[inner] + 1, 0::2])
+        b[inner, 1::2] = np.maximum(b[first[inner], 1::2], b[first[inner] + 1, 1::2])
+    return out
+
+
+def write_mesh(path, v, n):
+    tris = np.concatenate([v[:, :3], n[:, :3]], axis=1).astype(f32).reshape(-1, 3, 6)
+    with open(path, "wb") as fh:
+        fh.write(b"PRTMESH1")
+        fh.write(struct.pack("<I", tris.shape[0]))
+        fh.write(tris.tobytes())
+
+
+def _scene(prt, name):
+    if "dragon" in name:
+        prt.ensure_dragon_standin()
+    return prt.HostScene(name + ".json")
+
+
+def _median_ms(fn, n):
+    out = []
+    for _ in range(n):
+        t = time.perf_counter()
+        fn()
+        out.append(1e3 * (time.perf_counter() - t))
+    return round(float(np.median(out)), 4), round(float(min(out)), 4)
+
+
+def measure(prt, name, calls):
+    import ctypes as C
+    import torch
+    scene = _scene(prt, name)
+    a = prt.scene_arrays(scene.desc)
+    v0, n0, pi, nodes = a["vertices"].copy(), a["normals"].copy(), a["primitive_indices"].copy(), a["nodes"].copy()
+    mesh_file = os.path.splitext(os.path.basename(scene.lib.prth_scene_obj_path(scene.handle).decode()))[0] + ".prtmesh"   # (the loader falls back to it)
+    cfg = scene.config()
+    r = prt.Renderer(cfg, device=0)
+    r.upload_scene(scene)
+    out = {"triangles": int(scene.desc.triangle_count), "bvh_nodes": int(scene.desc.bvh_node_count), "cost_original": prt.bvh_cost(nodes)}
+    assert (r.read_bvh_bounds() == nodes["bounds"]).all()
+    v1 = deform(v0, 0.01)
+    dv, dn = torch.from_numpy(v1).cuda(), torch.from_numpy(n0).cuda()
+    torch.cuda.synchronize()
+    r.update_vertices(dv, dn)                                              # (the first update uploads the tables)
+    out["update_device_ms_median_min"] = _median_ms(lambda: r.update_vertices(dv, dn), calls)
+    out["update_device_no_normals_ms_median_min"] = _median_ms(lambda: r.update_vertices(dv, None), calls)
+    out["update_host_ms_median_min"] = _median_ms(lambda: r.update_vertices(v1, n0), max(calls // 2, 3))
+    assert (r.read_bvh_bounds() == numpy_refit(nodes, pi, v1)["bounds"]).all(), "the device refit disagrees with the numpy refit"
+
+    # the parent's paths for the same change
+    t = time.perf_counter()
+    nodes1 = numpy_refit(nodes, pi, v1)
+    numpy_s = time.perf_counter() - t
+    desc = prt.SceneDesc.from_buffer_copy(bytes(scene.desc))
+    desc.vertices, desc.normals = v1.ctypes.data_as(C.c_void_p), n0.ctypes.data_as(C.c_void_p)
+    desc.bvh_nodes = nodes1.ctypes.data_as(C.c_void_p)
+
+    def upload():
+        r.upload_scene(desc)
+        r.synchronize()
+    up = _median_ms(upload, 3)
+    out["refit_upload"] = {"numpy_refit_ms": round(1e3 * numpy_s, 2), "upload_scene_ms_median_min": up, "total_ms": round(1e3 * numpy_s + up[0], 2)}
+    out["deformations"] = {}
+    with tempfile.TemporaryDirectory() as d:
+        for amount in (0.01, 0.05, 0.20):
+            v = deform(v0, amount)
+            write_mesh(os.path.join(d, mesh_file), v, n0)
+            t = time.perf_counter()
+            rebuilt = prt.HostScene(name + ".json", models_dir=d)
+            build_s = time.perf_counter() - t
+            t = time.perf_counter()
+            r.upload_scene(rebuilt)
+            r.synchronize()
+            upload_s = time.perf_counter() - t
+            cost_rebuilt = prt.bvh_cost(prt.scene_arrays(rebuilt.desc)["nodes"])
+            r.upload_scene(scene)                                          # back to the original tree, refitted to the same vertices
+            r.update_vertices(v, None)
+            cost_refit = prt.bvh_cost(nodes, r.read_bvh_bounds())
+            out["deformations"]["%g" % amount] = {
+                "rebuild_upload": {"load_and_build_ms": round(1e3 * build_s, 2), "upload_scene_ms": round(1e3 * upload_s, 2),
+                                   "total_ms": round(1e3 * (build_s + upload_s), 2)},
+                "bvh_cost_refitted": cost_refit, "bvh_cost_rebuilt": cost_rebuilt, "refitted_over_rebuilt": round(cost_refit / cost_rebuilt, 4)}
+            rebuilt.close()
+    dev = out["update_device_ms_median_min"][0]
+    out["ratio_to_parent"] = {"rebuild_upload_over_update_device": round(out["deformations"]["0.01"]["rebuild_upload"]["total_ms"] / dev, 1),
+                              "refit_upload_over_update_device": round(out["refit_upload"]["total_ms"] / dev, 1),
+                              "rebuild_upload_over_update_host": round(out["deformations"]["0.01"]["rebuild_upload"]["total_ms"] / out["update_host_ms_median_min"][0], 1)}
+    r.close()
+    return out
+
+
+def kernels_phase(prt, names):
+    """the launches rocprofv3 times: KERNEL_CALLS device updates (with normals) per scene"""
+    import torch
+    for name in names:
+        scene = _scene(prt, name)
+        a = prt.scene_arrays(scene.desc)
+        r = prt.Renderer(scene.config(), device=0)
+        r.upload_scene(scene)
+        dv, dn = torch.from_numpy(deform(a["vertices"], 0.05)).cuda(), torch.from_numpy(a["normals"].copy()).cuda()
+        torch.cuda.synchronize()
+        for _ in range(KERNEL_CALLS):
+            r.update_vertices(dv, dn)
+        r.close()
+
+
+def kernel_times(names, timeout):
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "refit", "--",
+               sys.executable, os.path.abspath(__file__), "--phase", "kernels", "--scenes", ",".join(names)]
+        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
+        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+        assert traces, "rocprofv3 wrote no kernel trace"
+        with open(traces[0]) as fh:
+            rows = [(row["Kernel_Name"], int(row["Start_Timestamp"]), int(row["End_Timestamp"])) for row in csv.DictReader(fh)]
+    rows = sorted((r for r in rows if "refit_" in r[0]), key=lambda r: r[1])
+    # one update = a check launch and everything up to the next one
+    starts = [i for i, r in enumerate(rows) if "refit_check" in r[0]]
+    assert len(starts) == KERNEL_CALLS * len(names), (len(starts), len(rows))
+    out = {}
+    for s, name in enumerate(names):
+        best = None
+        for c in range(1, KERNEL_CALLS):                     # (call 0 follows the tables' upload)
+            i = starts[s * KERNEL_CALLS + c]
+            j = starts[s * KERNEL_CALLS + c + 1] if s * KERNEL_CALLS + c + 1 < len(starts) else len(rows)
+            one = rows[i:j]
+            lv = [r for r in one if "refit_level" in r[0] or "refit_root_leaf" in r[0]]
+            rec = {"check_us": round(sum(e - b for n, b, e in one if "refit_check" in n) / 1e3, 2),
+                   "tri_us": round(sum(e - b for n, b, e in one if "refit_tri" in n) / 1e3, 2),
+                   "levels_busy_us": round(sum(e - b for n, b, e in lv) / 1e3, 2), "level_launches": len(lv),
+                   "levels_span_us": round((lv[-1][2] - lv[0][1]) / 1e3, 2) if lv else 0.0,
+                   "tri_to_root_span_us": round((one[-1][2] - one[1][1]) / 1e3, 2) if len(one) > 1 else 0.0}
+            if best is None or rec["tri_to_root_span_us"] < best["tri_to_root_span_us"]:
+                best = rec
+        out[name] = best
+    out["note"] = "kernel durations of one prt_update_vertices_device call (best of %d), rocprofv3 --kernel-trace --stats; levels_span = first " \
+                  "level's start to the root's end (launch gaps included), levels_busy = the sum of the level kernels' own durations" % (KERNEL_CALLS - 1)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="cornell_coat,cornell_dragon")
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--phase", default="all", choices=["all", "rates", "kernels"])
+    ap.add_argument("--rocprof-timeout", type=int, default=300)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    prt = importlib.import_module("photorealistic-rendering-using-opencl_amd")
+    names = a.scenes.split(",")
+    if a.phase == "kernels":
+        kernels_phase(prt, names)
+        return
+    doc = {"build_id": prt.build_id(), "calls": a.calls, "scenes": {}}
+    for name in names:
+        doc["scenes"][name] = measure(prt, name, a.calls)
+        print(json.dumps({name: doc["scenes"][name]}), file=sys.stderr, flush=True)
+    if a.phase == "all":
+        try:
+            doc["kernel_time"] = kernel_times(names, a.rocprof_timeout)
+        except (subprocess.SubprocessError, AssertionError, KeyError, OSError) as e:
+            doc["kernel_time"] = {"error": repr(e)}
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
