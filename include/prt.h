@@ -518,14 +518,29 @@ int prt_synchronize(prt_ctx* ctx);
 int prt_read_framebuffer(prt_ctx* ctx, float* rgba);
 /* display side ("next" row N3): the reference's fragment shader (shaders/tonemapper.glsl:47-64: vignette,
  * filmic Reinhard with white point 1.2, smoothstep, gamma 2.2) applied on the device; 8-bit RGBA out, rows in
- * framebuffer order (what glReadPixels returns, include/GL/cl_gl_interop.h:147-150). */
+ * framebuffer order (what glReadPixels returns, include/GL/cl_gl_interop.h:147-150).  The vignette takes the pixel's
+ * place in the whole frame: a tile or a row-block part gets its rows of the whole frame's picture.  Alpha is 255.
+ * The transform is evaluated in float32, in the shader's order and without contraction, per channel x of the framebuffer:
+ *     v = x * vignette;   q = 57.25f*v*v;   v = (q / (q + v + 56.25f)) / curve(1.2f);   t = clamp((v + 0.025f) / 1.025f, 0, 1);
+ *     out = rint(255 * clamp(pow(t*t*(3 - 2*t), 1/2.2f), 0, 1))
+ * with fmin / fmax that ignore a NaN operand.  So a NaN, +-inf and any value whose 57.25f*v*v overflows float32 (|x * vignette|
+ * above about 2.4e18; q / (q + ...) is inf / inf there) map to 0 -- black, where exact arithmetic would say 255 for the large
+ * ones --, and a zero of either sign and the denormals map to the byte of 0.0 (14 at the centre of the frame). */
 int prt_tonemap_rgba8(prt_ctx* ctx, uint8_t* rgba);
 /* same, device to device, into caller-owned device memory (e.g. a torch tensor).  Asynchronous on a stream given
  * with prt_set_stream (ordered with the caller's other work there); complete on return otherwise (the context's own
  * stream is private and non-blocking: nothing of the caller's is ordered against it). */
 int prt_copy_framebuffer_to_device(prt_ctx* ctx, void* device_rgba);
 
-/* r_flat, in the reference's 112-byte RTD layout (checkpoint / resume / parity checks). */
+/* r_flat, in the reference's 112-byte RTD layout (checkpoint / resume / parity checks), one record per pixel of this context's
+ * frame part in framebuffer order.  The device keeps 80 bytes per pixel; of a record these are carried, bit for bit (floats as
+ * their bits: NaN payloads, signed zeros and denormals included): origin[0..2], time, dir[0..2], dist, mask[0..2], total,
+ * acc[0..3], samples, diff, spec, trans, scatters.  was_specular and reset are carried as flags: any non-zero value is read back
+ * as 1.  origin[3], dir[3], mask[3] and the pad bytes are not carried: prt_write_state ignores them and prt_read_state returns
+ * them as zero (as it does the converged bit of prt_render_adaptive, which no record shows).
+ * prt_write_state also sets the framebuffer, as the render kernels leave it: acc[k] / (float)samples per channel (IEEE float32
+ * division), and +0.0 in all four channels where samples == 0, whatever acc holds.  It leaves the context not fresh (prt_render_spp
+ * and prt_render_adaptive need a prt_reset) and the adaptive statistics plane invalid. */
 int prt_read_state(prt_ctx* ctx, prt_path_state* state);
 int prt_write_state(prt_ctx* ctx, const prt_path_state* state);
 

@@ -254,6 +254,39 @@ def test_schedules_change_no_bit(prt, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_live_list_past_one_scan_run_and_with_a_ragged_tail(prt, monkeypatch):
+    """331 x 199 = 65 869 pixels: 1 030 wave counts, so each of live_scan_kernel's 1 024 threads sums a run of two and the threads above 514
+    have empty runs; the last wave of live_count / live_write has 13 pixels; neither side is a multiple of the 8 x 8 tile.  Lists from the first
+    freeze on (compact_below 100), on a context whose list buffers were sized for a smaller frame before"""
+    W, H = 331, 199
+    assert (W * H + 63) // 64 == 1030 and W * H % 64 == 13
+    seeds = prt.seed_pairs(_frames(MAX))
+    all_px = np.ones(W * H, bool)
+    scene, cfg, cam, env, r = _setup(prt, "cornell_coat", W, H)
+    r.set_option("compact", 0)
+    ref = _adaptive(r, seeds)[:2]
+    assert r.adaptive_report().list_launches == 0
+    assert len(np.unique(ref[0]["samples"])) >= 3, np.unique(ref[0]["samples"])
+    r.close()
+    for streams in ("1", "2"):
+        monkeypatch.setenv("PRT_STREAMS", streams)
+        scene, cfg, cam, env, r = _setup(prt, "cornell_coat", 64, 48)
+        for name, value in (("compact", 1), ("compact_below", 100), ("frames_per_launch", 16)):
+            r.set_option(name, value)
+        _adaptive(r, seeds)                                   # allocates the list and its wave counts for 3 072 pixels
+        assert r.adaptive_report().list_builds >= 1
+        r.resize(W, H)
+        r.set_camera(variant_camera(prt, "cornell_coat", W, H))
+        got = _adaptive(r, seeds)[:2]
+        assert r.stats().concurrent == int(streams)
+        _same_pixels(ref, got, all_px, "lists from the first freeze on, PRT_STREAMS=%s, after a 64 x 48 render on the same context" % streams)
+        rep = r.adaptive_report()
+        assert rep.list_builds >= 2 and rep.list_launches >= 1 and 0 < rep.list_live_lanes <= rep.list_lanes, \
+            (rep.list_builds, rep.list_launches, rep.list_live_lanes, rep.list_lanes)
+        r.close()
+
+
+@pytest.mark.gpu
 def test_schedules_change_no_bit_through_the_big_tree(prt, monkeypatch):
     """the 871 k-triangle stand-in on a strip of its 1080p frame (rows through the mesh): tiles and lists, tile order on and off"""
     W, H, row0, rows = 1920, 1080, 500, 24
