@@ -163,8 +163,13 @@ int prt_upload_scene(prt_ctx* ctx, const prt_scene_desc* scene);
  * normals and the refitted nodes, bit for bit.
  * Lifetime: an update makes the guides stale and forgets measured tile orders, as prt_set_camera does.  It keeps the path state, the
  * framebuffer (unchanged until the next render) and both temporal histories.  The loop per displayed frame: update, prt_reset, render,
- * prt_render_guides, prt_denoise_temporal.  The reprojection's depth and normal tests are what reject surfaces that moved; where they happen
- * to pass on a moved surface the history GHOSTS (there are no motion vectors of animated geometry) -- prt_reset_history empties it.  Spheres,
+ * prt_render_guides, prt_denoise_temporal.  Without motion (prt_set_motion, below: off by default) the reprojection treats every surface as if it
+ * had stood still: its depth and normal tests reject most surfaces that moved (their history restarts), and where they happen to pass the
+ * history of another surface point is blended in.  With motion on, the guide render also says where each pixel's point of the mesh was
+ * before the update and the reprojection looks there: the history follows the deforming mesh.  What still does not follow: spheres, quads
+ * and SDF primitives (prt_upload_scene moves them: no history across it), surfaces seen through mirrors or glass (the virtual point behind a
+ * delta chain carries no motion), and a surface that turns by more than cos_n between two frames (the normal test compares the current normal
+ * with the one stored in the previous frame; previous-frame normals are out of scope) -- those restart.  prt_reset_history empties it.  Spheres,
  * quads, SDF primitives and materials are not touched: moving them stays prt_upload_scene's job.  The tables a refit needs (4 bytes per slot
  * and per inner node) go to the device with the first update: a static scene costs no device memory.
  * Refused, each leaving the scene exactly as it was: PRT_ERR_NOT_READY without a scene or with T == 0; PRT_ERR_INVALID_ARGUMENT for null
@@ -281,6 +286,43 @@ int prt_get_adaptive_report(prt_ctx* ctx, prt_adaptive_report* out);
 int prt_render_guides(prt_ctx* ctx, uint32_t samples);
 int prt_read_guides(prt_ctx* ctx, float* out8);
 
+/* Motion of deforming geometry into the temporal reprojection (no counterpart in the reference).  Opt-in: prt_set_motion(ctx, 1); off (the
+ * default) every bit of every result is what it is without these calls.
+ * The motion plane: per pixel of the context's frame part one more float4 {D.x, D.y, D.z, m}, written by prt_render_guides with motion on.  IT
+ * DESCRIBES THE DISPLACEMENT OF THE GEOMETRY BETWEEN THE PREVIOUS prt_render_guides AND THIS ONE:
+ *   Snapshot: with motion on, prt_update_vertices / prt_update_vertices_device copy the triangle records (48 bytes per slot; the buffer is
+ *     allocated by the first such update) before the refit overwrites them -- after every refusal is decided (a refused update leaves the
+ *     snapshot as it was), one device-to-device copy on the context's stream, and only when no snapshot is pending: of several updates
+ *     between two guide renders the oldest geometry is kept.  prt_render_guides with motion on measures from the pending snapshot and
+ *     consumes it; without one (no update since the last guide render) the plane is all zeros.  The rule is the context's own: a rank that
+ *     only renders and exports behaves as the one that filters.  prt_upload_scene and turning motion off drop the snapshot and free it.
+ *   Per guide sample s whose FIRST hit (no delta event before it) is a mesh triangle -- the triangle wins finish_closest against spheres,
+ *     quads and SDF primitives --, with (slot, u, v) that hit, f32, no contraction, per component:
+ *         q(rec) = (rec.p0 - rec.e1 * u) + rec.e2 * v       (p1 = p0 - e1, p2 = p0 + e2; u weighs vertex 1, v vertex 2, as the hit's normal)
+ *         d_s    = q(tri_prev[slot]) - q(tri_geom[slot])    (where the point was, minus where it is; exactly 0 for an unchanged record)
+ *     Hits on spheres, quads and SDF primitives, hits behind a mirror or glass chain and misses contribute nothing.
+ *   Per pixel: D = (sum of d_s in sample order) / (float)hits (IEEE division; hits = the guides' own hit count: the mean over the hits, as the
+ *     guides' depth), m = (float)contributing_samples * (1 / samples).  hits == 0, or no snapshot pending: D = 0, m = 0.
+ *   The eight guide floats are the same bits with motion on and off; tiles and row blocks work as for the guides (global coordinates: the
+ *     union of the parts is the whole frame's plane bit for bit).
+ * In the reprojection (prt_denoise_temporal, below): a covered pixel with m > 0 and (D.x, D.y, D.z) != (0, 0, 0) takes
+ *     e = ((position + d * z_p) + D) - P_prev
+ *   and everything downstream unchanged: dist = |e|, the projection, the taps' depth test against the previous guides, the normal test (the
+ *   current normal against the stored one: a surface that turns by more than cos_n restarts), the blend.  Every other pixel, and a call
+ *   without a plane, takes the expressions of prt_denoise_temporal as they stand: a plane of zeros gives the same bits as no plane.
+ * prt_set_motion: default 0.  A change makes the guides stale and keeps both histories; a call with the value in force does nothing.  PRT_ERR_UNSUPPORTED with a debug view.  A scene without
+ *   triangles is accepted: its planes are zeros.
+ * prt_read_motion: width * rows * 4 floats, framebuffer order.  PRT_ERR_NOT_READY while motion is off or there are no valid guides rendered
+ *   with motion on; PRT_ERR_INVALID_ARGUMENT for a null pointer or a context without a frame size.
+ * prt_export_motion: the plane of the frame part (whole frame, tile or row blocks) into device memory of the caller, ordered on the
+ *   context's stream as prt_export_denoise_inputs.  Refused as prt_read_motion, and for a pointer that is not 16-byte aligned.  Both calls
+ *   write nothing of the context.
+ * prt_denoise_temporal uses the context's plane when motion is on and the plane belongs to the valid guides; prt_denoise_records_temporal_motion
+ *   (below) takes it as an argument beside the records, whose 64-byte layout is unchanged. */
+int prt_set_motion(prt_ctx* ctx, int enable);
+int prt_read_motion(prt_ctx* ctx, float* out4);
+int prt_export_motion(prt_ctx* ctx, void* device_motion);
+
 /* Denoiser: the spatial part of SVGF (Schied et al. 2017), an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010), guided by the
  * guides above.  L(c) = 0.2126 r + 0.7152 g + 0.0722 b.  Inputs: the framebuffer colour c, the guides {a, cov, n, z} and the luminance
  * variance of the pixel's mean, v, from
@@ -332,7 +374,8 @@ int prt_denoise(prt_ctx* ctx, const prt_denoise_params* params, float* rgba, uin
  * Hz = horizontal, Vt = vertical).  At the end of each call the history takes the current guides and camera.  L(c) as in prt_denoise.
  *   World point of pixel p = (x, y): d = normalize(onPlane(p) - position), onPlane = create_cam_ray's expression at the pixel centre
  *     (sx = x / (W-1), sy = (H-1-y) / (H-1)), with the current camera.  cov_p > 0: X = position + z_p d -- the pinhole centre ray (with a
- *     lens an approximation; after a mirror or glass chain the virtual point behind the surface).  cov_p = 0: the pixel reprojects as the
+ *     lens an approximation; after a mirror or glass chain the virtual point behind the surface).  With a motion plane (prt_set_motion) and m_p > 0,
+ *     D_p != 0: X + D_p, where that point of the mesh was, in its place.  cov_p = 0: the pixel reprojects as the
  *     direction d (a point at infinity).
  *   Projection into the previous camera: e = X - P (d for a direction); no history when dot(e, M - P) <= 0.  f = M - P,
  *     q = e dot(f, f) / dot(e, f) - f, a = dot(q, Hz) / dot(Hz, Hz), b = dot(q, Vt) / dot(Vt, Vt); x' = (a + 1)/2 (W-1),
@@ -414,6 +457,11 @@ int prt_denoise_records(prt_ctx* ctx, const prt_denoise_params* params, int widt
                         float* rgba, uint8_t* rgba8);
 int prt_denoise_records_temporal(prt_ctx* ctx, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
                                  int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8);
+/* prt_denoise_records_temporal with the motion plane of the records' frame (width * height float4 {D, m} in device memory, 16-byte aligned:
+ * the gathered prt_export_motion of every part).  device_motion NULL is exactly prt_denoise_records_temporal; both calls share the record history. */
+int prt_denoise_records_temporal_motion(prt_ctx* ctx, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
+                                        int width, int height, const void* device_records, const void* device_motion, void* device_rgba,
+                                        float* rgba, uint8_t* rgba8);
 int prt_reset_records_history(prt_ctx* ctx);
 int prt_read_records_history(prt_ctx* ctx, int width, int height, float* out8);
 

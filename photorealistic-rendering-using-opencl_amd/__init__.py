@@ -393,6 +393,23 @@ class Renderer:
         self._chk(self.lib.prt_read_guides(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_guides")
         return out
 
+    def set_motion(self, enable=True):
+        """prt_set_motion: the guide renders also write the motion plane of the deforming mesh (update_vertices) and denoise_temporal
+        reprojects through it (prt.h).  Off by default; makes the guides stale, keeps the histories"""
+        self._chk(self.lib.prt_set_motion(self.ctx, 1 if enable else 0), "prt_set_motion")
+
+    def read_motion(self):
+        """the motion plane of the last render_guides: float32 [rows, width, 4] = {D.xyz, m} per pixel, framebuffer order (prt.h)"""
+        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        self._chk(self.lib.prt_read_motion(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_motion")
+        return out
+
+    def export_motion(self, ptr_or_tensor):
+        """prt_export_motion: the motion plane of this context's frame part into device memory: a [rows, width, 4] float32 tensor on this
+        device (more rows are left alone) or a device address"""
+        p = self._device_ptr(ptr_or_tensor, self.rows * self.width * _capi.MOTION_FLOATS, "export_motion")
+        self._chk(self.lib.prt_export_motion(self.ctx, p), "prt_export_motion")
+
     _VAR_SOURCES = {"auto": _capi.PRT_DENOISE_VAR_AUTO, "stats": _capi.PRT_DENOISE_VAR_STATS, "spatial": _capi.PRT_DENOISE_VAR_SPATIAL}
 
     def denoise(self, passes=DENOISE_DEFAULTS["passes"], var_source="auto", sigma_l=DENOISE_DEFAULTS["sigma_l"],
@@ -451,16 +468,16 @@ class Renderer:
         p = self._device_ptr(ptr_or_tensor, self.rows * self.width * _capi.DENOISE_RECORD_FLOATS, "export_denoise_inputs")
         self._chk(self.lib.prt_export_denoise_inputs(self.ctx, p), "prt_export_denoise_inputs")
 
-    def _records_call(self, name, head, records, width, height, tonemap, out):
+    def _records_call(self, name, head, records, width, height, tonemap, out, extra=()):
         width, height = int(width), int(height)
-        rec = self._device_ptr(records, width * height * _capi.DENOISE_RECORD_FLOATS, name)
+        rec = (self._device_ptr(records, width * height * _capi.DENOISE_RECORD_FLOATS, name),) + tuple(extra)
         fn = getattr(self.lib, name)
         if out is not None:
-            self._chk(fn(self.ctx, *head, width, height, rec, self._device_ptr(out, width * height * 4, name), None, None), name)
+            self._chk(fn(self.ctx, *head, width, height, *rec, self._device_ptr(out, width * height * 4, name), None, None), name)
             return out
         host = np.zeros((max(height, 0), max(width, 0), 4), dtype=np.uint8 if tonemap else np.float32)   # a size below 1 is the library's to refuse
         ptr = host.ctypes.data_as(C.c_void_p)
-        self._chk(fn(self.ctx, *head, width, height, rec, None, None if tonemap else ptr, ptr if tonemap else None), name)
+        self._chk(fn(self.ctx, *head, width, height, *rec, None, None if tonemap else ptr, ptr if tonemap else None), name)
         return host
 
     def denoise_records(self, records, width, height, passes=DENOISE_DEFAULTS["passes"], var_source="auto", sigma_l=DENOISE_DEFAULTS["sigma_l"],
@@ -477,13 +494,19 @@ class Renderer:
                                  sigma_l=DENOISE_DEFAULTS["sigma_l"], sigma_n=DENOISE_DEFAULTS["sigma_n"], sigma_z=DENOISE_DEFAULTS["sigma_z"],
                                  sigma_a=DENOISE_DEFAULTS["sigma_a"], alpha_color=TEMPORAL_DEFAULTS["alpha_color"],
                                  alpha_moments=TEMPORAL_DEFAULTS["alpha_moments"], tau_z=TEMPORAL_DEFAULTS["tau_z"], cos_n=TEMPORAL_DEFAULTS["cos_n"],
-                                 history_cap=TEMPORAL_DEFAULTS["history_cap"], feedback=TEMPORAL_DEFAULTS["feedback"], tonemap=False, out=None):
+                                 history_cap=TEMPORAL_DEFAULTS["history_cap"], feedback=TEMPORAL_DEFAULTS["feedback"], tonemap=False, out=None,
+                                 motion=None):
         """prt_denoise_records_temporal: denoise_records() with denoise_temporal()'s step in front.  `cam`: the camera the records were rendered
-        with.  The record history is this context's second one (reset_records_history(); a call with another size empties it too)"""
+        with.  The record history is this context's second one (reset_records_history(); a call with another size empties it too).
+        motion: None, or the frame's motion plane (a [height, width, 4] float32 tensor on this device or a device address: the gathered
+        export_motion() of every part) -- prt_denoise_records_temporal_motion"""
         p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
         t = TemporalParams(float(alpha_color), float(alpha_moments), float(tau_z), float(cos_n), int(history_cap), self._FEEDBACK[feedback])
-        return self._records_call("prt_denoise_records_temporal", (C.byref(p), C.byref(t), C.byref(cam) if cam is not None else None),
-                                  records, width, height, tonemap, out)
+        head = (C.byref(p), C.byref(t), C.byref(cam) if cam is not None else None)
+        if motion is None:
+            return self._records_call("prt_denoise_records_temporal", head, records, width, height, tonemap, out)
+        mp = self._device_ptr(motion, int(width) * int(height) * _capi.MOTION_FLOATS, "prt_denoise_records_temporal_motion")
+        return self._records_call("prt_denoise_records_temporal_motion", head, records, width, height, tonemap, out, extra=(mp,))
 
     def reset_records_history(self):
         self._chk(self.lib.prt_reset_records_history(self.ctx), "prt_reset_records_history")

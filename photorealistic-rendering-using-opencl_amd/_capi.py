@@ -79,6 +79,7 @@ class DenoiseParams(C.Structure):
 PRT_DENOISE_VAR_AUTO, PRT_DENOISE_VAR_STATS, PRT_DENOISE_VAR_SPATIAL = 0, 1, 2
 DENOISE_DEFAULTS = dict(passes=5, sigma_l=3.0, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1)
 DENOISE_RECORD_FLOATS = 16      # PRT_DENOISE_RECORD_FLOATS: one record of prt_export_denoise_inputs / prt_denoise_records
+MOTION_FLOATS = 4               # one pixel of the motion plane {D.x, D.y, D.z, m} (prt_read_motion / prt_export_motion)
 
 
 class TemporalParams(C.Structure):
@@ -128,6 +129,9 @@ PRT_API = [
     ("prt_get_adaptive_report", C.c_int, [C.c_void_p, C.POINTER(AdaptiveReport)]),
     ("prt_render_guides", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_read_guides", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_set_motion", C.c_int, [C.c_void_p, C.c_int]),
+    ("prt_read_motion", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_export_motion", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_denoise", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]),
     ("prt_denoise_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]),
     ("prt_read_history", C.c_int, [C.c_void_p, C.c_void_p]),
@@ -136,6 +140,8 @@ PRT_API = [
     ("prt_denoise_records", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_denoise_records_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(Camera), C.c_int, C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_denoise_records_temporal_motion", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(Camera), C.c_int,
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_reset_records_history", C.c_int, [C.c_void_p]),
     ("prt_read_records_history", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("prt_set_pixel_filter", C.c_int, [C.c_void_p, C.c_uint32, C.c_float]),

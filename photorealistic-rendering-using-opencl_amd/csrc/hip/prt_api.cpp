@@ -147,6 +147,15 @@ struct prt_ctx {
     void* d_stage_vtx = nullptr; void* d_stage_nrm = nullptr;
     bool refit_ready = false;                      // the device tables are there
     bool refitted = false;                         // an update has run since the upload: d_refit_root holds the root's box
+    // prt_set_motion: d_tri_prev the triangle records (48 bytes per slot) as they were before the first update since the last guide render
+    // (allocated by that update, freed with the scene and when motion is turned off); snap_valid: such a snapshot is pending -- the next
+    // prt_render_guides consumes it.  d_motion the motion plane of the frame part (one float4 {D, m} per pixel, allocated on first use,
+    // freed with the frame); motion_valid: it was written by the guide render that made guides_valid
+    bool motion = false;
+    void* d_tri_prev = nullptr;
+    bool snap_valid = false;
+    float4* d_motion = nullptr;
+    bool motion_valid = false;
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -237,6 +246,8 @@ static void free_frame(prt_ctx* c) {
     p = c->d_dn_g; free_dev(p); c->d_dn_g = nullptr;
     p = c->d_hist; free_dev(p); c->d_hist = nullptr;
     p = c->d_hist_guides; free_dev(p); c->d_hist_guides = nullptr;
+    p = c->d_motion; free_dev(p); c->d_motion = nullptr;
+    c->motion_valid = false;
     c->guides_valid = false;
     c->hist_valid = false;
     for (int j = 0; j < prt_ctx::MAX_SUB; ++j) {
@@ -250,6 +261,8 @@ static void free_scene(prt_ctx* c) {
     free_dev(c->d_spheres); free_dev(c->d_quads); free_dev(c->d_sdfs); free_dev(c->d_mats); free_dev(c->d_light_tab);
     free_dev(c->d_slot_vtx); free_dev(c->d_level_pairs); free_dev(c->d_refit_root); free_dev(c->d_stage_vtx); free_dev(c->d_stage_nrm);
     c->refit_ready = c->refitted = false;
+    free_dev(c->d_tri_prev);
+    c->snap_valid = false;
 }
 
 extern "C" void prt_destroy(prt_ctx* c) {
@@ -311,6 +324,8 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     // (the refit tables and staging buffers are the old tree's: a static scene holds none on the device)
     free_dev(c->d_slot_vtx); free_dev(c->d_level_pairs); free_dev(c->d_refit_root); free_dev(c->d_stage_vtx); free_dev(c->d_stage_nrm);
     c->refit_ready = c->refitted = false;
+    free_dev(c->d_tri_prev);                         // (the snapshot is the old scene's: no motion across an upload)
+    c->snap_valid = false;
     c->slot_vtx.swap(ps.slot_vtx); c->level_pairs.swap(ps.level_pairs); c->level_first.swap(ps.level_first); c->node_box.swap(ps.node_box);
     std::memcpy(c->root_bounds, ps.root_bounds, sizeof(c->root_bounds));
     c->n_tris = s->triangle_count; c->n_nodes = s->triangle_count ? s->bvh_node_count : 0u;
@@ -384,6 +399,15 @@ extern "C" int prt_update_vertices_device(prt_ctx* c, const void* d_vertices, co
     HIPCHK(c, hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (bad) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_update_vertices: a vertex with a non-finite x, y or z (the scene is unchanged)");
+    // motion (prt.h prt_set_motion): the records as they are go to the snapshot before the refit overwrites them -- unless one is pending
+    // already: of several updates between two guide renders the oldest geometry is the one the motion plane is measured from.  Every
+    // refusal is behind us (an allocation failure here still leaves the scene as it was)
+    if (c->motion && !c->snap_valid) {
+        const size_t snap_bytes = (c->slot_vtx.empty() ? 1 : c->slot_vtx.size()) * sizeof(TriGeom);
+        if (!c->d_tri_prev) HIPCHK(c, hipMalloc(&c->d_tri_prev, snap_bytes));
+        HIPCHK(c, hipMemcpyAsync(c->d_tri_prev, c->d_tri_geom, snap_bytes, hipMemcpyDeviceToDevice, c->stream));
+        c->snap_valid = true;
+    }
     RefitTables t;
     t.slot_vtx = static_cast<const uint32_t*>(c->d_slot_vtx); t.n_slots = c->slot_vtx.size();
     t.level_pairs = static_cast<const uint32_t*>(c->d_level_pairs);
@@ -958,11 +982,70 @@ extern "C" int prt_render_guides(prt_ctx* c, uint32_t samples) {
     if (samples < 1 || samples > 64) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_guides: samples must be 1 .. 64");
     HIPCHK(c, hipSetDevice(c->device));
     c->guides_valid = false;
+    c->motion_valid = false;
     if (!c->d_guides) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_guides), c->npix * 2 * sizeof(float4)));
-    launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides, c->stream);
+    if (c->motion && !c->d_motion) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_motion), c->npix * sizeof(float4)));
+    const bool snap = c->motion && c->snap_valid && c->d_tri_prev;
+    // the motion instances only where there is a snapshot to measure from; no update since the last guide render: the plain kernels and a
+    // plane of zeros
+    if (snap) launch_guides_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides,
+                                   static_cast<const TriGeom*>(c->d_tri_prev), c->d_motion, c->stream);
+    else launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides, c->stream);
     HIPCHK(c, hipGetLastError());
+    if (c->motion && !snap) HIPCHK(c, hipMemsetAsync(c->d_motion, 0, c->npix * sizeof(float4), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->guides_valid = true;
+    if (c->motion) {
+        c->snap_valid = false;                         // consumed: the next plane is measured from the geometry these guides saw
+        c->motion_valid = true;
+    }
+    return PRT_OK;
+}
+
+// ---- motion of deforming geometry (prt.h prt_set_motion) ---------------------------------------------------------------------------------------
+extern "C" int prt_set_motion(prt_ctx* c, int enable) {
+    CTX_CHECK(c);
+    if (enable && c->cfg.view_option != PRT_VIEW_RESULTS) return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_motion: a debug view has no denoiser to carry motion into");
+    if ((enable != 0) == c->motion) return PRT_OK;     // (unchanged: a per-frame call costs nothing and keeps the guides)
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->motion = enable != 0;
+    c->guides_valid = false;                           // (both histories are kept, as by prt_set_camera)
+    c->motion_valid = false;
+    if (!c->motion) {
+        free_dev(c->d_tri_prev);
+        c->snap_valid = false;
+    }
+    return PRT_OK;
+}
+
+static int motion_ready(prt_ctx* c, const char* who) {
+    const std::string w(who);
+    if (!c->motion) return fail(c, PRT_ERR_NOT_READY, w + ": motion is off (prt_set_motion)");
+    if (!c->guides_valid || !c->motion_valid || !c->d_motion)
+        return fail(c, PRT_ERR_NOT_READY, w + ": no guides with a motion plane for this scene, camera, map and frame (prt_render_guides)");
+    return PRT_OK;
+}
+
+extern "C" int prt_read_motion(prt_ctx* c, float* out4) {
+    CTX_CHECK(c);
+    if (!out4 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_motion: bad arguments");
+    int rc = motion_ready(c, "prt_read_motion");
+    if (rc) return rc;
+    if ((rc = prt_synchronize(c))) return rc;
+    HIPCHK(c, hipMemcpy(out4, c->d_motion, c->npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+extern "C" int prt_export_motion(prt_ctx* c, void* device_motion) {
+    CTX_CHECK(c);
+    if (!device_motion || !aligned16(device_motion) || !c->have_size)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_export_motion: bad arguments (a 16-byte aligned device pointer, a context with a frame size)");
+    int rc = motion_ready(c, "prt_export_motion");
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(device_motion, c->d_motion, c->npix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    if (c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));       // (as prt_export_denoise_inputs)
     return PRT_OK;
 }
 
@@ -1080,8 +1163,10 @@ extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatia
     h.cn = half_next; h.m = half_next + c->npix;
     float4* out = c->d_dn + 2 * c->npix;
     c->hist_valid = false;                         // (until the call has run: a failure leaves the history empty)
+    // the context's motion plane when motion is on and the plane is the valid guides' own (prt.h)
+    const float4* motion = (c->motion && c->motion_valid) ? c->d_motion : nullptr;
     launch_denoise_temporal(c->fb, c->S.q4, c->d_adapt, spatial_var, c->d_guides, c->width, c->rows, p, t, c->cam, h, c->d_dn,
-                            c->d_dn + c->npix, c->d_dn_g, out, c->stream);
+                            c->d_dn + c->npix, c->d_dn_g, out, c->stream, motion);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->d_hist_guides, c->d_guides, c->npix * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1152,11 +1237,11 @@ static int records_output(prt_ctx* c, const float4* out, int W, int H, void* dev
     return PRT_OK;
 }
 
-// prt_denoise_records (t, cam null) and prt_denoise_records_temporal
+// prt_denoise_records (t, cam null) and prt_denoise_records_temporal (device_motion: null, or prt_denoise_records_temporal_motion's plane)
 static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params& p, const prt_temporal_params* t, const prt_camera* cam, int W,
-                           int H, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8) {
+                           int H, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8, const void* device_motion = nullptr) {
     const std::string w(who);
-    if (W < 1 || H < 1 || !device_records || !aligned16(device_records) || (device_rgba && !aligned16(device_rgba)))
+    if (W < 1 || H < 1 || !device_records || !aligned16(device_records) || (device_rgba && !aligned16(device_rgba)) || !aligned16(device_motion))
         return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": needs width >= 1, height >= 1 and 16-byte aligned device pointers (records not null)");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = (size_t)W * (size_t)H;
@@ -1213,7 +1298,7 @@ static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params
     h.cn_prev = half_prev; h.m_prev = half_prev + npix; h.guides_prev = c->d_rec_hist_guides; h.cam_prev = c->rec_hist_cam; h.valid = c->rec_hist_valid;
     h.cn = half_next; h.m = half_next + npix;
     c->rec_hist_valid = false;                     // (until the call has run: a failure leaves the history empty)
-    launch_denoise_temporal_var(fb, guides, W, H, p, *t, dc, h, buf0, buf1, g, out, c->stream);
+    launch_denoise_temporal_var(fb, guides, W, H, p, *t, dc, h, buf0, buf1, g, out, c->stream, static_cast<const float4*>(device_motion));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->d_rec_hist_guides, guides, npix * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1234,8 +1319,9 @@ extern "C" int prt_denoise_records(prt_ctx* c, const prt_denoise_params* params,
     return denoise_records(c, "prt_denoise_records", p, nullptr, nullptr, width, height, device_records, device_rgba, rgba, rgba8);
 }
 
-extern "C" int prt_denoise_records_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
-                                            int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8) {
+extern "C" int prt_denoise_records_temporal_motion(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal,
+                                                   const prt_camera* cam, int width, int height, const void* device_records,
+                                                   const void* device_motion, void* device_rgba, float* rgba, uint8_t* rgba8) {
     CTX_CHECK(c);
     prt_denoise_params p{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
                          PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
@@ -1243,11 +1329,17 @@ extern "C" int prt_denoise_records_temporal(prt_ctx* c, const prt_denoise_params
     prt_temporal_params t{PRT_TEMPORAL_DEFAULT_ALPHA_COLOR, PRT_TEMPORAL_DEFAULT_ALPHA_MOMENTS, PRT_TEMPORAL_DEFAULT_TAU_Z, PRT_TEMPORAL_DEFAULT_COS_N,
                           PRT_TEMPORAL_DEFAULT_HISTORY_CAP, PRT_TEMPORAL_FEEDBACK_ATROUS};
     if (temporal) t = *temporal;
-    int rc = temporal_param_checks(c, t, "prt_denoise_records_temporal");
-    if (!rc) rc = denoise_param_checks(c, p, "prt_denoise_records_temporal");
+    const char* who = device_motion ? "prt_denoise_records_temporal_motion" : "prt_denoise_records_temporal";
+    int rc = temporal_param_checks(c, t, who);
+    if (!rc) rc = denoise_param_checks(c, p, who);
     if (rc) return rc;
-    if (!cam) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_denoise_records_temporal: null camera");
-    return denoise_records(c, "prt_denoise_records_temporal", p, &t, cam, width, height, device_records, device_rgba, rgba, rgba8);
+    if (!cam) return fail(c, PRT_ERR_INVALID_ARGUMENT, std::string(who) + ": null camera");
+    return denoise_records(c, who, p, &t, cam, width, height, device_records, device_rgba, rgba, rgba8, device_motion);
+}
+
+extern "C" int prt_denoise_records_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
+                                            int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    return prt_denoise_records_temporal_motion(c, spatial, temporal, cam, width, height, device_records, nullptr, device_rgba, rgba, rgba8);
 }
 
 extern "C" int prt_reset_records_history(prt_ctx* c) {

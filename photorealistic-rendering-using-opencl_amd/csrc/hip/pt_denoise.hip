@@ -2,6 +2,7 @@
 // A translation unit of its own: no code object of the render kernels changes with it.
 //
 //   guide_kernel<SDF>   K guide samples per pixel (pt_guides.h), one lane per pixel, 8x8 tiles per 64-lane wave
+//   guide_motion_kernel<SDF>, filtered_guides_motion_kernel   the same, and the motion plane (pt_motion.h; prt.h prt_set_motion)
 //   dn_var_kernel       {rgb, v} per pixel: the framebuffer colour and the luminance variance of its mean (stats plane or 5x5 moments)
 //   dn_gauss_kernel     3x3 Gaussian of v (one per pass)
 //   dn_atrous_kernel    one a-trous pass: 5x5 taps at step 2^i, weights from normal, depth, albedo and luminance; ping-pongs {rgb, v}
@@ -10,14 +11,18 @@
 // ping-pong buffers, framebuffer) stays in the L2 / Infinity Cache, a tap costs three 16-byte loads.
 #include "pt_guides.h"
 #include "pt_launch.h"
+#include "pt_motion.h"
 
 namespace prt {
 using namespace dev;
 
 // ---- guides --------------------------------------------------------------------------------------------------------------------------
 // FILTER: the sample offsets warped by the context's pixel filter (prt.h prt_set_pixel_filter; filtered_guides_kernel)
-template <bool SDF, bool FILTER>
-PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* __restrict__ out) {
+// MOTION: also the motion plane {D, m} of the pixel, from the triangle records before the update(s) (tri_prev: an argument of its own, DevScene
+// is the render kernels' kernarg block) and sc.tri_geom; the eight guide floats are the other instances' bit for bit
+template <bool SDF, bool FILTER, bool MOTION>
+PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* __restrict__ out,
+                        const TriGeom* __restrict__ tri_prev, float4* __restrict__ motion) {
     const int tiles_x = (fa.width + 7) / 8;
     const int lane = threadIdx.x & 63;
     const int lx = (int)(blockIdx.x % (unsigned)tiles_x) * 8 + (lane & 7);
@@ -31,6 +36,7 @@ PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArg
     f3 albedo = splat(0.0f), nsum = splat(0.0f);
     float zsum = 0.0f;
     unsigned hits = 0;
+    MotionSum msum = motion_sum_begin();
     for (unsigned s = 0; s < samples; ++s) {
         float fx, fy;
         guide_offsets(s, fx, fy);
@@ -46,6 +52,8 @@ PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArg
             ++hits;
             zsum = zsum + g.depth;
             if (dot(g.normal, g.normal) == dot(g.normal, g.normal)) nsum = nsum + g.normal;     // (a degenerate mesh normal is NaN: left out)
+            if constexpr (MOTION)
+                if (g.direct_triangle) motion_sum_add(msum, motion_displacement(tri_prev, sc.tri_geom, g.slot, g.u, g.v));
         }
     }
     const float inv_k = 1.0f / (float)samples;
@@ -54,35 +62,69 @@ PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArg
     const size_t id = (size_t)ly * (size_t)fa.width + (size_t)lx;
     out[2 * id] = make_float4(albedo.x * inv_k, albedo.y * inv_k, albedo.z * inv_k, (float)hits * inv_k);
     out[2 * id + 1] = make_float4(n.x, n.y, n.z, hits ? zsum / (float)hits : 0.0f);
+    if constexpr (MOTION) {
+        const MotionQuad m = motion_pixel(msum, hits, samples);
+        motion[id] = make_float4(m.x, m.y, m.z, m.w);
+    }
 }
 template <bool SDF>
 __global__ __launch_bounds__(64) void guide_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
                                                    float4* __restrict__ out) {
-    guide_pixel<SDF, false>(sc, cam, fa, samples, out);
+    guide_pixel<SDF, false, false>(sc, cam, fa, samples, out, nullptr, nullptr);
 }
 // under a pixel filter (no SDF build: prt_set_pixel_filter refuses SDF scenes)
 __global__ __launch_bounds__(64) void filtered_guides_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
                                                           float4* __restrict__ out) {
-    guide_pixel<false, true>(sc, cam, fa, samples, out);
+    guide_pixel<false, true, false>(sc, cam, fa, samples, out, nullptr, nullptr);
+}
+// the motion instances: plain, SDF, pixel filter
+template <bool SDF>
+__global__ __launch_bounds__(64) void guide_motion_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
+                                                          float4* __restrict__ out, const TriGeom* __restrict__ tri_prev,
+                                                          float4* __restrict__ motion) {
+    guide_pixel<SDF, false, true>(sc, cam, fa, samples, out, tri_prev, motion);
+}
+__global__ __launch_bounds__(64) void filtered_guides_motion_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
+                                                                    float4* __restrict__ out, const TriGeom* __restrict__ tri_prev,
+                                                                    float4* __restrict__ motion) {
+    guide_pixel<false, true, true>(sc, cam, fa, samples, out, tri_prev, motion);
 }
 
-template <bool SDF, bool FILTER>
-static void launch_guides_t(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream) {
+// one launcher for the plain and the motion instances (MOTION: tri_prev and motion are the two further kernel arguments)
+template <bool SDF, bool FILTER, bool MOTION>
+static void launch_guides_t(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                            float4* motion, hipStream_t stream) {
     const size_t lds = (size_t)sc.stack_levels * 64 * sizeof(unsigned);
     static size_t lds_attr = 0;
-    const void* k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_kernel) : reinterpret_cast<const void*>(&guide_kernel<SDF>);
+    const void* k;
+    if constexpr (MOTION) k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_motion_kernel) : reinterpret_cast<const void*>(&guide_motion_kernel<SDF>);
+    else k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_kernel) : reinterpret_cast<const void*>(&guide_kernel<SDF>);
     if (lds > 65536u && lds > lds_attr) {
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         lds_attr = lds;
     }
     const unsigned tiles = (unsigned)(((fa.width + 7) / 8) * ((fa.rows + 7) / 8));
-    if constexpr (FILTER) hipLaunchKernelGGL(filtered_guides_kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
-    else hipLaunchKernelGGL((guide_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
+    if constexpr (MOTION) {
+        if constexpr (FILTER) hipLaunchKernelGGL(filtered_guides_motion_kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, motion);
+        else hipLaunchKernelGGL((guide_motion_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, motion);
+    } else {
+        if constexpr (FILTER) hipLaunchKernelGGL(filtered_guides_kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
+        else hipLaunchKernelGGL((guide_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
+    }
+}
+template <bool MOTION>
+static void launch_guides_m(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                            float4* motion, hipStream_t stream) {
+    if (fa.filter_kind != PRT_FILTER_NONE) launch_guides_t<false, true, MOTION>(sc, cam, fa, samples, out, tri_prev, motion, stream);
+    else if (sc.n_sdfs) launch_guides_t<true, false, MOTION>(sc, cam, fa, samples, out, tri_prev, motion, stream);
+    else launch_guides_t<false, false, MOTION>(sc, cam, fa, samples, out, tri_prev, motion, stream);
 }
 void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream) {
-    if (fa.filter_kind != PRT_FILTER_NONE) launch_guides_t<false, true>(sc, cam, fa, samples, out, stream);
-    else if (sc.n_sdfs) launch_guides_t<true, false>(sc, cam, fa, samples, out, stream);
-    else launch_guides_t<false, false>(sc, cam, fa, samples, out, stream);
+    launch_guides_m<false>(sc, cam, fa, samples, out, nullptr, nullptr, stream);
+}
+void launch_guides_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                          float4* motion, hipStream_t stream) {
+    launch_guides_m<true>(sc, cam, fa, samples, out, tri_prev, motion, stream);
 }
 
 // ---- the filter ----------------------------------------------------------------------------------------------------------------------

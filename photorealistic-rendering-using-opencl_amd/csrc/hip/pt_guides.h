@@ -56,9 +56,10 @@ PT_DEV Ray guide_cam_ray(int cx, int cy, int width, int height, const DevCamera&
     return guide_cam_ray_at(cx, cy, width, height, cam, fx - 0.5f, fy - 0.5f, lx, ly);
 }
 
-// closest hit of `ray` against the whole scene: the tree walked to its end, then finish_closest.  Out: ray.t / pos / normal / backside
+// closest hit of `ray` against the whole scene: the tree walked to its end, then finish_closest.  Out: ray.t / pos / normal / backside,
+// and th: the tree's closest triangle (the hit itself when mesh_id comes out -1 and the ray hit)
 template <bool SDF>
-PT_DEV bool guide_trace(const DevScene& sc, Ray& ray, const TravStack& stk, int& mesh_id) {
+PT_DEV bool guide_trace(const DevScene& sc, Ray& ray, const TravStack& stk, int& mesh_id, TriHit& th) {
     const RayPre p = ray_pre(ray);
     WalkState w;
     walk_begin(sc, false, ray, PT_INF, p, w, stk);
@@ -68,6 +69,7 @@ PT_DEV bool guide_trace(const DevScene& sc, Ray& ray, const TravStack& stk, int&
     }
     TravRes r;
     r.found = w.found; r.t = w.t; r.th.u = w.u; r.th.v = w.v; r.th.slot = w.slot;
+    th = r.th;
     return finish_closest<SDF>(sc, ray, r, mesh_id);
 }
 
@@ -75,19 +77,23 @@ PT_DEV f3 clamp01(f3 c) {
     return F3(prt_fmin(prt_fmax(c.x, 0.0f), 1.0f), prt_fmin(prt_fmax(c.y, 0.0f), 1.0f), prt_fmin(prt_fmax(c.z, 0.0f), 1.0f));
 }
 
-struct GuideSample { f3 albedo, normal; float depth; bool hit; };
+// direct_triangle: the hit that gives the values is the ray's FIRST (no delta event before it) and a mesh triangle (the one that wins
+// finish_closest: mesh_id == -1); then {slot, u, v} name it (prt.h prt_set_motion: the samples that carry motion)
+struct GuideSample { f3 albedo, normal; float depth; bool hit; unsigned slot; float u, v; bool direct_triangle; };
 
 // one guide sample along `ray` (prt.h: the delta chain, the per-hit values, the miss)
 template <bool SDF>
 PT_DEV GuideSample guide_sample(const DevScene& sc, Ray ray, const TravStack& stk) {
     GuideSample g;
     g.normal = splat(0.0f); g.depth = 0.0f; g.hit = false;
+    g.slot = 0u; g.u = 0.0f; g.v = 0.0f; g.direct_triangle = false;
     f3 tint = splat(1.0f);
     float dist = 0.0f;
     for (int events = 0;; ++events) {
         ray.normal = splat(0.0f);
         int mid;
-        if (!guide_trace<SDF>(sc, ray, stk, mid)) {
+        TriHit th;
+        if (!guide_trace<SDF>(sc, ray, stk, mid, th)) {
             g.albedo = tint * clamp01(env_lookup(sc, ray.dir));
             return g;
         }
@@ -100,6 +106,8 @@ PT_DEV GuideSample guide_sample(const DevScene& sc, Ray ray, const TravStack& st
             g.normal = dot(ray.normal, ray.dir) > 0.0f ? -ray.normal : ray.normal;
             g.depth = dist;
             g.hit = true;
+            g.direct_triangle = events == 0 && mid == -1;
+            g.slot = th.slot; g.u = th.u; g.v = th.v;
             return g;
         }
         const f3 n = ray.normal;                                  // the shading normal as finish_closest leaves it (what bsdf sampling frames)

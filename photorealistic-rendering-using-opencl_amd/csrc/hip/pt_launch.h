@@ -52,6 +52,10 @@ void launch_live_list(const DevState& S, size_t n, unsigned max_spp, uint32_t* w
 // {normal, depth}).  prt_denoise: the filter of prt.h on the full frame W x H, out = filtered rgba (alpha of fb); buf0 / buf1: W x H float4,
 // g: W x H float of scratch
 void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream);
+// ... and the motion plane (prt.h prt_set_motion; one float4 {D, m} per pixel) from tri_prev, the triangle records (one per slot, as
+// sc.tri_geom) of the geometry before the update(s): the motion instances of the guide kernels
+void launch_guides_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                          float4* motion, hipStream_t stream);
 void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                     const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
 // ... its pieces: dn_var_kernel's {rgb, v} into out; a-trous pass i (step 2^i, its Gaussian into g first) from `in` into `out`, with the
@@ -59,7 +63,8 @@ void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool
 void launch_denoise_var(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, int W, int H, float4* out, hipStream_t stream);
 void launch_denoise_pass(const float4* in, const float4* guides, int W, int H, const prt_denoise_params& p, unsigned i, float* g,
                          const float4* alpha_src, float4* out, hipStream_t stream);
-// pt_temporal.hip.  prt_denoise_temporal: the previous call's history (read) and the halves this call writes; `valid` false = empty history
+// pt_temporal.hip.  prt_denoise_temporal: the previous call's history (read) and the halves this call writes; `valid` false = empty history.
+// motion (both launchers): null, or the motion plane of `guides` (W x H float4 {D, m}, device)
 struct TemporalHistory {
     const float4* cn_prev;          // {c.rgb, n} per pixel
     const float4* m_prev;           // {m1, m2, v, 0}
@@ -71,11 +76,11 @@ struct TemporalHistory {
 };
 void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                              const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
-                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
+                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream, const float4* motion = nullptr);
 // ... everything behind its variance step: buf1 holds the frame's {rgb, v} (dn_var_kernel's output, or a caller's) on entry
 void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, int H, const prt_denoise_params& p, const prt_temporal_params& t,
                                  const DevCamera& cam, const TemporalHistory& h, float4* buf0, float4* buf1, float* g, float4* out,
-                                 hipStream_t stream);
+                                 hipStream_t stream, const float4* motion = nullptr);
 // pt_records.hip.  prt_export_denoise_inputs: the records (prt.h: 4 float4 per pixel) of a W x rows frame part; adapt null = no stats
 // (v = 0, has_stats = 0).  prt_denoise_records: W x H records into the planes the filter reads -- fb {c, alpha}, guides (2 float4 per
 // pixel), var {c, v of the record} -- and 1 into *no_stats if any record has has_stats != 1 (the caller zeroes the word first)

@@ -36,11 +36,14 @@ PT_DEV float tm_grad1(const float4* __restrict__ gd, int x, int y, int sx, int s
 
 // fb: framebuffer; var: dn_var_kernel's {c, v} of the current frame (v for n < 4); gd / gd_prev: current / previous guides (2 float4 per
 // pixel); h_cn_prev / h_m_prev: previous history {c, n} / {m1, m2, v, 0}.  Out: {c_i, v} and the new history.
+// motion: null, or the motion plane {D, m} of the current guides (prt.h prt_set_motion): a covered pixel with m > 0 and D != 0 reprojects
+// X + D, where its surface point was, instead of X; every other pixel -- and so a plane of zeros -- takes today's expressions
 __global__ __launch_bounds__(256) void tm_reproject_kernel(const float4* __restrict__ fb, const float4* __restrict__ var,
                                                            const float4* __restrict__ gd, const float4* __restrict__ gd_prev,
                                                            const float4* __restrict__ h_cn_prev, const float4* __restrict__ h_m_prev,
                                                            const DevCamera cur, const DevCamera prev, int W, int H, const TmParams P,
-                                                           float4* __restrict__ out, float4* __restrict__ h_cn, float4* __restrict__ h_m) {
+                                                           float4* __restrict__ out, float4* __restrict__ h_cn, float4* __restrict__ h_m,
+                                                           const float4* __restrict__ motion) {
     const int x = (int)(blockIdx.x * 16 + threadIdx.x), y = (int)(blockIdx.y * 16 + threadIdx.y);
     if (x >= W || y >= H) return;
     const size_t id = (size_t)y * W + x;
@@ -58,7 +61,12 @@ __global__ __launch_bounds__(256) void tm_reproject_kernel(const float4* __restr
         const f3 d = normalize(onPlane - position);
         const f3 Pp = ld3(prev.position), Hz = ld3(prev.horizontal), Vt = ld3(prev.vertical);
         const f3 f = ld3(prev.middle) - Pp;
-        const f3 e = covp ? (position + d * np.w) - Pp : d;
+        f3 X = position + d * np.w;
+        if (motion && covp) {
+            const float4 mv = motion[id];
+            if (mv.w > 0.0f && (mv.x != 0.0f || mv.y != 0.0f || mv.z != 0.0f)) X = X + F3(mv.x, mv.y, mv.z);
+        }
+        const f3 e = covp ? X - Pp : d;
         const float dist = covp ? length(e) : 0.0f;
         const float ef = dot(e, f);
         if (ef > 0.0f) {
@@ -126,20 +134,20 @@ __global__ __launch_bounds__(256) void tm_feedback_kernel(const float4* __restri
 
 void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                              const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
-                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream) {
+                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream, const float4* motion) {
     launch_denoise_var(fb, q4, adapt, spatial, W, H, buf1, stream);
-    launch_denoise_temporal_var(fb, guides, W, H, p, t, cam, h, buf0, buf1, g, out, stream);
+    launch_denoise_temporal_var(fb, guides, W, H, p, t, cam, h, buf0, buf1, g, out, stream, motion);
 }
 
 void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, int H, const prt_denoise_params& p, const prt_temporal_params& t,
                                  const DevCamera& cam, const TemporalHistory& h, float4* buf0, float4* buf1, float* g, float4* out,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, const float4* motion) {
     const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
     TmParams P;
     P.alpha_color = t.alpha_color; P.alpha_moments = t.alpha_moments; P.tau_z = t.tau_z; P.cos_n = t.cos_n; P.cap = (float)t.history_cap;
     P.has_hist = h.valid ? 1 : 0;
     hipLaunchKernelGGL(tm_reproject_kernel, grd, blk, 0, stream, fb, buf1, guides, h.guides_prev, h.cn_prev, h.m_prev, cam, h.cam_prev, W, H,
-                       P, buf0, h.cn, h.m);
+                       P, buf0, h.cn, h.m, motion);
     float4* cur = buf0;
     float4* nxt = buf1;
     for (unsigned i = 0; i < p.passes; ++i) {

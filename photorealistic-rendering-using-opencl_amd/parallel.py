@@ -11,6 +11,8 @@ the expensive middle of the picture.
 """
 import numpy as np
 
+from ._capi import DENOISE_RECORD_FLOATS as RECORD_FLOATS, MOTION_FLOATS
+
 BLOCK_ROWS = 16
 
 
@@ -51,16 +53,32 @@ def merge_on_rank0(tile, height, width, world, dist):
     return gather_rows_on_rank0(tile, height, width, world, dist)
 
 
-def denoise_on_rank0(renderer, height, width, world, dist, cam=None, temporal=False, **params):
+def pack_motion_tile(records, motion):
+    """(rows, width, 16) records and (rows, width, 4) motion -> ONE (rows, width, 20) tile: what a rank sends when the motion plane travels
+    with the records, so that there is still exactly one collective"""
+    import torch
+    return torch.cat([records, motion], dim=-1).contiguous()
+
+
+def split_motion_tile(full):
+    """the gathered (height, width, 20) tile -> the two contiguous buffers the filter reads: (height, width, 16) records, (height, width, 4) motion"""
+    return full[..., :RECORD_FLOATS].contiguous(), full[..., RECORD_FLOATS:RECORD_FLOATS + MOTION_FLOATS].contiguous()
+
+
+def denoise_on_rank0(renderer, height, width, world, dist, cam=None, temporal=False, motion=False, **params):
     """The denoised frame of a render dealt over `world` ranks in row blocks (prt_set_row_blocks(width, height, BLOCK_ROWS, world, rank) on
     every rank, rendered, guides rendered): every rank exports its records (Renderer.export_denoise_inputs) into a
     (max_rows_per_rank, width, 16) tensor, ONE collective gathers them to rank 0 -- instead of the framebuffer's gather, not on top of it -- and
     rank 0's context filters the whole frame (Renderer.denoise_records, or with temporal=True denoise_records_temporal with `cam`, the frame's
-    camera).  params: the keywords of Renderer.denoise / denoise_temporal.  Returns the (height, width, 4) float32 tensor on rank 0's device,
+    camera).  motion=True (needs temporal=True and Renderer.set_motion on every rank): every rank also exports its motion plane
+    (Renderer.export_motion) and sends both as one (rows, width, 20) tile -- still one collective --, which rank 0 splits into the two
+    contiguous buffers of prt_denoise_records_temporal_motion.  params: the keywords of Renderer.denoise / denoise_temporal.  Returns the (height, width, 4) float32 tensor on rank 0's device,
     None on the other ranks.  The bits are those of prt_denoise on one whole-frame context."""
     import torch
     if temporal and cam is None:
         raise ValueError("denoise_on_rank0: temporal=True needs the frame's camera")
+    if motion and not temporal:
+        raise ValueError("denoise_on_rank0: motion=True needs temporal=True (the motion plane feeds the reprojection)")
     rank = dist.get_rank() if (world > 1 and dist is not None and dist.is_initialized()) else 0
     device = torch.device("cuda", torch.cuda.current_device())
     tile = torch.zeros((max_rows_per_rank(height, world), width, 16), dtype=torch.float32, device=device)
@@ -69,13 +87,22 @@ def denoise_on_rank0(renderer, height, width, world, dist, cam=None, temporal=Fa
     # side starts behind the other's finished work
     torch.cuda.current_stream().synchronize()
     renderer.export_denoise_inputs(tile)
+    if motion:
+        mtile = torch.zeros((tile.shape[0], width, MOTION_FLOATS), dtype=torch.float32, device=device)
+        renderer.export_motion(mtile)
     renderer.synchronize()
+    if motion:
+        tile = pack_motion_tile(tile, mtile)
+        torch.cuda.current_stream().synchronize()
     records = gather_rows_on_rank0(tile, height, width, world, dist)
     if rank != 0:
         return None
+    plane = None
+    if motion:
+        records, plane = split_motion_tile(records)
     records = records.contiguous()
     torch.cuda.current_stream().synchronize()
     out = torch.empty((height, width, 4), dtype=torch.float32, device=device)
     if temporal:
-        return renderer.denoise_records_temporal(records, width, height, cam, out=out, **params)
+        return renderer.denoise_records_temporal(records, width, height, cam, out=out, motion=plane, **params)
     return renderer.denoise_records(records, width, height, out=out, **params)

@@ -9,6 +9,10 @@ Per scene (the teapot of cornell_coat and the 871 k-triangle stand-in of BASELIN
                      SAH build) plus prt_upload_scene
   refit_upload       the parent's cheaper path: the caller's nodes refitted in numpy (vectorised, by value) plus prt_upload_scene alone
 and bvh_cost (SAH, package helper) of the refitted tree against the rebuilt one per deformation.
+With --phase motion (prt_set_motion): what the motion mode adds, two contexts (motion on / off) timed alternately, call by call, medians over
+--calls rounds: an update with and without the snapshot copy (a small guide render between the timed calls consumes the snapshot, so every
+timed update of the "on" arm takes one), prt_render_guides (4 samples) at 1920x1080 with the motion instance and with the plain one, and
+prt_denoise_temporal with and without the plane.
 Kernel times: from `rocprofv3 --kernel-trace --stats` in a run of its own (this script with --phase kernels).  One JSON document on stdout
 (and into --out).
 
@@ -162,6 +166,59 @@ def measure(prt, name, calls):
     return out
 
 
+def motion_phase(prt, name, rounds, width=1920, height=1080):
+    """the cost of prt_set_motion on scene `name`: {update, guides, temporal} x {off, on}, arms alternated within every round"""
+    import torch
+    scene = _scene(prt, name)
+    a = prt.scene_arrays(scene.desc)
+    v0, n0 = a["vertices"].copy(), a["normals"].copy()
+    cfg = scene.config()
+    cam = prt.default_camera(width, height)
+    dn = torch.from_numpy(n0).cuda()
+    dv = [torch.from_numpy(deform(v0, 0.01, phase=0.05 * k)).cuda() for k in range(2)]
+    torch.cuda.synchronize()
+    arms = {}
+    for arm in ("off", "on"):
+        small, big = prt.Renderer(cfg, device=0), prt.Renderer(cfg, device=0)
+        for r, (w, h) in ((small, (64, 48)), (big, (width, height))):
+            r.upload_scene(scene)
+            r.set_camera(prt.default_camera(w, h))
+            r.resize(w, h)
+            r.set_motion(arm == "on")
+            r.update_vertices(dv[0], dn)                                   # (the first update uploads the tables and allocates the snapshot)
+            r.render_guides(1)
+        big.reset()
+        big.render_spp(1, prt.seed_pairs(4 * max(cfg.max_bounces, 8) + 64))
+        arms[arm] = (small, big)
+    t = {k: {"off": [], "on": []} for k in ("update", "guides", "temporal")}
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        fn()
+        return 1e3 * (time.perf_counter() - t0)
+    for k in range(rounds + 2):
+        for arm in (("off", "on") if k % 2 == 0 else ("on", "off")):
+            small, big = arms[arm]
+            small.render_guides(1)                                         # consumes a pending snapshot: the timed update takes a fresh one
+            ms_u = timed(lambda: small.update_vertices(dv[k % 2], dn))
+            big.update_vertices(dv[k % 2], dn)
+            ms_g = timed(lambda: big.render_guides(4))
+            ms_t = timed(lambda: big.denoise_temporal())
+            if k >= 2:                                                     # (two warm-up rounds: allocations, first launches)
+                t["update"][arm].append(ms_u); t["guides"][arm].append(ms_g); t["temporal"][arm].append(ms_t)
+    moving = float((np.abs(arms["on"][1].read_motion()[..., :3]).max(-1) > 0).mean())
+    for small, big in arms.values():
+        small.close()
+        big.close()
+    out = {"triangles": int(scene.desc.triangle_count), "frame": [width, height], "rounds": rounds, "guide_samples": 4,
+           "pixels_with_motion": round(moving, 4), "snapshot_bytes": 48 * int(scene.desc.triangle_count)}
+    for k, arms_t in t.items():
+        out[k] = {arm: {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(min(v)), 4), "max_ms": round(float(max(v)), 4)}
+                  for arm, v in arms_t.items()}
+        out[k]["on_minus_off_median_ms"] = round(out[k]["on"]["median_ms"] - out[k]["off"]["median_ms"], 4)
+    return out
+
+
 def kernels_phase(prt, names):
     """the launches rocprofv3 times: KERNEL_CALLS device updates (with normals) per scene"""
     import torch
@@ -215,7 +272,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="cornell_coat,cornell_dragon")
     ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--phase", default="all", choices=["all", "rates", "kernels"])
+    ap.add_argument("--phase", default="all", choices=["all", "rates", "kernels", "motion"])
     ap.add_argument("--rocprof-timeout", type=int, default=300)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -223,6 +280,14 @@ def main():
     names = a.scenes.split(",")
     if a.phase == "kernels":
         kernels_phase(prt, names)
+        return
+    if a.phase == "motion":
+        doc = {"build_id": prt.build_id(), "motion": {name: motion_phase(prt, name, a.calls) for name in names}}
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(text + "\n")
         return
     doc = {"build_id": prt.build_id(), "calls": a.calls, "scenes": {}}
     for name in names:
