@@ -88,9 +88,15 @@ typedef struct prt_config {
                                       * vertex that samples the light (handleSurface, base.cl:168-172) the light-sample strategy is a coin flip
                                       * between LIGHT_INDICES[0] and the ENVIRONMENT MAP, sampled in proportion to its luminance x sin(theta)
                                       * and combined with the BSDF sample by the power heuristic; a BSDF-sampled ray that escapes adds the map
-                                      * with the complementary weight and ends its path in that segment.  The expectation of every pixel is
-                                      * the one of the default mode (a GPU test checks the converged pictures against each other); the random
-                                      * number sequence is not, so this mode has no bit-exact counterpart.  Surfaces only: refused together
+                                      * with the complementary weight and ends its path in that segment.  The expectation of every complete
+                                      * path is the one of the default mode, bounce caps included: a vertex whose counters reset the path
+                                      * (MAX_BOUNCES, MAX_DIFF_BOUNCES, ...) gets no light from the map in the default mode -- its escaped ray
+                                      * would be looked up in a segment that never runs -- and gets none here; the escaped ray's term passes
+                                      * the same Russian roulette.  (Limit: a material whose lobes count against DIFFERENT caps -- coat, rough
+                                      * dielectric -- at a vertex where only one of them is full takes the map sample or not by the lobe its
+                                      * BSDF sample drew; the expectation there is the default's only approximately.)  tests/test_env_sampling.py
+                                      * compares 8 x 8 block means of the two modes; the random
+                                      * number sequence is not the default's, so this mode has no bit-exact counterpart.  Surfaces only: refused together
                                       * with a global medium, SDF primitives, a debug view or pick_random_light. */
 } prt_config;
 
@@ -507,6 +513,20 @@ int prt_read_records_history(prt_ctx* ctx, int width, int height, float* out8);
 int prt_set_pixel_filter(prt_ctx* ctx, uint32_t kind, float radius);
 int prt_pixel_filter_offsets(uint32_t kind, float radius, uint32_t gx, uint32_t gy, uint32_t k0, uint32_t n, float* out2);
 
+/* The sampling density of an environment map under prt_config::env_importance_sampling, as the cumulative tables prt_upload_envmap builds
+ * for the kernels (no counterpart in the reference).  Needs no device and no context.  rgb: w x h float RGB texels, row 0 = the +y pole.
+ *   lum(i, j)  = 0.2126 r + 0.7152 g + 0.0722 b of texel (i, j) in float64; 0 where that is not in (0, 1e30)
+ *   m(i, j)    = the largest lum over the 3 x 3 neighbourhood of (i, j): columns wrap (i - 1 of column 0 is column w - 1), rows clamp
+ *   s(j)       = sin(pi (j + 0.5) / h), the row centre's sin(theta)
+ *   f(i, j)    = m(i, j) s(j) + 0.05 mean(m s) s(j) pi / 2        (the floor: 5 % of the mean, in proportion to the solid angle;
+ *                                                                   a map without a positive texel: f = s(j) pi / 2)
+ *   rows[j]    = sum of f over rows 0 .. j - 1 / sum of f,  j = 0 .. h          (rows[0] = 0, rows[h] = 1)
+ *   cols[j (w + 1) + i] = sum of f(0 .. i - 1, j) / sum of f(., j),  i = 0 .. w   (0 .. 1 in every row)
+ * summed in float64 in index order, each entry rounded to float32.  The density over directions inside texel (i, j), at polar coordinate
+ * v = theta / pi, is (rows[j + 1] - rows[j]) (cols[j][i + 1] - cols[j][i]) w h / (2 pi^2 sin(pi v)): positive wherever the bilinear lookup of
+ * the map can be. */
+int prt_env_cdf(const float* rgb, int w, int h, float* rows /* h + 1 */, float* cols /* h * (w + 1) */);
+
 /* Scheduling knob of the render kernel (no counterpart in the reference; results do not depend on it, tests check
  * that): a wave ends a BVH-walk phase once fewer than `lanes` of its 64 lanes are still walking (and fewer than wait for the
  * phase to end); the lanes cut off resume in the wave's next phase.  1 = every walk runs to its end (lock step).
@@ -612,7 +632,10 @@ int prt_selftest_math(prt_ctx* ctx, int fn, const float* a, const float* b, floa
  * Fresnel, light sampling, medium and phase sampling, camera ray, primitive tests, environment lookup -- fn 1..11, layouts in
  * csrc/hip/pt_selftest.h; fn 12: the pixel filter's offset, params {kind as uint bits, radius}, in {gx, gy, k as uint bits}, out {dx, dy},
  * csrc/hip/pt_filter.hip): 80 floats of shared parameters, 32 floats in and 32 floats out per case.  The known-answer
- * fixtures tests/golden/kat_*.npz hold what the REFERENCE's own functions return on the same cases. */
+ * fixtures tests/golden/kat_*.npz hold what the REFERENCE's own functions return on the same cases.
+ * fn 13 / 14: the environment-map importance sampling (not in the reference) on the map uploaded to a context created with
+ * env_importance_sampling (PRT_ERR_INVALID_ARGUMENT without such a map); params is not read.  fn 13, env_sample: in {xi0, xi1}, out {d.xyz, pdf,
+ * the texel i and j the search chose as uint bits, env_pdf(d), env_lookup(d).rgb}.  fn 14: in a direction, out {env_pdf, env_lookup.rgb}. */
 int prt_selftest_fn(prt_ctx* ctx, int fn, const float* params, const float* in, float* out, int n);
 
 const char* prt_last_error(prt_ctx* ctx);

@@ -22,7 +22,7 @@ REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["PIXEL_FILTERS", "PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["PIXEL_FILTERS", "PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "env_cdf", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -195,6 +195,19 @@ def pixel_filter_offsets(kind, radius, gx, gy, k0, n):
     if rc:
         raise PrtError("prt_pixel_filter_offsets failed (%d): %s" % (rc, load_library().prt_last_global_error().decode()), rc)
     return out
+
+
+def env_cdf(rgb):
+    """prt_env_cdf: the tables prt_upload_envmap builds of a map float32 [h, w, 3] under env_importance_sampling (prt.h): (rows float32 [h + 1],
+    cols float32 [h, w + 1]).  Needs no GPU"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    h, w = rgb.shape[:2]
+    rows, cols = np.zeros(h + 1, dtype=np.float32), np.zeros((h, w + 1), dtype=np.float32)
+    rc = load_library().prt_env_cdf(rgb.ctypes.data_as(C.c_void_p), w, h, rows.ctypes.data_as(C.c_void_p), cols.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise PrtError("prt_env_cdf failed (%d): %s" % (rc, load_library().prt_last_global_error().decode()), rc)
+    return rows, cols
 
 
 def scene_arrays(desc):
@@ -583,7 +596,7 @@ class Renderer:
         return out
 
     def selftest_fn(self, fn, params, cases):
-        """prt_selftest_fn: params = 80 floats, cases = [n, 32] float32 -> [n, 32] float32"""
+        """prt_selftest_fn: params = 80 floats, cases = [n, 32] float32 -> [n, 32] float32 (fn 13 / 14 work on the uploaded map; params unused)"""
         params = np.ascontiguousarray(params, dtype=np.float32)
         cases = np.ascontiguousarray(cases, dtype=np.float32)
         assert params.size == 80 and cases.ndim == 2 and cases.shape[1] == 32

@@ -146,6 +146,7 @@ PRT_API = [
     ("prt_read_records_history", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("prt_set_pixel_filter", C.c_int, [C.c_void_p, C.c_uint32, C.c_float]),
     ("prt_pixel_filter_offsets", C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("prt_env_cdf", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("prt_set_walk_min_lanes", C.c_int, [C.c_void_p, C.c_uint32]),
     ("prt_set_option", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     ("prt_kernel_variant", C.c_char_p, [C.c_void_p]),

@@ -1421,6 +1421,15 @@ extern "C" int prt_pixel_filter_offsets(uint32_t kind, float radius, uint32_t gx
     return PRT_OK;
 }
 
+extern "C" int prt_env_cdf(const float* rgb, int w, int h, float* rows, float* cols) {
+    if (!rgb || !rows || !cols || w <= 0 || h <= 0) { g_global_error = "prt_env_cdf: bad arguments"; return PRT_ERR_INVALID_ARGUMENT; }
+    std::vector<float> r, c;
+    build_env_cdf(rgb, w, h, r, c);
+    std::memcpy(rows, r.data(), r.size() * sizeof(float));
+    std::memcpy(cols, c.data(), c.size() * sizeof(float));
+    return PRT_OK;
+}
+
 extern "C" int prt_set_walk_min_lanes(prt_ctx* c, uint32_t lanes) {
     CTX_CHECK(c);
     if (lanes < 1 || lanes > 64) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_walk_min_lanes: 1..64");
@@ -1604,7 +1613,10 @@ extern "C" int prt_selftest_math(prt_ctx* c, int fn, const float* a, const float
 
 extern "C" int prt_selftest_fn(prt_ctx* c, int fn, const float* params, const float* in, float* out, int n) {
     CTX_CHECK(c);
-    if (!params || !in || !out || n <= 0 || fn < 1 || fn > 12) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: bad arguments");
+    if (!params || !in || !out || n <= 0 || fn < 1 || fn > 14) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: bad arguments");
+    const bool env_fn = fn == 13 || fn == 14;                  // environment importance sampling on the uploaded map (pt_selftest.h selftest_env)
+    if (env_fn && !(c->sc.env_cdf_rows && c->sc.env_cdf_cols && c->d_env))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: fn 13 / 14 need a map uploaded to a context created with env_importance_sampling");
     HIPCHK(c, hipSetDevice(c->device));
     float tab[PT_FILTER_TAB + 1] = {};
     float r = 0.0f;
@@ -1626,6 +1638,7 @@ extern "C" int prt_selftest_fn(prt_ctx* c, int fn, const float* params, const fl
     if (e == hipSuccess && fn == 12) e = hipMemcpy(dtab, tab, sizeof(tab), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         if (fn == 12) launch_selftest_filter(kind, r, kind >= PRT_FILTER_GAUSSIAN ? dtab : nullptr, di, dout, n, c->stream);
+        else if (env_fn) launch_selftest_env(fn, c->sc.env, c->sc.env_w, c->sc.env_h, c->sc.env_cdf_rows, c->sc.env_cdf_cols, di, dout, n, c->stream);
         else launch_selftest_fn(fn, dp, di, dout, n, c->stream);
         e = hipStreamSynchronize(c->stream);
     }

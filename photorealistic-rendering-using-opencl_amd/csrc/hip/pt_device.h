@@ -1308,10 +1308,9 @@ PT_DEV unsigned cdf_find(const float* __restrict__ cdf, unsigned n, float xi) { 
     while (hi - lo > 1u) { const unsigned mid = (lo + hi) >> 1; if (cdf[mid] <= xi) lo = mid; else hi = mid; }
     return lo;
 }
-PT_DEV float env_texel_pdf(const DevScene& sc, unsigned i, unsigned j, float v) {     // density over directions at texel (i, j), polar coordinate v in [0, 1]
+PT_DEV float env_texel_pdf(const DevScene& sc, unsigned i, unsigned j, float sin_theta) {     // density over directions at texel (i, j), at polar angle theta
     const float* cols = sc.env_cdf_cols + (size_t)j * (unsigned)(sc.env_w + 1);
     const float prow = sc.env_cdf_rows[j + 1u] - sc.env_cdf_rows[j], pcol = cols[i + 1u] - cols[i];
-    const float sin_theta = prt_sin(v * PT_PI);
     if (!(sin_theta > 0.0f)) return 0.0f;
     return prow * pcol * (float)sc.env_w * (float)sc.env_h / (2.0f * PT_PI * PT_PI * sin_theta);
 }
@@ -1329,7 +1328,7 @@ PT_DEV EnvSample env_sample(const DevScene& sc, float xi0, float xi1) {
     sincos_pair(phi, sp, cp);
     EnvSample es;
     es.d = F3(st * cp, ct, st * sp);                                                   // the inverse of envMapEquirect
-    es.pdf = env_texel_pdf(sc, i, j, v);
+    es.pdf = env_texel_pdf(sc, i, j, st);
     return es;
 }
 PT_DEV float env_pdf(const DevScene& sc, f3 dir) {
@@ -1338,7 +1337,9 @@ PT_DEV float env_pdf(const DevScene& sc, f3 dir) {
     int i = (int)(cx * (float)sc.env_w), j = (int)(cy * (float)sc.env_h);
     i = i < 0 ? 0 : (i >= sc.env_w ? sc.env_w - 1 : i);
     j = j < 0 ? 0 : (j >= sc.env_h ? sc.env_h - 1 : j);
-    return env_texel_pdf(sc, (unsigned)i, (unsigned)j, cy);
+    // sin(theta) from the direction's own x and z, not as sin(acos(y)): towards the poles acos loses the angle's relative accuracy (6e-8 / theta^2),
+    // and the density of a direction env_sample made would differ from the density it was made with (3e-5 at sin(theta) = 0.03, 1e-3 at 0.006)
+    return env_texel_pdf(sc, (unsigned)i, (unsigned)j, prt_sqrt(dir.x * dir.x + dir.z * dir.z));
 }
 // the density a BSDF sample of direction e.wo was drawn with (LambertBSDF_pdf as the reference compiles it is 0: SURVEY s9-Q7)
 template <unsigned MATS>
@@ -1711,6 +1712,16 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
     if (L.kind == K_SURFACE_MIS) {
         constexpr bool ENVIS = (MATS & PT_MATS_ENVIS) != 0;
         const Mat mat = load_mat<dist_mask<MATS>()>((L.mesh_id + 1) ? &sc.mats[L.mesh_id + 1] : &sc.mats[sc.n_meshes + 1]);
+        // PT_MATS_ENVIS: does the map light this vertex at all?  In the default mode it does so through the BSDF-sampled ray alone, looked up in the
+        // path's next segment -- which a path that this vertex's counters reset (lane_finish_segment's caps, after its increments by
+        // L.sampledLobe) never runs.  Such a vertex gets neither the map sample nor the escaped ray's term, and its light sample is no coin's side
+        bool env_live = false;
+        if (ENVIS) {
+            const unsigned lobe = L.w2_ran ? L.sampledLobe : mat.lobes;      // (no direction sampled: as if every lobe of the material had been)
+            const int diff = (int)L.diff + ((lobe & (PRT_LOBE_DIFFUSE_R | PRT_LOBE_GLOSSY_R)) != 0), spec = (int)L.spec + ((lobe & PRT_LOBE_SPECULAR_R) != 0);
+            const int trans = (int)L.trans + ((lobe & PRT_LOBE_TRANSMISSIVE) != 0);
+            env_live = !(L.total + 1u >= (unsigned)sc.max_bounces || diff >= sc.max_diff_bounces || spec >= sc.max_spec_bounces || trans >= sc.max_trans_bounces);
+        }
         if (L.w2_ran && L.h.didHit) {                                    // the probe ray, base.cl:58-75
             const int mid = L.h.mesh_id;
             const unsigned lbits = mat_bits(sc.mats + (mid + 1));
@@ -1721,13 +1732,20 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
             }
         } else if (ENVIS && L.w2_ran) {
             // the BSDF-sampled ray escapes: the map along it, weighted against the map's own sampling strategy (a mirror direction
-            // cannot be produced by it), and the path ends here instead of in a segment of its own
-            const float w = (L.sampledLobe & PRT_LOBE_SPECULAR) ? 1.0f : power_heuristic(L.pdf, 0.5f * env_pdf(sc, L.dir));
-            L.a = env_lookup(sc, L.dir) * L.weight * w;
+            // cannot be produced by it), and the path ends here instead of in a segment of its own.  The default mode looks the map up in the
+            // path's NEXT segment, which only a path that survives this vertex's Russian roulette and bounce caps has (lane_finish_segment,
+            // pathtracing.cl:97-115): the same roulette and the same caps decide here
             L.terminate = true;
+            float keep = env_live ? 1.0f : 0.0f;
+            const float roulettePdf = fmax3(L.mask * L.weight);
+            if (env_live && L.total + 1u > 2u && roulettePdf < 0.1f) keep = next1D(L.rng) < roulettePdf ? 1.0f / roulettePdf : 0.0f;
+            if (keep > 0.0f) {
+                const float w = (L.sampledLobe & PRT_LOBE_SPECULAR) ? 1.0f : power_heuristic(L.pdf, 0.5f * env_pdf(sc, L.dir));
+                L.a = env_lookup(sc, L.dir) * L.weight * (w * keep);
+            }
         }
         // lightSample, base.cl:79-134 (from ray.pos = the probe ray's hit point: SURVEY s9-Q4)
-        if (ENVIS && next1D(L.rng) < 0.5f) {                             // the light-sample strategy of this vertex is the environment map
+        if (ENVIS && env_live && next1D(L.rng) < 0.5f) {                 // the light-sample strategy of this vertex is the environment map
             const float xi0 = next1D(L.rng), xi1 = next1D(L.rng);
             const EnvSample es = env_sample(sc, xi0, xi1);
             if (es.pdf > 0.0f) {
@@ -1761,7 +1779,7 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
                     if (MEDIUM) contribution = contribution * vexp(splat(sc.fog_sigma_t) * (-1.0f * rec.dist));
                     contribution = contribution * power_heuristic(rec.pdf, bsdf_pdf<MATS>(sc, e, mat));
                     L.vis = contribution / rec.pdf;
-                    if (ENVIS) L.vis = L.vis * 2.0f;                     // (the light was the coin's other side: probability 1 / 2)
+                    if (ENVIS && env_live) L.vis = L.vis * 2.0f;         // (the light was the coin's other side: probability 1 / 2)
                 }
             }
         }

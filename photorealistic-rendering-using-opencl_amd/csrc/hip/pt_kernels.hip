@@ -247,6 +247,19 @@ __global__ void selftest_fn_kernel(int fn, const float* __restrict__ params, con
     for (int k = 0; k < 32; ++k) out[32 * (size_t)i + k] = y[k];
 }
 
+// fn 13 / 14 (pt_selftest.h selftest_env): the environment-map importance sampling on the context's map and tables, one case per lane
+__global__ void selftest_env_kernel(int fn, const float* __restrict__ env, int env_w, int env_h, const float* __restrict__ rows,
+                                    const float* __restrict__ cols, const float* __restrict__ in, float* __restrict__ out, int n) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    DevScene sc = DevScene();
+    sc.env = env; sc.env_w = env_w; sc.env_h = env_h; sc.env_cdf_rows = rows; sc.env_cdf_cols = cols;
+    float x[32], y[32];
+    for (int k = 0; k < 32; ++k) x[k] = in[32 * (size_t)i + k];
+    selftest_env(fn, sc, x, y);
+    for (int k = 0; k < 32; ++k) out[32 * (size_t)i + k] = y[k];
+}
+
 #ifdef PT_POOL_STATS
 void dump_pool_stats() {
     unsigned long long h[32] = {0};
@@ -322,6 +335,9 @@ void launch_selftest_math(int fn, const float* a, const float* b, float* out, in
 }
 void launch_selftest_fn(int fn, const float* params, const float* in, float* out, int n, hipStream_t stream) {
     hipLaunchKernelGGL(selftest_fn_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, fn, params, in, out, n);
+}
+void launch_selftest_env(int fn, const float* env, int env_w, int env_h, const float* rows, const float* cols, const float* in, float* out, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(selftest_env_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, fn, env, env_w, env_h, rows, cols, in, out, n);
 }
 void launch_tonemap(const float4* fb, unsigned char* out, const FrameArgs& fa, hipStream_t stream) {
     const size_t npix = (size_t)fa.width * (size_t)fa.rows;

@@ -38,6 +38,8 @@ void launch_state_to_rtd(const DevState& S, prt_path_state* out, size_t n, hipSt
 void launch_rtd_to_state(const prt_path_state* in, const DevState& S, float4* fb, size_t n, hipStream_t stream);
 void launch_selftest_math(int fn, const float* a, const float* b, float* out, int n, hipStream_t stream);
 void launch_selftest_fn(int fn, const float* params, const float* in, float* out, int n, hipStream_t stream);
+// prt_selftest_fn fn 13 / 14 (pt_selftest.h selftest_env): env_sample / env_pdf and env_lookup on a map with its build_env_cdf tables (device pointers)
+void launch_selftest_env(int fn, const float* env, int env_w, int env_h, const float* rows, const float* cols, const float* in, float* out, int n, hipStream_t stream);
 // prt_selftest_fn fn 12 (pt_filter.hip): filter_offset of pt_filter.h on the device, n cases of 32 floats in / out (in: gx, gy, k as uint bits;
 // out: dx, dy); tab: the kind's table (device) or null
 void launch_selftest_filter(unsigned kind, float r, const float* tab, const float* in, float* out, int n, hipStream_t stream);

@@ -3,6 +3,8 @@
 // (tests/golden/kat_*.npz): `params` up to 80 floats shared by a call, 32 floats in / 32 floats out per case, uint
 // values as float bit patterns, the RNG state in in[30..31] / out[30..31].  Compiled into libprt (selftest_fn_kernel)
 // and, for the CPU tests, into tests/emu.
+// selftest_env (fn 13 / 14) drives the environment-map importance sampling -- which the reference does not have, so no fixture can hold it --
+// on a caller's map and its tables (build_env_cdf): same 32-in / 32-out cases, no params (selftest_env_kernel; tests/emu emu_selftest_env).
 #pragma once
 #include "pt_device.h"
 
@@ -142,6 +144,30 @@ PT_DEV void selftest_fn(const int fn, const float* params, const float* x, float
     default: break;
     }
     y[30] = prt_u2f(rng.s0); y[31] = prt_u2f(rng.s1);
+}
+
+// fn 13: env_sample.  in: xi0, xi1; out: d.xyz, pdf, the texel (i, j) the two searches chose (uint bits), then env_pdf(d) and env_lookup(d) of
+//        the direction it produced
+// fn 14: env_pdf and env_lookup.  in: a direction; out: pdf, rgb
+// `sc`: env, env_w, env_h, env_cdf_rows, env_cdf_cols
+PT_DEV void selftest_env(const int fn, const DevScene& sc, const float* x, float* y) {
+    for (int k = 0; k < 32; ++k) y[k] = 0.0f;
+    if (fn == 13) {
+        const EnvSample es = env_sample(sc, x[0], x[1]);
+        const unsigned j = cdf_find(sc.env_cdf_rows, (unsigned)sc.env_h, x[0]);
+        const unsigned i = cdf_find(sc.env_cdf_cols + (size_t)j * (unsigned)(sc.env_w + 1), (unsigned)sc.env_w, x[1]);
+        y[0] = es.d.x; y[1] = es.d.y; y[2] = es.d.z; y[3] = es.pdf;
+        y[4] = prt_u2f(i); y[5] = prt_u2f(j);
+        y[6] = env_pdf(sc, es.d);
+        const f3 c = env_lookup(sc, es.d);
+        y[7] = c.x; y[8] = c.y; y[9] = c.z;
+    } else if (fn == 14) {
+        const f3 d = F3(x[0], x[1], x[2]);
+        y[0] = env_pdf(sc, d);
+        const f3 c = env_lookup(sc, d);
+        y[1] = c.x; y[2] = c.y; y[3] = c.z;
+    }
+    y[30] = x[30]; y[31] = x[31];
 }
 
 }  // namespace dev

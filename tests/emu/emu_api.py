@@ -47,6 +47,8 @@ def lib():
         _lib.emu_variant_row.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         _lib.emu_selftest_fn.restype = None
         _lib.emu_selftest_fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _lib.emu_selftest_env.restype = None
+        _lib.emu_selftest_env.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     return _lib
 
 
@@ -78,6 +80,17 @@ def selftest_fn(fn, params, cases):
     cases = np.ascontiguousarray(cases, dtype=np.float32)
     out = np.zeros_like(cases)
     lib().emu_selftest_fn(int(fn), params.ctypes.data_as(C.c_void_p), cases.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cases.shape[0])
+    return out
+
+
+def selftest_env(fn, env, cases):
+    """prt_selftest_fn fn 13 / 14 on the host: env float32 [h, w, 3], cases [n, 32] -> [n, 32] (csrc/hip/pt_selftest.h selftest_env)"""
+    env = np.ascontiguousarray(env, dtype=np.float32)
+    cases = np.ascontiguousarray(cases, dtype=np.float32)
+    assert env.ndim == 3 and env.shape[2] == 3 and cases.ndim == 2 and cases.shape[1] == 32
+    out = np.zeros_like(cases)
+    lib().emu_selftest_env(int(fn), env.ctypes.data_as(C.c_void_p), env.shape[1], env.shape[0], cases.ctypes.data_as(C.c_void_p),
+                           out.ctypes.data_as(C.c_void_p), cases.shape[0])
     return out
 
 

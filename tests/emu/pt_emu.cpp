@@ -259,3 +259,11 @@ extern "C" int emu_variant_row(int i, uint32_t* mats, int* medium, const char** 
 extern "C" void emu_selftest_fn(int fn, const float* params, const float* in, float* out, int n) {
     for (int i = 0; i < n; ++i) selftest_fn(fn, params, in + 32 * (size_t)i, out + 32 * (size_t)i);
 }
+// prt_selftest_fn fn 13 / 14 on the host: selftest_env (csrc/hip/pt_selftest.h) on a map and the tables build_env_cdf makes of it
+extern "C" void emu_selftest_env(int fn, const float* rgb, int w, int h, const float* in, float* out, int n) {
+    std::vector<float> rows, cols;
+    build_env_cdf(rgb, w, h, rows, cols);
+    DevScene sc = DevScene();
+    sc.env = rgb; sc.env_w = w; sc.env_h = h; sc.env_cdf_rows = rows.data(); sc.env_cdf_cols = cols.data();
+    for (int i = 0; i < n; ++i) selftest_env(fn, sc, in + 32 * (size_t)i, out + 32 * (size_t)i);
+}

@@ -21,6 +21,19 @@ def test_every_declared_symbol_is_exported(prt):
     assert declared == bound, "python prototypes out of sync with include/prt.h: %s" % (declared ^ bound)
 
 
+def test_env_cdf_needs_no_device_and_no_context(prt):
+    """prt_env_cdf (host only, like prt_pixel_filter_offsets): a 1 x 1 map gives {0, 1} in both tables, a 2 x 1 map splits its row by the texels'
+    luminance (both see each other as neighbours: equal halves); bad arguments are refused with PRT_ERR_INVALID_ARGUMENT"""
+    import numpy as np
+    rows, cols = prt.env_cdf(np.full((1, 1, 3), 2.0, dtype=np.float32))
+    assert rows.tolist() == [0.0, 1.0] and cols.tolist() == [[0.0, 1.0]]
+    rows, cols = prt.env_cdf(np.array([[[1.0, 1.0, 1.0], [3.0, 3.0, 3.0]]], dtype=np.float32))
+    assert rows.tolist() == [0.0, 1.0] and cols.tolist() == [[0.0, 0.5, 1.0]]
+    lib = prt.load_library()
+    buf = np.zeros(8, dtype=np.float32).ctypes.data_as(C.c_void_p)
+    assert lib.prt_env_cdf(None, 1, 1, buf, buf) == -1 and lib.prt_env_cdf(buf, 1, 0, buf, buf) == -1 and lib.prt_env_cdf(buf, 1, 1, buf, None) == -1
+
+
 def test_struct_layouts_match_the_reference_abi(prt):
     c = prt._capi
     assert C.sizeof(c.Material) == 64 and C.sizeof(c.Mesh) == 256 and C.sizeof(c.BvhNode) == 36 and C.sizeof(c.Camera) == 80
