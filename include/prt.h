@@ -191,6 +191,45 @@ int prt_update_vertices(prt_ctx* ctx, const float* vertices, const float* normal
 int prt_update_vertices_device(prt_ctx* ctx, const void* d_vertices, const void* d_normals);
 int prt_read_bvh_bounds(prt_ctx* ctx, float* bounds6);
 
+/* Deforming geometry, second door: new vertices into the uploaded scene and a NEW TREE over all T triangles, built on the device in Morton order
+ * (no counterpart in the reference).  Arguments, alignment and staging are those of prt_update_vertices / prt_update_vertices_device; the call
+ * is ordered on the context's stream and complete on return.  max_leaf = 1 .. 64, 0 = the library's default (4).  Triangle i is vertices 3i,
+ * 3i+1, 3i+2; what the tree being replaced looked like does not matter (one that referenced 100 of T triangles comes back with T), so a mesh
+ * may be uploaded under a trivial tree -- a leaf root that names every triangle -- and get its real one here.
+ * The tree, all f32, no contraction:
+ *   1. Triangle box: the leaf rule of prt_update_vertices over the triangle's three vertices.  Centre per axis: c = lo * 0.5f + hi * 0.5f.
+ *   2. Extent of the centres per axis: lo = (min over all triangles) + 0.0f, hi = (max over all triangles) + 0.0f (the sign of a zero cannot
+ *      depend on the order of the reduction); scale = hi > lo ? 1024.0f / (hi - lo) : 0.0f.
+ *   3. q = (uint32) min((c - lo) * scale, 1023.0f) per axis (min(t, 1023) = t < 1023.0f ? t : 1023.0f); the 30-bit Morton code interleaves
+ *      the 10 bits of q.x, q.y, q.z with x in the highest bit of each triple, then y, then z.
+ *   4. key = (uint64)code << 32 | i: distinct, sorted ascending.
+ *   5. The binary radix tree of the sorted keys: a range [a, b] of positions with a < b splits behind the largest g in [a, b) whose key has a 0
+ *      in the highest bit in which key[a] and key[b] differ, into [a, g] and [g + 1, b].  A range of at most max_leaf triangles is a leaf;
+ *      T <= max_leaf gives a leaf root.
+ *   6. The inner ranges ("pairs") are numbered by (depth, first position): breadth-first, left to right, the root pair 0.  Node 0 is the
+ *      root; the children of pair k are nodes 2k + 1 and 2k + 2.
+ *   7. Slots: the leaves in pair order, a pair's left leaf first; within a leaf the triangles in sorted order.  primitive_indices[s] is the
+ *      triangle of slot s, a leaf's first_child_or_primitive its first slot (prt_upload_scene's own slot order).
+ *   8. Boxes and triangle records: the rules of prt_update_vertices on the new tables.
+ *   9. Every device buffer and table equals what prt_upload_scene of (new vertices, new normals, the tree of 1 - 8) makes with breadth-first
+ *      pair order.  The key has 62 significant bits: depth <= 62, within the 64-entry traversal stack and the 256 levels of a refit.
+ * A render after a rebuild is bit-identical to a fresh context that uploads what prt_read_bvh returns; prt_update_vertices afterwards refits
+ * the new topology; tile, row-block and rank contexts that each rebuild stay bit-identical in union to one whole-frame context.
+ * Lifetime: as an update -- path state, framebuffer and both histories are kept, guides and measured tile orders dropped.  normals == NULL
+ * carries the normal records to the new slots (through "a slot of the old tree that holds the triangle": where leaves shared a triangle
+ * their records are equal).  With prt_set_motion on, the snapshot the motion plane is measured from moves to the new slot order the same
+ * way: a pending one is permuted, otherwise the current records are taken; a triangle the old tree did not hold gets its new record (no
+ * motion).  The history follows the mesh across a rebuild as across an update.
+ * Refused, each leaving the scene exactly as it was (the tree is built into buffers of its own and swapped in at the end): what
+ * prt_update_vertices refuses (the 256-level limit apart: the old tree is not refitted), max_leaf > 64, and normals == NULL when the current
+ * tree does not reference every triangle (there is no normal record for the rest): PRT_ERR_INVALID_ARGUMENT.
+ * prt_read_bvh: the current tree in the reference's layout, node 0 the root: an uploaded tree as uploaded with its current boxes, a
+ * rebuilt one by rules 6 and 7 (inner nodes: primitive_count 0).  nodes == NULL writes *node_count only; primitive_indices (may be NULL)
+ * receives T entries.  prt_read_bvh_bounds keeps working, in the numbering prt_read_bvh returns. */
+int prt_rebuild_bvh(prt_ctx* ctx, const float* vertices, const float* normals, uint32_t max_leaf);
+int prt_rebuild_bvh_device(prt_ctx* ctx, const void* d_vertices, const void* d_normals, uint32_t max_leaf);
+int prt_read_bvh(prt_ctx* ctx, prt_bvh_node* nodes, uint32_t* node_count, uint64_t* primitive_indices);
+
 /* enqueueWriteBuffer(cl_camera), src/main.cpp:294-297 (every frame in the reference). */
 int prt_set_camera(prt_ctx* ctx, const prt_camera* cam);
 

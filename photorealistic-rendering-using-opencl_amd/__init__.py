@@ -339,6 +339,39 @@ class Renderer:
         self._chk(self.lib.prt_read_bvh_bounds(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_bvh_bounds")
         return out
 
+    def rebuild_bvh(self, vertices, normals=None, max_leaf=0):
+        """prt_rebuild_bvh / prt_rebuild_bvh_device: new vertices (and normals; None carries the current ones over) and a new Morton-order tree
+        over all T triangles, built on the device (prt.h).  Arguments as update_vertices; max_leaf 1 .. 64, 0 = the library's default"""
+        floats = 12 * getattr(self, "triangle_count", 0)
+        if isinstance(vertices, np.ndarray) or vertices is None:
+            v = None if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32)
+            n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32)
+            if (v is not None and v.size < floats) or (n is not None and n.size < floats):
+                raise ValueError("rebuild_bvh: needs float32 arrays of at least %d elements" % floats)
+            self._chk(self.lib.prt_rebuild_bvh(self.ctx, None if v is None else v.ctypes.data_as(C.c_void_p),
+                                               None if n is None else n.ctypes.data_as(C.c_void_p), int(max_leaf)), "prt_rebuild_bvh")
+        else:
+            if hasattr(vertices, "data_ptr"):
+                import torch
+                torch.cuda.current_stream(vertices.device).synchronize()
+            pv = self._device_ptr(vertices, floats, "rebuild_bvh")
+            pn = None if normals is None else self._device_ptr(normals, floats, "rebuild_bvh")
+            self._chk(self.lib.prt_rebuild_bvh_device(self.ctx, pv, pn, int(max_leaf)), "prt_rebuild_bvh_device")
+        count = C.c_uint32(0)
+        self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
+        self.bvh_node_count = int(count.value)
+
+    def read_bvh(self):
+        """prt_read_bvh: (nodes [node_count] of _capi.BVH_NODE_DTYPE, primitive_indices uint64 [T]): the current tree in the reference's layout,
+        node 0 the root -- the uploaded tree with its current boxes, or the rebuilt one"""
+        count = C.c_uint32(0)
+        self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
+        nodes = np.zeros(int(count.value), dtype=np.dtype(_capi.BVH_NODE_DTYPE))
+        prims = np.zeros(getattr(self, "triangle_count", 0), dtype=np.uint64)
+        if nodes.size:
+            self._chk(self.lib.prt_read_bvh(self.ctx, nodes.ctypes.data_as(C.c_void_p), C.byref(count), prims.ctypes.data_as(C.c_void_p)), "prt_read_bvh")
+        return nodes, prims
+
     def set_camera(self, cam):
         self._chk(self.lib.prt_set_camera(self.ctx, C.byref(cam)), "prt_set_camera")
 

@@ -116,6 +116,9 @@ PRT_API = [
     ("prt_update_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_update_vertices_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_read_bvh_bounds", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_rebuild_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("prt_rebuild_bvh_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("prt_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_set_camera", C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     ("prt_upload_envmap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("prt_resize", C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -105,5 +105,32 @@ void launch_refit_check(const float* vertices, size_t n_vertices, uint32_t* flag
 // into root6 (device, 6 floats)
 void launch_refit(const RefitTables& t, const float* vertices, const float* normals, NodePair* pairs, TriGeom* tri_geom, TriNrm* tri_nrm,
                   float* root6, hipStream_t stream);
+// pt_build.hip.  prt_rebuild_bvh: the scratch of one build over T triangles, carved out of one device allocation of the context
+struct BuildNode;
+struct BuildExtent;
+struct BuildHeader;
+struct BuildWork {
+    uint64_t* keys; uint64_t* keys_sorted;              // T: code << 32 | triangle
+    uint64_t* pair_keys; uint64_t* pair_keys_sorted;    // T - 1: depth << 32 | first position, per inner node of the radix tree
+    BuildNode* nodes; uint32_t* parent;                 // T - 1
+    uint32_t* order_in; uint32_t* order;                // T - 1: the inner node of each sorted position
+    uint32_t* pair_of; uint32_t* leaf_tris; uint32_t* slot_base;      // T - 1
+    uint32_t* old_slot;                                 // T: a slot of the tree being replaced that holds the triangle, or 0xFFFFFFFF
+    float* partials; BuildExtent* extent;               // 6 floats per block of 256 triangles; the extent of the centres
+    BuildHeader* hdr;                                   // what the host reads back
+    uint32_t* flags;                                    // [0] a non-finite vertex, [1] a triangle without an old slot
+    void* temp; size_t temp_bytes;                      // the sorts' and the scan's temporary storage
+};
+// the pointers of `w` for T triangles from `base` on (null: sizes only), the bytes all of it takes in *bytes
+hipError_t build_work_layout(uint32_t T, void* base, BuildWork& w, size_t* bytes);
+// w.old_slot from the slot table of the tree being replaced; check_missing: 1 into w.flags[1] (zeroed by the caller) if a triangle has none
+void launch_build_old_slots(const BuildWork& w, const uint32_t* old_slot_vtx, size_t n_old_slots, uint32_t T, bool check_missing, hipStream_t stream);
+// rules 1 - 7 of prt.h: NodePair::meta of every pair (boxes zeroed), slot_vtx (T entries), the identity level_pairs, and w.hdr.  T <= max_leaf:
+// slot_vtx alone (a leaf root over slots 0 .. T - 1)
+hipError_t launch_build_tree(const BuildWork& w, const float* vertices, uint32_t T, uint32_t max_leaf, NodePair* pairs, uint32_t* slot_vtx,
+                             uint32_t* level_pairs, hipStream_t stream);
+// per new slot: TriNrm from the triangle's old slot (carry_nrm) and the motion snapshot in the new slot order (prev_new non-null; pt_build.h)
+void launch_build_carry(const BuildWork& w, const uint32_t* slot_vtx, uint32_t n_slots, bool carry_nrm, const TriNrm* nrm_old, TriNrm* nrm_new,
+                        const TriGeom* prev_old, const TriGeom* geom_new, TriGeom* prev_new, hipStream_t stream);
 
 }  // namespace prt
