@@ -139,7 +139,17 @@ int prt_create(int device, const prt_config* cfg, prt_ctx** out);
 /* process exit in the reference; explicit here. */
 void prt_destroy(prt_ctx* ctx);
 
-/* clw::buffer::create x5 + mBufMaterial, src/main.cpp:401-418,93-122.  Copies and re-packs. */
+/* Size limits of the device tables.  The render kernels address the node pairs (64 bytes each), the triangle records of the leaf slots
+ * (48 bytes each, one slot per leaf reference of a triangle) and the materials (48 bytes each, object_count[7] + 2 records) by a 32-bit byte
+ * offset from the table's base: each table stays below 4 GiB.  A scene, a refit or a device rebuild whose tables would be larger is refused
+ * with PRT_ERR_UNSUPPORTED and a message that names the limit it passed. */
+#define PRT_MAX_TRIANGLE_SLOTS 89478485u   /* floor((2^32 - 1) / 48) */
+#define PRT_MAX_NODE_PAIRS 67108863u       /* 2^26 - 1 */
+#define PRT_MAX_MATERIALS 89478485u        /* floor((2^32 - 1) / 48); the 24-bit mesh index of a hit record binds first */
+#define PRT_MAX_ENV_TEXELS 357913941u      /* floor((2^32 - 1) / 12): prt_upload_envmap, width x height of the RGB float map */
+#define PRT_MAX_ENV_SIDE 16777215          /* 2^24 - 1: prt_upload_envmap, width and height each (the texel index is a 24-bit multiply) */
+
+/* clw::buffer::create x5 + mBufMaterial, src/main.cpp:401-418,93-122.  Copies and re-packs.  PRT_ERR_UNSUPPORTED beyond the limits above. */
 int prt_upload_scene(prt_ctx* ctx, const prt_scene_desc* scene);
 
 /* Deforming geometry: new vertices into the uploaded scene, the tree REFITTED on the device (no counterpart in the reference, whose scene is
@@ -222,7 +232,8 @@ int prt_read_bvh_bounds(prt_ctx* ctx, float* bounds6);
  * motion).  The history follows the mesh across a rebuild as across an update.
  * Refused, each leaving the scene exactly as it was (the tree is built into buffers of its own and swapped in at the end): what
  * prt_update_vertices refuses (the 256-level limit apart: the old tree is not refitted), max_leaf > 64, and normals == NULL when the current
- * tree does not reference every triangle (there is no normal record for the rest): PRT_ERR_INVALID_ARGUMENT.
+ * tree does not reference every triangle (there is no normal record for the rest): PRT_ERR_INVALID_ARGUMENT.  T - 1 > PRT_MAX_NODE_PAIRS (the
+ * pair table is sized for a tree of single-triangle leaves): PRT_ERR_UNSUPPORTED.
  * prt_read_bvh: the current tree in the reference's layout, node 0 the root: an uploaded tree as uploaded with its current boxes, a
  * rebuilt one by rules 6 and 7 (inner nodes: primitive_count 0).  nodes == NULL writes *node_count only; primitive_indices (may be NULL)
  * receives T entries.  prt_read_bvh_bounds keeps working, in the numbering prt_read_bvh returns. */

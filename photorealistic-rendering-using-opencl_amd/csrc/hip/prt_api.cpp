@@ -395,6 +395,12 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 static int refit_tables(prt_ctx* c);
 
+// the size limits of the tables a refit or a rebuild writes and the render kernels read by 32-bit offsets (prt.h PRT_MAX_*; pt_layout.h)
+static int table_limits(prt_ctx* c, const std::string& who, uint64_t slots, uint64_t pairs) {
+    const char* m = table_limit_error(slots, pairs, (uint64_t)c->sc.n_meshes + 2u);
+    return m ? fail(c, PRT_ERR_UNSUPPORTED, who + ": " + m) : PRT_OK;
+}
+
 // the checks both variants share, and the device tables on the first update
 static int refit_prepare(prt_ctx* c, const void* vertices, const char* who) {
     const std::string w(who);
@@ -402,6 +408,7 @@ static int refit_prepare(prt_ctx* c, const void* vertices, const char* who) {
     if (!vertices) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null vertices");
     if (!c->sc.root_is_leaf && c->level_first.size() > 257u)
         return fail(c, PRT_ERR_UNSUPPORTED, w + ": the tree has more than 256 levels of pairs (one launch per level)");
+    if (int rc = table_limits(c, w, c->n_slots, c->sc.n_pairs)) return rc;       // (the tables the refit kernels write)
     HIPCHK(c, hipSetDevice(c->device));
     return refit_tables(c);
 }
@@ -515,6 +522,8 @@ extern "C" int prt_rebuild_bvh_device(prt_ctx* c, const void* d_vertices, const 
     const uint32_t T = c->n_tris;
     const bool leaf_root = T <= max_leaf;
     const bool carry_nrm = d_normals == nullptr;
+    // the new tables: one slot per triangle, and room for the T - 1 pairs of a tree of single-triangle leaves
+    if (int rc = table_limits(c, "prt_rebuild_bvh", T, T > 1u ? T - 1u : 1u)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refit_tables(c);                             // (the slot table of the tree being replaced: "old slot of triangle")
     if (rc) return rc;
@@ -686,6 +695,10 @@ extern "C" int prt_set_camera(prt_ctx* c, const prt_camera* cam) {
 extern "C" int prt_upload_envmap(prt_ctx* c, const float* rgb, int w, int h) {
     CTX_CHECK(c);
     if (!rgb || w <= 0 || h <= 0) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_envmap: bad arguments");
+    if ((uint64_t)w * (uint64_t)h > PRT_MAX_ENV_TEXELS)       // (env_texel reads the map by a 32-bit byte offset, like the scene's tables)
+        return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_envmap: more than 357913941 texels (PRT_MAX_ENV_TEXELS: 12-byte texels below 4 GiB, 32-bit offsets)");
+    if (w > PRT_MAX_ENV_SIDE || h > PRT_MAX_ENV_SIDE)
+        return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_envmap: a side of more than 16777215 texels (PRT_MAX_ENV_SIDE: the texel index is a 24-bit multiply)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->guides_valid = false;

@@ -119,14 +119,27 @@ template <typename T> PT_HD const PT_CONST pt_vf4* const_vf4(const T* p) { retur
 PT_HD unsigned const_u32(const uint32_t* p, unsigned i) { return ((const PT_CONST uint32_t*)p)[i]; }
 PT_HD int const_i32(const int32_t* p, unsigned i) { return ((const PT_CONST int32_t*)p)[i]; }
 PT_HD float const_f32(const float* p, size_t i) { return ((const PT_CONST float*)p)[i]; }
-PT_HD DevSphere const_sphere(const DevSphere* p, unsigned i) {
-    const pt_vf4 a = const_vf4(p + i)[0];
+// A record of a per-lane table (pairs, tri_geom, tri_nrm, mats) at {uniform base, 32-bit byte offset} (pt_layout.h pair_offset /
+// rec48_offset): an unsigned offset zero-extended onto a byte pointer is what the compiler turns into a load with a scalar base
+// register pair and ONE vector offset register, where `base + index` costs a 64-bit multiply-add or shift-add and a register pair
+template <typename T> PT_HD unsigned table_offset(unsigned i) {
+    static_assert(sizeof(T) == 64 || sizeof(T) == 48, "NodePair, or a 48-byte record");
+    return sizeof(T) == 64 ? pair_offset(i) : rec48_offset(i);
+}
+template <typename T> PT_HD const float4* table_at(const T* base, unsigned i) { return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + table_offset<T>(i)); }
+template <typename T> PT_HD const PT_CONST pt_vf4* const_table_at(const T* base, unsigned i) { return (const PT_CONST pt_vf4*)((const PT_CONST char*)base + table_offset<T>(i)); }
+// (the primitives by a lane's own mesh index -- direct_pdf_mesh, sample_light_pick, the SDF normal -- the same way: they are fewer than 2^23,
+// prt_upload_scene, so `i * sizeof(T)` stays far below 2^32; the loops over all of them keep their uniform `p + i`)
+template <typename T> PT_HD const PT_CONST pt_vf4* const_lane_at(const T* base, unsigned i) { return (const PT_CONST pt_vf4*)((const PT_CONST char*)base + i * (unsigned)sizeof(T)); }
+PT_HD DevSphere sphere_of(const PT_CONST pt_vf4* q) {
+    const pt_vf4 a = q[0];
     DevSphere s;
     s.pos[0] = a.x; s.pos[1] = a.y; s.pos[2] = a.z; s.radius = a.w;
     return s;
 }
-PT_HD DevQuad const_quad(const DevQuad* p, unsigned i) {
-    const PT_CONST pt_vf4* q = const_vf4(p + i);
+PT_HD DevSphere const_sphere(const DevSphere* p, unsigned i) { return sphere_of(const_vf4(p + i)); }
+PT_HD DevSphere lane_sphere(const DevSphere* p, unsigned i) { return sphere_of(const_lane_at(p, i)); }
+PT_HD DevQuad quad_of(const PT_CONST pt_vf4* q) {
     const pt_vf4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4];
     DevQuad r;
     r.base[0] = a.x; r.base[1] = a.y; r.base[2] = a.z; r.area = a.w;
@@ -136,14 +149,17 @@ PT_HD DevQuad const_quad(const DevQuad* p, unsigned i) {
     r.anchor[0] = e.x; r.anchor[1] = e.y; r.anchor[2] = e.z; r.u1 = e.w;
     return r;
 }
-PT_HD DevSdf const_sdf(const DevSdf* p, unsigned i) {
-    const PT_CONST pt_vf4* q = const_vf4(p + i);
+PT_HD DevQuad const_quad(const DevQuad* p, unsigned i) { return quad_of(const_vf4(p + i)); }
+PT_HD DevQuad lane_quad(const DevQuad* p, unsigned i) { return quad_of(const_lane_at(p, i)); }
+PT_HD DevSdf sdf_of(const PT_CONST pt_vf4* q) {
     const pt_vf4 a = q[0], b = q[1];
     DevSdf r;
     r.pos[0] = a.x; r.pos[1] = a.y; r.pos[2] = a.z; r.type = prt_f2u(a.w);
     r.params[0] = b.x; r.params[1] = b.y; r.params[2] = b.z; r.params[3] = b.w;
     return r;
 }
+PT_HD DevSdf const_sdf(const DevSdf* p, unsigned i) { return sdf_of(const_vf4(p + i)); }
+PT_HD DevSdf lane_sdf(const DevSdf* p, unsigned i) { return sdf_of(const_lane_at(p, i)); }
 PT_DEV f3 vexp(f3 a) { return F3(prt_exp(a.x), prt_exp(a.y), prt_exp(a.z)); }
 PT_DEV float fmax3(f3 v) { return prt_fmax(prt_fmax(v.x, v.y), v.z); }
 PT_DEV float avg3(f3 v) { return (v.x * 1.0f + v.y * 1.0f + v.z * 1.0f) * 0.3333333333333333333333333333333333333333333333f; }
@@ -198,9 +214,9 @@ struct Mat {                                                     // Material, he
 // DM: the microfacet distributions the scene's materials use (PRT_DIST_* bits; 7 = any): masking the field with a compile-time constant
 // lets the compiler drop the lobes' code for the others (render_kernel's PT_MATS_DISTS bits)
 template <unsigned DM = 7u>
-PT_DEV Mat load_mat(const DevMaterial* m) {
+PT_DEV Mat load_mat(const DevMaterial* mats, unsigned i) {
     Mat r;
-    const PT_CONST pt_vf4* q = const_vf4(m);                 // (a uniform `m` -- the light's material -- is three scalar loads)
+    const PT_CONST pt_vf4* q = const_table_at(mats, i);      // (a uniform `i` -- the light's material -- is three scalar loads)
     const pt_vf4 a = q[0], e = q[1], kk = q[2];
     r.color = F3(a.x, a.y, a.z); r.roughness = a.w;
     r.eta = F3(e.x, e.y, e.z); r.k = F3(kk.x, kk.y, kk.z);
@@ -209,7 +225,11 @@ PT_DEV Mat load_mat(const DevMaterial* m) {
     return r;
 }
 
-PT_DEV unsigned mat_bits(const DevMaterial* m) { return const_u32(reinterpret_cast<const uint32_t*>(m), 7u); }   // DevMaterial::bits
+// DevMaterial::bits.  (The field's 28 bytes are part of the 32-bit offset: a caller that goes on to load_mat the same record then forms that
+// offset where it loads, and not as a 64-bit value carried over from here, which would cost the load its scalar base)
+PT_DEV unsigned mat_bits(const DevMaterial* mats, unsigned i) { return *(const PT_CONST uint32_t*)((const PT_CONST char*)mats + (rec48_offset(i) + 28u)); }
+// the material record of mesh `mesh_id` (-1: the guard record 0): below 2^24 (pack_scene), and said so for a 24-bit multiply
+PT_DEV unsigned mat_index(int mesh_id) { return (unsigned)(mesh_id + 1) & 0xffffffu; }
 
 // sin(x) and cos(x) of one argument from ONE evaluation of prt_sincos_kernel: the reduction and both polynomials are the same in prt_sin and
 // prt_cos (include/prt_detmath.h), only the quadrant selects differ, and a caller that takes both used to evaluate them twice (about 30
@@ -390,7 +410,7 @@ struct TravStack {
 
 struct PairData { float4 b0, b1, b2; uint4 meta; };
 PT_DEV PairData load_pair(const NodePair* __restrict__ pairs, unsigned node) {
-    const float4* q = reinterpret_cast<const float4*>(pairs + node);
+    const float4* q = table_at(pairs, node);
     PairData d;
     d.b0 = q[0]; d.b1 = q[1]; d.b2 = q[2];
     d.meta = *reinterpret_cast<const uint4*>(q + 3);
@@ -448,7 +468,7 @@ __device__ unsigned long long g_walk_stats[16];
 // a wave's walks for a bounded number of steps; a lane whose ray needs more keeps {node, sp, t, hit, pending run} for the wave's
 // next walk phase, the LDS stack column stays the lane's own.  found: (closest) a triangle was accepted, (any) a triangle closer
 // than tmax exists.  (u, v, slot: the last accepted triangle, as in TriHit; slot and three flags share a word -- pack_scene
-// refuses 2^29 triangle slots and more; `last`: the stack was empty when the step ended: the walk is over once the run is tested)
+// refuses more than PT_MAX_SLOTS < 2^27 triangle slots; `last`: the stack was empty when the step ended: the walk is over once the run is tested)
 struct WalkState {
     unsigned node;
     unsigned sp : 7, pend_count : 25;       // entries on the stack (at most 64); triangles of the step's leaves still to test
@@ -550,7 +570,7 @@ PT_DEV void walk_box(const DevScene& sc, const bool ANY_HIT, const Ray& ray, con
     walk_box_data(d, ANY_HIT, ray, p, w, stack);
 }
 PT_DEV void walk_tri(const DevScene& sc, const bool ANY_HIT, const Ray& ray, WalkState& w) {
-    const float4* q = reinterpret_cast<const float4*>(sc.tri_geom + w.pend_first);
+    const float4* q = table_at(sc.tri_geom, w.pend_first);
     const float4 a = q[0], b = q[1], c4 = q[2];
     walk_tri_data(a, b, c4, ANY_HIT, ray, w);
 }
@@ -670,7 +690,7 @@ PT_DEV bool finish_closest(const DevScene& sc, Ray& ray, const TravRes& tr, int&
     float t = tr.t;
     mesh_id = -1;
     if (tr.found) {
-        const float4* nq = reinterpret_cast<const float4*>(sc.tri_nrm + tr.th.slot);
+        const float4* nq = table_at(sc.tri_nrm, tr.th.slot);
         const float4 a = nq[0], b = nq[1], c = nq[2];
         ray.normal = F3(a.x, a.y, a.z) * (1.0f - tr.th.u - tr.th.v) + F3(b.x, b.y, b.z) * tr.th.u + F3(c.x, c.y, c.z) * tr.th.v;   // triangle.cl:22,30-34
     }
@@ -689,7 +709,7 @@ PT_DEV bool finish_closest(const DevScene& sc, Ray& ray, const TravRes& tr, int&
     if (SDF && sc.n_sdfs) {                                                                  // intersect.cl:185-194
         if (intersect_sdf(sc, ray, t, mesh_id)) {
             ray.pos = ray.origin + ray.dir * t;
-            ray.normal = sdf_normal(const_sdf(sc.sdfs, (unsigned)(mesh_id - (int)sc.n_spheres)), ray.pos);
+            ray.normal = sdf_normal(lane_sdf(sc.sdfs, (unsigned)(mesh_id - (int)sc.n_spheres)), ray.pos);
         }
     }
     if (sc.geom_flags & PRT_GEOM_QUAD) {
@@ -705,7 +725,7 @@ PT_DEV bool finish_closest(const DevScene& sc, Ray& ray, const TravRes& tr, int&
         }
     }
     bool nTrans = true;
-    if (sc.ntrans_mask) nTrans = ((mat_bits(sc.mats + (mesh_id + 1)) & 0xffffu) & ~sc.ntrans_mask) != 0;
+    if (sc.ntrans_mask) nTrans = ((mat_bits(sc.mats, mat_index(mesh_id)) & 0xffffu) & ~sc.ntrans_mask) != 0;
     ray.t = t;
     ray.backside = dot(ray.normal, ray.dir) > 0.0f;
     if (nTrans && ray.backside) ray.normal = -ray.normal;
@@ -779,8 +799,8 @@ PT_DEV float quad_direct_pdf(const DevQuad& qd, f3 dir, f3 p) {
 }
 // directPdf of the mesh that a probe ray hit (mesh_id >= 0)
 PT_DEV float direct_pdf_mesh(const DevScene& sc, int mesh_id, f3 dir, f3 p) {
-    if ((sc.geom_flags & PRT_GEOM_SPHERE) && (unsigned)mesh_id < sc.n_spheres) return sphere_direct_pdf(const_sphere(sc.spheres, (unsigned)mesh_id), p);
-    if ((sc.geom_flags & PRT_GEOM_QUAD) && (unsigned)mesh_id >= sc.quad_mesh_base) return quad_direct_pdf(const_quad(sc.quads, (unsigned)mesh_id - sc.quad_mesh_base), dir, p);
+    if ((sc.geom_flags & PRT_GEOM_SPHERE) && (unsigned)mesh_id < sc.n_spheres) return sphere_direct_pdf(lane_sphere(sc.spheres, (unsigned)mesh_id), p);
+    if ((sc.geom_flags & PRT_GEOM_QUAD) && (unsigned)mesh_id >= sc.quad_mesh_base) return quad_direct_pdf(lane_quad(sc.quads, (unsigned)mesh_id - sc.quad_mesh_base), dir, p);
     return 0.0f;
 }
 PT_DEV bool sample_light0(const DevScene& sc, f3 p, LightSample& ls, Rng& rng) {
@@ -795,8 +815,8 @@ PT_DEV bool sample_light(const DevScene& sc, const bool PICK, f3 p, LightSample&
     if (!PICK) { mesh = sc.light_mesh; return sample_light0(sc, p, ls, rng); }
     const int k = (int)(next1D(rng) * (float)(sc.light_count + 1u));
     mesh = const_u32(sc.light_tab, (unsigned)k);
-    if ((sc.geom_flags & PRT_GEOM_SPHERE) && mesh < sc.n_spheres) return sphere_sample_direct(const_sphere(sc.spheres, mesh), p, ls, rng);
-    if ((sc.geom_flags & PRT_GEOM_QUAD) && mesh >= sc.quad_mesh_base) return quad_sample_direct(const_quad(sc.quads, mesh - sc.quad_mesh_base), p, ls, rng);
+    if ((sc.geom_flags & PRT_GEOM_SPHERE) && mesh < sc.n_spheres) return sphere_sample_direct(lane_sphere(sc.spheres, mesh), p, ls, rng);
+    if ((sc.geom_flags & PRT_GEOM_QUAD) && mesh >= sc.quad_mesh_base) return quad_sample_direct(lane_quad(sc.quads, mesh - sc.quad_mesh_base), p, ls, rng);
     return false;                                    // geometry.cl:11-32: only spheres and quads can be sampled
 }
 
@@ -1284,7 +1304,10 @@ PT_DEV void medium_sample_distance(const DevScene& sc, MediumSample& ms, const R
 // ---- env map: kernels/utils.cl:46 + read_imagef(samplerA), OpenCL 1.2 s8.2, CLK_ADDRESS_CLAMP ----------
 PT_DEV f3 env_texel(const DevScene& sc, int i, int j) {
     if (i < 0 || j < 0 || i >= sc.env_w || j >= sc.env_h) return splat(0.0f);
-    const float* p = sc.env + ((size_t)j * sc.env_w + i) * 3;
+    // (a 32-bit byte offset from the uniform base, as table_at: prt_upload_envmap refuses maps of 4 GiB and more and sides of 2^24 and
+    // more, PRT_MAX_ENV_TEXELS / PRT_MAX_ENV_SIDE -- the masks say so to the compiler: one 24-bit multiply-add for the texel index)
+    const unsigned texel = ((unsigned)j & 0xffffffu) * ((unsigned)sc.env_w & 0xffffffu) + (unsigned)i;
+    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(sc.env) + texel * 12u);
     return F3(p[0], p[1], p[2]);
 }
 PT_DEV f3 env_lookup(const DevScene& sc, f3 dir) {
@@ -1600,7 +1623,7 @@ PT_DEV void lane_front(const DevScene& sc, const DevCamera& cam, const FrameArgs
     L.h_valid = false;
     L.kind = K_NONE; L.terminate = false; L.w2_ran = false; L.sh = false;
     L.vis = splat(0.0f);
-    const Mat mat = load_mat<dist_mask<MATS>()>((L.mesh_id + 1) ? &sc.mats[L.mesh_id + 1] : &sc.mats[sc.n_meshes + 1]);
+    const Mat mat = load_mat<dist_mask<MATS>()>(sc.mats, (L.mesh_id + 1) ? (unsigned)(L.mesh_id + 1) : sc.n_meshes + 1u);
     f3 emission = splat(0.0f);
     float alpha = 1.0f;
     if (MEDIUM) {
@@ -1619,7 +1642,7 @@ PT_DEV void lane_front(const DevScene& sc, const DevCamera& cam, const FrameArgs
                 const f3 f = splat(fv);
                 if (!(dot(f, f) == 0.0f)) {
                     L.sh = true; L.sh_d = rec.d; L.sh_tmax = rec.dist;
-                    const Mat lm = load_mat(&sc.mats[lmesh + 1]);
+                    const Mat lm = load_mat(sc.mats, lmesh + 1u);
                     const f3 tr = vexp(splat(sc.fog_sigma_t) * (-1.0f * rec.dist));
                     const f3 contribution = tr * lm.color * f * power_heuristic(rec.pdf, fv);
                     L.vis = contribution / rec.pdf;
@@ -1711,7 +1734,7 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
     if (MATS & PT_MATS_ENVIS) L.sh_vertex = false;
     if (L.kind == K_SURFACE_MIS) {
         constexpr bool ENVIS = (MATS & PT_MATS_ENVIS) != 0;
-        const Mat mat = load_mat<dist_mask<MATS>()>((L.mesh_id + 1) ? &sc.mats[L.mesh_id + 1] : &sc.mats[sc.n_meshes + 1]);
+        const Mat mat = load_mat<dist_mask<MATS>()>(sc.mats, (L.mesh_id + 1) ? (unsigned)(L.mesh_id + 1) : sc.n_meshes + 1u);
         // PT_MATS_ENVIS: does the map light this vertex at all?  In the default mode it does so through the BSDF-sampled ray alone, looked up in the
         // path's next segment -- which a path that this vertex's counters reset (lane_finish_segment's caps, after its increments by
         // L.sampledLobe) never runs.  Such a vertex gets neither the map sample nor the escaped ray's term, and its light sample is no coin's side
@@ -1724,9 +1747,9 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
         }
         if (L.w2_ran && L.h.didHit) {                                    // the probe ray, base.cl:58-75
             const int mid = L.h.mesh_id;
-            const unsigned lbits = mat_bits(sc.mats + (mid + 1));
+            const unsigned lbits = mat_bits(sc.mats, (unsigned)(mid + 1));
             if (lbits & PRT_MAT_LIGHT) {
-                const Mat lm = load_mat(&sc.mats[mid + 1]);
+                const Mat lm = load_mat(sc.mats, (unsigned)(mid + 1));
                 L.a = lm.color * L.weight * power_heuristic(L.pdf, direct_pdf_mesh(sc, mid, L.dir, hit_pos));
                 if (MEDIUM) L.a = L.a * vexp(splat(sc.fog_sigma_t) * (-1.0f * L.t));
             }
@@ -1774,7 +1797,7 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
                 const f3 fr = bsdf_eval2<MATS>(sc, e, mat);
                 if (!(dot(fr, fr) == 0.0f)) {
                     L.sh = true; L.sh_d = rec.d; L.sh_tmax = rec.dist;
-                    const Mat lm = load_mat(&sc.mats[lmesh + 1]);
+                    const Mat lm = load_mat(sc.mats, lmesh + 1u);
                     f3 contribution = lm.color * fr;
                     if (MEDIUM) contribution = contribution * vexp(splat(sc.fog_sigma_t) * (-1.0f * rec.dist));
                     contribution = contribution * power_heuristic(rec.pdf, bsdf_pdf<MATS>(sc, e, mat));
@@ -1787,9 +1810,9 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
         sh_o = L.origin;
         if (L.h.didHit) {
             const int mid = L.h.mesh_id;
-            const unsigned lbits = mat_bits(sc.mats + (mid + 1));
+            const unsigned lbits = mat_bits(sc.mats, (unsigned)(mid + 1));
             if (lbits & PRT_MAT_LIGHT) {
-                const Mat lm = load_mat(&sc.mats[mid + 1]);
+                const Mat lm = load_mat(sc.mats, (unsigned)(mid + 1));
                 const f3 tr = vexp(splat(sc.fog_sigma_t) * (-1.0f * L.h.t));
                 L.a = tr * lm.color * L.weight * power_heuristic(L.ps_pdf, direct_pdf_mesh(sc, mid, L.dir, L.origin));   // "b" of base.cl:259
             }

@@ -98,7 +98,7 @@ PT_DEV GuideSample guide_sample(const DevScene& sc, Ray ray, const TravStack& st
             return g;
         }
         dist = dist + ray.t;
-        const Mat mat = load_mat((mid + 1) ? &sc.mats[mid + 1] : &sc.mats[sc.n_meshes + 1]);
+        const Mat mat = load_mat(sc.mats, (mid + 1) ? (unsigned)(mid + 1) : sc.n_meshes + 1u);
         const bool cond = (mat.t & PRT_MAT_COND) && !(mat.t & PRT_MAT_ROUGH_COND);
         const bool diel = (mat.t & PRT_MAT_DIEL) && !(mat.t & PRT_MAT_ROUGH_DIEL);
         if (!(cond || diel) || events == PT_GUIDE_MAX_DELTA) {

@@ -71,6 +71,25 @@ struct alignas(16) DevMaterial {
 };
 static_assert(sizeof(DevSphere) == 16 && sizeof(DevQuad) == 80 && sizeof(DevMaterial) == 48, "prim records");
 
+// ---- 32-bit addressing of the per-lane tables.  A lane reads pairs[node], tri_geom[slot], tri_nrm[slot] and mats[i] at a table base that is the
+// same in every lane (a kernel argument, in scalar registers) plus a byte offset of its own.  The offset is formed in 32 bits -- one shift,
+// or a multiply by 3 and a shift for the 48-byte records -- and the load takes {scalar base, 32-bit vector offset}: no 64-bit multiply-add
+// or shift-add and no register pair per address (pt_device.h table_at / const_table_at).  The price is a bound on the tables: the
+// last byte of each must have an offset below 2^32 (include/prt.h PRT_MAX_*), which everything that sizes them checks with
+// table_limit_error: pack_scene, the refit and the device rebuild.
+constexpr uint32_t PT_MAX_SLOTS = 0xFFFFFFFFu / (uint32_t)sizeof(TriGeom);      // 89 478 485 (TriNrm: the same record size)
+constexpr uint32_t PT_MAX_PAIRS = 0xFFFFFFFFu / (uint32_t)sizeof(NodePair);     // 2^26 - 1
+constexpr uint32_t PT_MAX_MATS = 0xFFFFFFFFu / (uint32_t)sizeof(DevMaterial);   // 89 478 485
+PT_LAYOUT_HD uint32_t pair_offset(uint32_t node) { return node << 6; }          // node * sizeof(NodePair)
+PT_LAYOUT_HD uint32_t rec48_offset(uint32_t i) { return (i * 3u) << 4; }        // i * 48: TriGeom, TriNrm, DevMaterial
+// null, or what to say of tables of `slots` triangle records, `pairs` node pairs and `mats` material records (a pure function of the counts)
+inline const char* table_limit_error(uint64_t slots, uint64_t pairs, uint64_t mats) {
+    if (slots > PT_MAX_SLOTS) return "more than 89478485 triangle slots (PRT_MAX_TRIANGLE_SLOTS: 48-byte records below 4 GiB, 32-bit offsets)";
+    if (pairs > PT_MAX_PAIRS) return "more than 67108863 node pairs (PRT_MAX_NODE_PAIRS: 64-byte records below 4 GiB, 32-bit offsets)";
+    if (mats > PT_MAX_MATS) return "more than 89478485 material records (PRT_MAX_MATERIALS: 48-byte records below 4 GiB, 32-bit offsets)";
+    return nullptr;
+}
+
 // kernel argument block (passed by value: lives in the kernarg segment, read with scalar loads)
 struct DevScene {
     const NodePair* pairs;          // breadth-first order

@@ -76,7 +76,15 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
     if (n_mesh && !s->meshes) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: meshes is null");
     if (n_mesh >= (1u << 23)) return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_scene: 2^23 primitives or more (a hit record keeps the mesh index in 24 bits)");
     const uint32_t T = s->triangle_count, N = s->bvh_node_count;
-    if (T >= (1u << 29)) return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_scene: 2^29 triangles or more");
+    // the tables the render kernels read by a 32-bit byte offset (pt_layout.h table_limit_error): at least one slot per triangle, n_mesh + 2 materials
+    static_assert(PT_MAX_SLOTS == PRT_MAX_TRIANGLE_SLOTS && PT_MAX_PAIRS == PRT_MAX_NODE_PAIRS && PT_MAX_MATS == PRT_MAX_MATERIALS, "prt.h states the limits");
+    std::string limit_msg;
+    auto over_limit = [&](uint64_t slots, uint64_t n_pairs) {
+        const char* m = table_limit_error(slots, n_pairs, (uint64_t)n_mesh + 2);
+        if (m) limit_msg = std::string("prt_upload_scene: ") + m;
+        return m != nullptr;
+    };
+    if (over_limit(T, 0)) return fail(c, PRT_ERR_UNSUPPORTED, limit_msg.c_str());
     if (T && (!s->vertices || !s->normals || !s->primitive_indices || !s->bvh_nodes || !N))
         return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: triangle buffers incomplete");
 
@@ -118,9 +126,12 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
     // first, so that the leaves a walk step finds are ONE run of slots (pt_device.h walk_box / walk_tri).  slot_src[slot] =
     // position in primitive_indices.  A tree whose leaves share triangles gets one slot per reference (bounded: 4 x T).
     std::vector<uint32_t> slot_src;
-    const uint64_t max_slots = 4ull * T < (1ull << 29) ? 4ull * T : (1ull << 29) - 1;
+    const uint64_t max_slots = 4ull * T;
+    const char* const too_many_refs = "prt_upload_scene: the leaves reference more than 4 x the triangles";
     auto add_leaf = [&](const prt_bvh_node& nd, uint32_t& first_slot) {
-        if ((uint64_t)slot_src.size() + nd.primitive_count > max_slots) return false;
+        const uint64_t slots = (uint64_t)slot_src.size() + nd.primitive_count;
+        if (over_limit(slots, 0)) return false;
+        if (slots > max_slots) { limit_msg = too_many_refs; return false; }
         first_slot = (uint32_t)slot_src.size();
         for (uint32_t j = 0; j < nd.primitive_count; ++j) slot_src.push_back(nd.first_child_or_primitive + j);
         return true;
@@ -133,7 +144,7 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
         auto leaf_ok = [&](const prt_bvh_node& nd) { return (uint64_t)nd.first_child_or_primitive + nd.primitive_count <= T; };
         if (nodes[0].is_leaf) {
             if (!leaf_ok(nodes[0])) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: root leaf range out of bounds");
-            if (!add_leaf(nodes[0], sc.root_leaf_first)) return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_scene: the leaves reference more than 4 x the triangles");
+            if (!add_leaf(nodes[0], sc.root_leaf_first)) return fail(c, PRT_ERR_UNSUPPORTED, limit_msg.c_str());
             sc.root_leaf_count = nodes[0].primitive_count;
         } else {
             sc.root_is_leaf = 0;
@@ -208,6 +219,7 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
                     if (!nodes[fc].is_leaf) st.push_back(fc);
                 }
             }
+            if (over_limit(T, order.size())) return fail(c, PRT_ERR_UNSUPPORTED, limit_msg.c_str());
             pairs.resize(order.size());
             for (size_t k = 0; k < order.size(); ++k) {
                 const prt_bvh_node& nd = nodes[order[k]];
@@ -221,7 +233,7 @@ int pack_scene(const prt_config& cfg, const prt_scene_desc* s, PackedScene& out,
                         if (cn.primitive_count == 0xFFFFFFFFu) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_upload_scene: bad leaf");
                         // the walk keeps the triangles a step found pending in a 25-bit count (WalkState::pend_count = both leaf children of a pair)
                         if (cn.primitive_count >= (1u << 24)) return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_scene: a leaf of 2^24 triangles or more");
-                        if (!add_leaf(cn, p.meta[2 * ch])) return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_scene: the leaves reference more than 4 x the triangles");
+                        if (!add_leaf(cn, p.meta[2 * ch])) return fail(c, PRT_ERR_UNSUPPORTED, limit_msg.c_str());
                         p.meta[2 * ch + 1] = cn.primitive_count;
                     } else {
                         p.meta[2 * ch] = pair_of[nd.first_child_or_primitive + ch];

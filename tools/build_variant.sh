@@ -11,7 +11,7 @@ import importlib.util, sys
 spec = importlib.util.spec_from_file_location('b', '$P/build.py'); m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
 print(m.source_build_id(extra=sys.argv[1:]))" "$@")"
 COMMON="-std=c++17 -O3 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -DPT_UNITY -I$P/../include -I$P/csrc/host -I$P/csrc/hip"
-for s in prt_api.cpp pt_pack.cpp pt_kernels.hip pt_denoise.hip pt_temporal.hip pt_records.hip pt_filter.hip prt_build_id.cpp; do
+for s in prt_api.cpp pt_pack.cpp pt_kernels.hip pt_denoise.hip pt_temporal.hip pt_records.hip pt_filter.hip pt_refit.hip pt_build.hip prt_build_id.cpp; do
   /opt/rocm/bin/hipcc $COMMON -x hip --offload-arch=gfx950 "$@" -DPRT_BUILD_ID="\"$ID\"" -c $P/csrc/hip/$s -o $O/$s.o &
 done
 wait
