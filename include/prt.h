@@ -615,7 +615,7 @@ int prt_set_walk_min_lanes(prt_ctx* ctx, uint32_t lanes);
  *   "compact"           1 | 0   prt_render_adaptive: list launches once few pixels are live (see there); 0: tiles to the end
  *   "compact_below"     0 .. 100   ... once fewer than this percentage of the frame's pixels are live (default 50); a list is rebuilt
  *                               once its live pixels have fallen below half of it
- *   "test_drop_report"  0 | 1   tests only: the launches of prt_render_spp report their unfinished pixels into a spare word, so that the
+ *   "test_drop_report"  0 | 1   tests only: the launches of prt_render_spp and prt_render_adaptive report their unfinished pixels into a spare word, so that the
  *                               call sees a launch end without a report (PRT_ERR_HIP, state unusable until prt_reset) */
 int prt_set_option(prt_ctx* ctx, const char* name, int value);
 

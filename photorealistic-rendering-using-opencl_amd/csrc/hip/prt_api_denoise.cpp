@@ -1,0 +1,291 @@
+// prt_api_denoise.cpp -- the denoiser's calls of the C ABI (include/prt.h): the a-trous filter and its temporal variant on the context's frame
+// and on records, and both histories.
+#include "prt_ctx.h"
+
+static prt_denoise_params default_denoise_params() {
+    return prt_denoise_params{PRT_DENOISE_DEFAULT_PASSES, PRT_DENOISE_VAR_AUTO, PRT_DENOISE_DEFAULT_SIGMA_L, PRT_DENOISE_DEFAULT_SIGMA_N,
+                              PRT_DENOISE_DEFAULT_SIGMA_Z, PRT_DENOISE_DEFAULT_SIGMA_A};
+}
+static prt_temporal_params default_temporal_params() {
+    return prt_temporal_params{PRT_TEMPORAL_DEFAULT_ALPHA_COLOR, PRT_TEMPORAL_DEFAULT_ALPHA_MOMENTS, PRT_TEMPORAL_DEFAULT_TAU_Z, PRT_TEMPORAL_DEFAULT_COS_N,
+                               PRT_TEMPORAL_DEFAULT_HISTORY_CAP, PRT_TEMPORAL_FEEDBACK_ATROUS};
+}
+
+// the parameter checks of every denoise call ...
+static int denoise_param_checks(prt_ctx* c, const prt_denoise_params& p, const char* who) {
+    const std::string w(who);
+    if (p.passes < 1 || p.passes > 8) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": passes must be 1 .. 8");
+    if (!(p.sigma_l > 0.0f) || !(p.sigma_n > 0.0f) || !(p.sigma_z > 0.0f) || !(p.sigma_a > 0.0f))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": every sigma must be > 0 (and not NaN)");
+    if (p.var_source > PRT_DENOISE_VAR_SPATIAL) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown var_source");
+    return PRT_OK;
+}
+// ... and of the temporal ones
+static int temporal_param_checks(prt_ctx* c, const prt_temporal_params& t, const char* who) {
+    const std::string w(who);
+    if (!(t.alpha_color >= 0.0f && t.alpha_color <= 1.0f) || !(t.alpha_moments >= 0.0f && t.alpha_moments <= 1.0f))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": alpha_color and alpha_moments must be in [0, 1]");
+    if (!(t.tau_z > 0.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": tau_z must be > 0 (and not NaN)");
+    if (!(t.cos_n >= -1.0f && t.cos_n <= 1.0f)) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": cos_n must be in [-1, 1]");
+    if (t.history_cap < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": history_cap must be >= 1");
+    if (t.feedback > PRT_TEMPORAL_FEEDBACK_ATROUS) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown feedback");
+    return PRT_OK;
+}
+
+// the checks prt_denoise and prt_denoise_temporal share; *spatial: the variance source the call resolves to
+static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* who, bool* spatial) {
+    const std::string w(who);
+    int rc = denoise_param_checks(c, p, who);
+    if (rc) return rc;
+    rc = ready(c, who);
+    if (rc) return rc;
+    if (c->row0 != 0 || c->rows != c->full_height || c->n_parts != 1)
+        return fail(c, PRT_ERR_UNSUPPORTED, w + ": the filter needs the whole frame (tile and row-block contexts are refused)");
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, w + ": a debug view is not a picture to filter");
+    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, w + ": no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, w + ": nothing rendered since the reset");
+    const bool stats = c->stats_valid && c->d_adapt;
+    if (p.var_source == PRT_DENOISE_VAR_STATS && !stats)
+        return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs the last render since the reset to be prt_render_adaptive");
+    *spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL || (p.var_source == PRT_DENOISE_VAR_AUTO && !stats);
+    return PRT_OK;
+}
+
+// the filtered W x H plane `out` to the caller: device_rgba (device memory), rgba (host, prt_read_framebuffer's layout) and rgba8 (host,
+// prt_tonemap_rgba8's transform); any may be NULL.  The calls on the context's own frame pass its width and rows: denoise_checks has made
+// sure it is the whole frame, whose rows the tonemap maps as those of a W x H frame (one part: global row = local row, whatever block_rows)
+static int records_output(prt_ctx* c, const float4* out, int W, int H, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    const size_t npix = (size_t)W * (size_t)H;
+    if (device_rgba) HIPCHK(c, hipMemcpyAsync(device_rgba, out, npix * 16, hipMemcpyDeviceToDevice, c->stream));
+    if (rgba8) {
+        FrameArgs fa = frame_args(c, 1, 0, nullptr, 0, false);
+        fa.width = W; fa.full_height = H; fa.row0 = 0; fa.rows = H; fa.block_rows = 1; fa.n_parts = 1; fa.part = 0;
+        unsigned char* d = nullptr;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), npix * 4));
+        launch_tonemap(out, d, fa, c->stream);
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(rgba8, d, npix * 4, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rgba) HIPCHK(c, hipMemcpy(rgba, out, npix * 16, hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+// a temporal call on an npix-pixel history: what it reads (the half of the last call) and writes (the other half).  The history counts as
+// empty until history_commit: a failure in between leaves it empty
+static TemporalHistory history_begin(History& h, size_t npix) {
+    float4* half_prev = h.planes + 2 * npix * (size_t)h.cur;           // {c, n} plane, then {m1, m2, v, 0}
+    float4* half_next = h.planes + 2 * npix * (size_t)(h.cur ^ 1);
+    TemporalHistory t;
+    t.cn_prev = half_prev; t.m_prev = half_prev + npix; t.guides_prev = h.guides; t.cam_prev = h.cam; t.valid = h.valid;
+    t.cn = half_next; t.m = half_next + npix;
+    h.valid = false;
+    return t;
+}
+// ... and behind its launches: the guides and the camera of this call, and the flip
+static int history_commit(prt_ctx* c, History& h, const float4* guides, size_t npix, const DevCamera& cam) {
+    HIPCHK(c, hipMemcpyAsync(h.guides, guides, npix * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    h.cur ^= 1;
+    h.cam = cam;
+    h.valid = true;
+    return PRT_OK;
+}
+// the last call's half of an npix-pixel history, interleaved per pixel: {c, n}, {m1, m2, v, 0}
+static int read_history_planes(prt_ctx* c, const History& h, size_t npix, float* out8) {
+    std::vector<float4> p(2 * npix);
+    HIPCHK(c, hipMemcpy(p.data(), h.planes + 2 * npix * (size_t)h.cur, 2 * npix * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < npix; ++k) {
+        const float4 a = p[k], b = p[npix + k];
+        float* o = out8 + 8 * k;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    }
+    return PRT_OK;
+}
+
+extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    const prt_denoise_params p = params ? *params : default_denoise_params();
+    bool spatial = false;
+    int rc = denoise_checks(c, p, "prt_denoise", &spatial);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
+    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
+    float4* out = c->d_dn + 2 * c->npix;
+    launch_denoise(c->fb, c->S.q4, c->d_adapt, spatial, c->d_guides, c->width, c->rows, p, c->d_dn, c->d_dn + c->npix, c->d_dn_g, out, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return records_output(c, out, c->width, c->rows, nullptr, rgba, rgba8);
+}
+
+extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    const prt_denoise_params p = spatial ? *spatial : default_denoise_params();
+    const prt_temporal_params t = temporal ? *temporal : default_temporal_params();
+    int rc = temporal_param_checks(c, t, "prt_denoise_temporal");
+    if (rc) return rc;
+    bool spatial_var = false;
+    rc = denoise_checks(c, p, "prt_denoise_temporal", &spatial_var);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
+    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
+    // (a history without one of its buffers is empty: free_frame clears hist.valid, and only history_commit, which needs both, sets it)
+    if (!c->hist.planes) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->hist.planes), c->npix * 4 * sizeof(float4)));
+    if (!c->hist.guides) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->hist.guides), c->npix * 2 * sizeof(float4)));
+    const TemporalHistory h = history_begin(c->hist, c->npix);
+    float4* out = c->d_dn + 2 * c->npix;
+    // the context's motion plane when motion is on and the plane is the valid guides' own (prt.h)
+    const float4* motion = (c->motion && c->motion_valid) ? c->d_motion : nullptr;
+    launch_denoise_temporal(c->fb, c->S.q4, c->d_adapt, spatial_var, c->d_guides, c->width, c->rows, p, t, c->cam, h, c->d_dn,
+                            c->d_dn + c->npix, c->d_dn_g, out, c->stream, motion);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = history_commit(c, c->hist, c->d_guides, c->npix, c->cam))) return rc;
+    return records_output(c, out, c->width, c->rows, nullptr, rgba, rgba8);
+}
+
+extern "C" int prt_read_history(prt_ctx* c, float* out8) {
+    CTX_CHECK(c);
+    if (!out8 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_history: bad arguments");
+    if (!c->hist.valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_history: the history is empty (prt_denoise_temporal)");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    return read_history_planes(c, c->hist, c->npix, out8);
+}
+
+extern "C" int prt_reset_history(prt_ctx* c) {
+    CTX_CHECK(c);
+    c->hist.valid = false;
+    return PRT_OK;
+}
+
+// ---- denoiser inputs as records (prt.h prt_export_denoise_inputs, prt_denoise_records; pt_records.hip) ---------------------------------------
+extern "C" int prt_export_denoise_inputs(prt_ctx* c, void* device_records) {
+    CTX_CHECK(c);
+    if (!device_records || !aligned16(device_records) || !c->have_size)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_export_denoise_inputs: bad arguments (a 16-byte aligned device pointer, a context with a frame size)");
+    if (c->state_undefined) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: an earlier render call failed half-way; prt_reset or prt_write_state first");
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_export_denoise_inputs: a debug view is not a picture to filter");
+    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: nothing rendered since the reset");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool stats = c->stats_valid && c->d_adapt;
+    launch_records_export(c->fb, c->S.q4, stats ? c->d_adapt : nullptr, c->d_guides, c->width, c->rows, static_cast<float4*>(device_records), c->stream);
+    HIPCHK(c, hipGetLastError());
+    // (prt_copy_framebuffer_to_device: on a caller's stream the records are ordered like the caller's other work; the context's own stream is
+    // private: finish before returning)
+    if (c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+// prt_denoise_records (t, cam null) and prt_denoise_records_temporal (device_motion: null, or prt_denoise_records_temporal_motion's plane)
+static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params& p, const prt_temporal_params* t, const prt_camera* cam, int W,
+                           int H, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8, const void* device_motion = nullptr) {
+    const std::string w(who);
+    if (W < 1 || H < 1 || !device_records || !aligned16(device_records) || (device_rgba && !aligned16(device_rgba)) || !aligned16(device_motion))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": needs width >= 1, height >= 1 and 16-byte aligned device pointers (records not null)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)W * (size_t)H;
+    if (c->rec_cap < npix) {
+        free_dev(c->d_rec);
+        c->rec_cap = 0;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_rec), npix * (6 * sizeof(float4) + sizeof(float)) + sizeof(unsigned)));
+        c->rec_cap = npix;
+    }
+    float4* fb = c->d_rec;
+    float4* guides = fb + npix;
+    float4* buf0 = fb + 3 * npix;
+    float4* buf1 = fb + 4 * npix;
+    float4* out = fb + 5 * npix;
+    float* g = reinterpret_cast<float*>(fb + 6 * npix);
+    unsigned* d_flag = reinterpret_cast<unsigned*>(g + npix);
+    float4* var = t ? buf1 : buf0;                   // (where the variance step of launch_denoise_temporal / launch_denoise leaves {rgb, v})
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), c->stream));
+    launch_records_import(static_cast<const float4*>(device_records), W, H, fb, guides, var, d_flag, c->stream);
+    HIPCHK(c, hipGetLastError());
+    bool spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL;
+    if (!spatial) {
+        unsigned no_stats = 0;
+        HIPCHK(c, hipMemcpyAsync(&no_stats, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (no_stats && p.var_source == PRT_DENOISE_VAR_STATS)
+            return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs stats in every record (rendered by prt_render_adaptive)");
+        spatial = no_stats != 0;
+    }
+    if (spatial) launch_denoise_var(fb, nullptr, nullptr, true, W, H, var, c->stream);       // the 5x5 moments of the gathered colours
+    if (!t) {
+        float4* cur = buf0;
+        float4* nxt = buf1;
+        for (unsigned i = 0; i < p.passes; ++i) {
+            const bool last = i + 1 == p.passes;
+            launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, last ? out : nxt, c->stream);
+            float4* tmp = cur; cur = nxt; nxt = tmp;
+        }
+        HIPCHK(c, hipGetLastError());
+        return records_output(c, out, W, H, device_rgba, rgba, rgba8);
+    }
+    History& rh = c->rec_hist;
+    if (!rh.planes || !rh.guides || c->rec_hist_w != W || c->rec_hist_h != H) {
+        rh.valid = false;
+        free_dev(rh.planes);
+        free_dev(rh.guides);
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&rh.planes), npix * 4 * sizeof(float4)));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&rh.guides), npix * 2 * sizeof(float4)));
+        c->rec_hist_w = W; c->rec_hist_h = H;
+    }
+    DevCamera dc;
+    make_dev_camera(*cam, dc);
+    const TemporalHistory h = history_begin(rh, npix);
+    launch_denoise_temporal_var(fb, guides, W, H, p, *t, dc, h, buf0, buf1, g, out, c->stream, static_cast<const float4*>(device_motion));
+    HIPCHK(c, hipGetLastError());
+    if (int rc = history_commit(c, rh, guides, npix, dc)) return rc;
+    return records_output(c, out, W, H, device_rgba, rgba, rgba8);
+}
+
+extern "C" int prt_denoise_records(prt_ctx* c, const prt_denoise_params* params, int width, int height, const void* device_records,
+                                   void* device_rgba, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    const prt_denoise_params p = params ? *params : default_denoise_params();
+    int rc = denoise_param_checks(c, p, "prt_denoise_records");
+    if (rc) return rc;
+    return denoise_records(c, "prt_denoise_records", p, nullptr, nullptr, width, height, device_records, device_rgba, rgba, rgba8);
+}
+
+extern "C" int prt_denoise_records_temporal_motion(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal,
+                                                   const prt_camera* cam, int width, int height, const void* device_records,
+                                                   const void* device_motion, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    const prt_denoise_params p = spatial ? *spatial : default_denoise_params();
+    const prt_temporal_params t = temporal ? *temporal : default_temporal_params();
+    const char* who = device_motion ? "prt_denoise_records_temporal_motion" : "prt_denoise_records_temporal";
+    int rc = temporal_param_checks(c, t, who);
+    if (!rc) rc = denoise_param_checks(c, p, who);
+    if (rc) return rc;
+    if (!cam) return fail(c, PRT_ERR_INVALID_ARGUMENT, std::string(who) + ": null camera");
+    return denoise_records(c, who, p, &t, cam, width, height, device_records, device_rgba, rgba, rgba8, device_motion);
+}
+
+extern "C" int prt_denoise_records_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, const prt_camera* cam,
+                                            int width, int height, const void* device_records, void* device_rgba, float* rgba, uint8_t* rgba8) {
+    return prt_denoise_records_temporal_motion(c, spatial, temporal, cam, width, height, device_records, nullptr, device_rgba, rgba, rgba8);
+}
+
+extern "C" int prt_reset_records_history(prt_ctx* c) {
+    CTX_CHECK(c);
+    c->rec_hist.valid = false;
+    return PRT_OK;
+}
+
+extern "C" int prt_read_records_history(prt_ctx* c, int width, int height, float* out8) {
+    CTX_CHECK(c);
+    if (!out8 || width < 1 || height < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: bad arguments");
+    if (!c->rec_hist.valid || !c->rec_hist.planes)
+        return fail(c, PRT_ERR_NOT_READY, "prt_read_records_history: the record history is empty (prt_denoise_records_temporal)");
+    if (width != c->rec_hist_w || height != c->rec_hist_h)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: the record history has another size");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    return read_history_planes(c, c->rec_hist, (size_t)width * (size_t)height, out8);
+}

@@ -20,6 +20,9 @@ struct LaunchOpts {
 // what a launch ran: kernel variant, wave-count build, pixel-to-wave mapping (prt_kernel_variant)
 struct RenderLaunch { const char* name = ""; int waves = 0; int scatter = 0; int ordered = 0; int pool = 0; int pix_per_wave = 64; int adaptive = 0; int list = 0; };   // ordered: the tiles were taken in the launcher's order; adaptive: the PT_MATS_ADAPT build, list: over a live-pixel list
 
+// a tree beyond one XCD's L2 (more than 64 k node pairs): what the launchers and the render drivers choose by tree size, they choose by this
+inline bool big_tree(const DevScene& sc) { return sc.n_pairs > 65536u; }
+
 // launches the row of the variant table the scene and the options select (pt_variant.h select_variant)
 RenderLaunch launch_render(const DevScene& sc, const DevCamera& cam, const DevState& S, const FrameArgs& fa, float4* fb,
                            hipStream_t stream, const LaunchOpts& lo);

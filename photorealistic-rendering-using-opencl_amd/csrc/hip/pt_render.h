@@ -6,7 +6,7 @@
 // Launch geometry: one wave per workgroup, owning an 8x8 pixel tile (primary rays of one wave walk the same BVH nodes), or 64
 // pixels of 64 tiles in launches with few rounds of waves; dynamic LDS (DevScene::stack_levels x 256 B per workgroup) holds the
 // traversal stacks.  A 1920x1080 frame is 32 400 workgroups >> 256 CUs x 24 resident waves, rendered as two interleaved sets of
-// tiles on two streams (prt_api.cpp).
+// tiles on two streams (prt_api_render.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,14 +95,14 @@ static inline unsigned launch_grid(const DevScene& sc, const FrameArgs& fa, cons
     const unsigned tiles_x = ((unsigned)fa.width + 7u) / 8u, tiles_y = ((unsigned)fa.rows + 7u) / 8u;
     const unsigned n_tiles = tiles_x * tiles_y;
     const unsigned grid = fa.tile_first >= n_tiles ? 0u : (n_tiles - fa.tile_first + fa.tile_stride - 1) / fa.tile_stride;   // tiles of this sub-part
-    scatter = lo.scatter >= 0 ? lo.scatter != 0 : grid <= (sc.n_pairs > 65536u ? 24576u : 6144u);
+    scatter = lo.scatter >= 0 ? lo.scatter != 0 : grid <= (big_tree(sc) ? 24576u : 6144u);
     return grid;
 }
 // Pixels per wave (FrameArgs::sub_shift).  A launch whose tiles leave wave slots of the chip empty -- one rank's share of a frame
 // split N ways, a small frame -- lasts as long as its slowest wave, and a wave as long as its slowest lane's chain of segments (every
 // frame of a pixel follows its previous one: DESIGN.md s5); with 32 or 16 pixels per wave the maximum runs over fewer lanes, an
 // iteration walks for fewer of them, and the waves that would have idled hold the other halves.  `in_flight`: launches that share the
-// chip (the sub-parts of prt_api.cpp).  6 144 slots = 256 CUs x 4 SIMDs x 6 waves.
+// chip (the sub-parts of prt_api_render.cpp).  6 144 slots = 256 CUs x 4 SIMDs x 6 waves.
 static inline unsigned launch_sub_shift(const LaunchOpts& lo, unsigned grid, unsigned in_flight) {
     if (lo.pix_per_wave == 64) return 0u;
     if (lo.pix_per_wave == 32) return 1u;
@@ -142,9 +142,9 @@ static void launch_variant_w(const DevScene& sc, const DevCamera& cam, const Dev
     // every walk runs to its end (lock step) -- the share of 8 ranks 0.091 -> 0.077 s, of 4 ranks 0.117 -> 0.108 s, of 2 ranks 0.175 -> 0.209 s, the
     // whole frame 0.286 -> 0.340 s (tools/shard_time.py, 256 spp).  Through a big tree the bound stays (the same sweep: +-2 %, or worse).
     // (with fewer pixels per wave the thresholds shrink with the lanes that can walk at all)
-    const bool few_waves = sc.n_pairs <= 65536u && (unsigned long long)(grid >> fb_args.sub_shift) * (fa.tile_stride ? fa.tile_stride : 1u) <= 9216ull;
-    if (!fb_args.walk_min_lanes) fb_args.walk_min_lanes = few_waves ? 1u : max(2u, (sc.n_pairs > 65536u ? 20u : ((MEDIUM || scatter) ? 6u : 8u)) >> fb_args.sub_shift);
-    if (!fb_args.shadow_min_lanes) fb_args.shadow_min_lanes = sc.n_pairs > 65536u ? max(2u, 12u >> fb_args.sub_shift) : 1u;
+    const bool few_waves = !big_tree(sc) && (unsigned long long)(grid >> fb_args.sub_shift) * (fa.tile_stride ? fa.tile_stride : 1u) <= 9216ull;
+    if (!fb_args.walk_min_lanes) fb_args.walk_min_lanes = few_waves ? 1u : max(2u, (big_tree(sc) ? 20u : ((MEDIUM || scatter) ? 6u : 8u)) >> fb_args.sub_shift);
+    if (!fb_args.shadow_min_lanes) fb_args.shadow_min_lanes = big_tree(sc) ? max(2u, 12u >> fb_args.sub_shift) : 1u;
     if constexpr ((MATS & PT_MATS_ADAPT) != 0u)                 // (launch_variant: the adaptive build of the set)
         hipLaunchKernelGGL((render_kernel_adaptive<MATS, MEDIUM, WAVES>), dim3(grid), dim3(PT_BLOCK), lds, stream, sc, cam, S, fb_args, fb);
     else if (WAVES == PT_BIG_WAVES && (fb_args.tile_order || fb_args.tile_cost))     // (prt_render_spp asks for it through big trees only)
@@ -169,7 +169,7 @@ RenderLaunch launch_variant(const Variant& v, const DevScene& sc, const DevCamer
     // the raymarcher's latency wants the sixth wave more than its spills cost) -- so the run-time dispatch runs its 96-register build with or
     // without a medium (and with it the debug-view, light-pick and environment-sampling sets, which are that dispatch plus a flag), SDF its 80.
     constexpr bool five = !(MATS & PT_MATS_SDF) && ((MATS & ~PT_MATS_FLAGS) == 0u || (!MEDIUM && (MATS & PRT_MAT_COAT) != 0u));
-    const int waves = lo.waves ? lo.waves : (sc.n_pairs > 65536u ? PT_BIG_WAVES : ((scatter || five) ? PT_WAVES : PT_BIG_WAVES));
+    const int waves = lo.waves ? lo.waves : (big_tree(sc) ? PT_BIG_WAVES : ((scatter || five) ? PT_WAVES : PT_BIG_WAVES));
     RenderLaunch r;
     r.name = v.name; r.scatter = scatter ? 1 : 0;
     if (fa.adapt) {

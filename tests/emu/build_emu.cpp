@@ -1,6 +1,6 @@
 // tests/emu/build_emu.cpp -- TEST INFRASTRUCTURE: the bodies of the build kernels (csrc/hip/pt_build.h) and of the refit kernels (pt_refit.h)
 // compiled for the host and run serially over pack_scene's output, in the order the device's launches impose, with std::sort / a running sum
-// where the device calls the library's sorts and scan, and with the bookkeeping of prt_rebuild_bvh_device (csrc/hip/prt_api.cpp) around them:
+// where the device calls the library's sorts and scan, and with the bookkeeping of prt_rebuild_bvh_device (csrc/hip/prt_api_scene.cpp) around them:
 // build into fresh tables, swap at the end, carry the normals and the motion snapshot.  tests/emu/build_api.py binds it.  With
 // -DBUILD_EMU_MAIN a stand-alone program for sanitizer runs (see main below).
 #include <algorithm>

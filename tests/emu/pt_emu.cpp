@@ -168,7 +168,7 @@ LaunchOpts env_launch_opts() {
 }  // namespace
 
 // same arguments as oracle/pt_oracle.h's pto_job, plus the schedule.  Returns 0, or the prt error code of pack_scene.
-// filter_kind / filter_r / filter_tab: prt_set_pixel_filter's state as prt_api.cpp puts it into FrameArgs (tab: T[0 .. 256] of the Gaussian and
+// filter_kind / filter_r / filter_tab: prt_set_pixel_filter's state as prt_ctx.h (frame_args) puts it into FrameArgs (tab: T[0 .. 256] of the Gaussian and
 // Blackman-Harris kinds, else null).  A kind other than PRT_FILTER_NONE runs the PT_MATS_FILTER rows, and is refused (PRT_ERR_UNSUPPORTED) for
 // the configs prt_set_pixel_filter refuses (filter_unsupported).  PT_EMU_GENERIC=1 / PT_EMU_ANY_DIST=1: LaunchOpts::generic / any_dist.
 extern "C" int emu_render(const prt_config* cfg, const prt_scene_desc* desc, const prt_camera* camera, const float* env_rgb, int env_w, int env_h,

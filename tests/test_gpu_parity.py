@@ -732,6 +732,53 @@ def test_a_launch_that_does_not_report_aborts_the_render(prt):
     r.close()
 
 
+@pytest.mark.parametrize("lists", [False, True], ids=["tiles", "lists"])
+def test_an_adaptive_launch_that_does_not_report_aborts_the_render(prt, monkeypatch, lists):
+    """prt_render_adaptive launches its sub-parts through the same path as prt_render_spp, so a report that never arrives ends it the same
+    way: PRT_ERR_HIP, the state unusable until prt_reset, and after the reset the context renders what a fresh one renders, bit for bit.
+    24 x 20 pixels = 3 x 3 tiles with ragged right and bottom edges on two streams (5 and 4 tiles), 8 frames per launch: several rounds;
+    `lists`: list launches from the first freeze on (the pixels of the light freeze at min_spp: their luminance has no spread)."""
+    W, H, MIN, MAX, REL = 24, 20, 2, 8, 0.2
+    monkeypatch.setenv("PRT_STREAMS", "2")
+    seeds = prt.seed_pairs(MAX * 16 + 64)
+    scene = prt.HostScene("cornell_diffuse.json")
+
+    def renderer():
+        r = prt.Renderer(scene.config(), device=0)
+        r.upload_scene(scene)
+        r.set_camera(prt.default_camera(W, H))
+        r.resize(W, H)
+        r.set_option("frames_per_launch", 8)
+        if lists:
+            r.set_option("compact", 1)
+            r.set_option("compact_below", 100)
+        return r
+
+    r = renderer()
+    r.set_option("test_drop_report", 1)
+    with pytest.raises(prt.PrtError) as ei:
+        r.render_adaptive(seeds, MIN, MAX, REL)
+    assert ei.value.code == prt.PRT_ERR_HIP and "without reporting" in str(ei.value), str(ei.value)
+    with pytest.raises(prt.PrtError) as ei:                  # the state may hold run-ahead leads: unusable until reset
+        r.render_adaptive(seeds, MIN, MAX, REL)
+    assert ei.value.code == prt.PRT_ERR_NOT_READY and "half-way" in str(ei.value), str(ei.value)
+    r.set_option("test_drop_report", 0)
+    r.reset()
+    r.render_adaptive(seeds, MIN, MAX, REL)
+    assert r.stats().concurrent == 2
+    rep = r.adaptive_report()
+    print("adaptive report: tile launches %d, list launches %d, list builds %d" % (rep.tile_launches, rep.list_launches, rep.list_builds))
+    if lists:
+        assert rep.list_launches >= 1
+    got = r.read_framebuffer()
+    r.close()
+    fresh = renderer()
+    fresh.render_adaptive(seeds, MIN, MAX, REL)
+    want = fresh.read_framebuffer()
+    fresh.close()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
 @pytest.mark.parametrize("case", ["config2", "config3a", "config4"])
 def test_hip_agrees_with_the_reference_under_glibc_math(prt, case):
     """Math this repository did not write, ON THE GPU PATH.  Every bit-exact test here is relative to include/prt_detmath.h (it feeds the
