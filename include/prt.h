@@ -156,7 +156,8 @@ int prt_upload_scene(prt_ctx* ctx, const prt_scene_desc* scene);
  * static: moving a triangle there means rebuilding the tree and creating every buffer again, as prt_upload_scene does here).  The tree's
  * topology is kept -- which node is whose child, which triangles a leaf holds --; the triangle records and every box are recomputed from the
  * new vertices, bottom-up.  T, primitive_indices and bvh_nodes are those of the last prt_upload_scene; `vertices` and `normals` have the layout
- * of prt_scene_desc: float4[3*T], de-indexed, xyz used.  normals == NULL keeps the uploaded normals (they are not read).
+ * of prt_scene_desc: float4[3*T], de-indexed, xyz used.  normals == NULL keeps the uploaded normals (they are not read) -- or,
+ * with prt_set_smooth_normals (below), generates them from the new vertices.
  *   prt_update_vertices          host memory: staged through a device buffer of the context (allocated on first use), then the device path.
  *   prt_update_vertices_device   device memory of the context's device, 16-byte aligned; ordered on the context's stream, complete on return
  *                                (the caller's buffers may be reused then).
@@ -240,6 +241,61 @@ int prt_read_bvh_bounds(prt_ctx* ctx, float* bounds6);
 int prt_rebuild_bvh(prt_ctx* ctx, const float* vertices, const float* normals, uint32_t max_leaf);
 int prt_rebuild_bvh_device(prt_ctx* ctx, const void* d_vertices, const void* d_normals, uint32_t max_leaf);
 int prt_read_bvh(prt_ctx* ctx, prt_bvh_node* nodes, uint32_t* node_count, uint64_t* primitive_indices);
+
+/* Deforming geometry: smooth shading normals regenerated on the device (no counterpart in the reference, whose normals come from the importer
+ * once: GenSmoothNormals of assimp, csrc/host/model_loader.cpp smooth_missing_normals here).  Opt-in; off (the default) every bit of every
+ * result is what it is without these calls: normals == NULL keeps / carries the normal records, which after a deformation are the rest
+ * pose's.  The caller gives the mesh's smoothing topology once; from then on every prt_update_vertices, prt_update_vertices_device,
+ * prt_rebuild_bvh and prt_rebuild_bvh_device called with normals == NULL generates the float4[3T] normals from the new vertices -- after the
+ * finite-vertex check has passed, into a buffer of the context, so a refused call still leaves the scene exactly as it was -- and proceeds
+ * exactly as if that array had been passed as `normals` (prt_rebuild_bvh's refusal of normals == NULL under a tree that does not reference
+ * every triangle does not apply then: there is a normal for every corner).  Explicit normals are used as without the topology;
+ * prt_set_motion reads geometry records only and is unaffected.
+ * Corner c = 3i + k is vertex k of triangle i of prt_scene_desc::vertices.  The topology is a group id per corner: the corners of one group
+ * share their faces' normals.  All f32, no contraction; sqrtf and / correctly rounded:
+ *   Face i, with a = v[3i], b = v[3i+1], c = v[3i+2] (xyz):
+ *       u = b - a;   w = c - a
+ *       r = (u.y*w.z - u.z*w.y,  u.z*w.x - u.x*w.z,  u.x*w.y - u.y*w.x)
+ *       l = sqrtf((r.x*r.x + r.y*r.y) + r.z*r.z);     f = l > 0 ? r / l (per component) : r
+ *     (unit_face_normal of the loader.  It points the opposite way from the triangle record's n = cross(e1, e2), kernels/geometry/triangle.cl:15,
+ *     and is not derived from that record: the signs of zeros would differ.)
+ *   Corner c of face i, in group g with members m_0 < m_1 < ... (corner indices, c itself among them; face j = m / 3):
+ *       s = 0
+ *       for each member in that order:
+ *           d = (f_j.x*f_i.x + f_j.y*f_i.y) + f_j.z*f_i.z
+ *           if (d >= crease_cos)  s += (PRT_NORMALS_UNIT ? f_j : r_j)    per component
+ *       L = sqrtf((s.x*s.x + s.y*s.y) + s.z*s.z);     normal = L > 0 ? s / L : f_i;     lane 3 = 0
+ *     A face counts once per corner it has in the group.  NaN and overflow go through the formulas as they stand; a NaN d fails the test.
+ *   With PRT_NORMALS_UNIT, PRT_LOADER_CREASE_COS and the groups of prt_weld_corners this is smooth_missing_normals operation for operation, for
+ *   a single-mesh model.
+ * Deterministic, no atomics: the result depends on the vertices and the topology only; tile, row-block and rank contexts that each set the
+ * same topology and update stay bit-identical in union to one whole-frame context.
+ * Cost: two launches in front of the refit's record pass -- one lane per triangle, then one lane per corner that gathers one 16-byte face
+ * record per member of its group: the sum over the groups of valence^2 gathers.  A pole of valence 1000 is slow but correct.
+ * Device memory, all allocated by prt_set_smooth_normals (an update cannot fail on an allocation after the scene has been touched), per
+ * triangle: 12 bytes of ids, 12 of the member table, 16 of face records {f, l} (PRT_NORMALS_AREA: 16 more, {r, 0}) and 48 of generated
+ * normals -- 88 (104) bytes -- plus 4 * (n_groups + 1) bytes of group offsets.
+ * prt_weld_corners (host only: no device, no context, as prt_env_cdf): corners whose positions are bit-identical after x + 0.0f per component
+ *   (so -0 equals +0: the key of smooth_missing_normals) form one group; groups are numbered in order of first appearance by corner index.
+ *   PRT_ERR_INVALID_ARGUMENT (message: prt_last_global_error) for null pointers, T == 0 or a non-finite x, y or z.  Callers who want hard
+ *   edges or seams pass ids of their own to prt_set_smooth_normals.
+ * prt_set_smooth_normals: copies the ids, builds the group-to-members table on the host (a stable counting sort: a group's members in
+ *   ascending corner order; an id no corner names is an empty group) and uploads it.  Needs an uploaded scene with T > 0, else
+ *   PRT_ERR_NOT_READY.  Refused with PRT_ERR_INVALID_ARGUMENT, each leaving the previous topology in force: an id >= n_groups, n_groups == 0,
+ *   an unknown weighting, a crease_cos that is not finite.  PRT_ERR_UNSUPPORTED for T > PRT_MAX_TRIANGLE_SLOTS (corners are 32-bit indices).
+ *   corner_group == NULL turns the feature off and frees the buffers.  Setting it changes nothing of the scene by itself: records, guides and
+ *   histories keep their bits until the next update or rebuild.  It survives prt_reset, prt_resize, tile and row-block calls, camera changes,
+ *   updates and rebuilds; prt_upload_scene turns it off (T may have changed).
+ * prt_read_normals: the current normal records de-slotted into corner order, float4[3T]: for triangle i the three normals of a slot that
+ *   holds it (where leaves share a triangle their records are equal), lane 3 = 0; a triangle that no slot holds reads as zeros.  For an
+ *   uploaded, a refitted and a rebuilt tree, smooth normals on or off.  PRT_ERR_NOT_READY without a scene, PRT_ERR_INVALID_ARGUMENT for a
+ *   null pointer. */
+#define PRT_NORMALS_UNIT 0u   /* sum of the faces' unit normals: the loader's / assimp's rule */
+#define PRT_NORMALS_AREA 1u   /* sum of the faces' raw cross products: area-weighted */
+#define PRT_LOADER_CREASE_COS (-0.99619470f)   /* cos(175 deg): the smoothing-angle limit of the loader */
+int prt_weld_corners(const float* vertices /* float4[3T] */, uint32_t T, uint32_t* corner_group /* 3T */, uint32_t* n_groups);
+int prt_set_smooth_normals(prt_ctx* ctx, const uint32_t* corner_group /* 3T, NULL = off */, uint32_t n_groups, uint32_t weighting, float crease_cos);
+int prt_read_normals(prt_ctx* ctx, float* normals /* float4[3T] */);
 
 /* enqueueWriteBuffer(cl_camera), src/main.cpp:294-297 (every frame in the reference). */
 int prt_set_camera(prt_ctx* ctx, const prt_camera* cam);

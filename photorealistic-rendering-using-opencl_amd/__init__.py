@@ -15,14 +15,14 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import PIXEL_FILTERS, PIXEL_FILTER_DEFAULT_RADIUS, DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
+from ._capi import NORMALS_WEIGHTINGS, LOADER_CREASE_COS, PIXEL_FILTERS,PIXEL_FILTER_DEFAULT_RADIUS, DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["PIXEL_FILTERS", "PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "env_cdf", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["NORMALS_WEIGHTINGS", "LOADER_CREASE_COS", "weld_corners", "PIXEL_FILTERS","PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "env_cdf", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -210,6 +210,20 @@ def env_cdf(rgb):
     return rows, cols
 
 
+def weld_corners(vertices):
+    """prt_weld_corners: (groups uint32 [3T], n_groups) of vertices float32 [3T, 4] -- corners at bit-identical positions (-0 = +0) share a
+    group, groups numbered by first appearance (prt.h): the smoothing topology of the loader, for Renderer.set_smooth_normals.  Needs no GPU"""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    if v.size == 0 or v.size % 12:
+        raise ValueError("weld_corners: needs float32 [3T, 4] with T > 0")
+    T = v.size // 12
+    groups, n = np.zeros(3 * T, dtype=np.uint32), C.c_uint32(0)
+    rc = load_library().prt_weld_corners(v.ctypes.data_as(C.c_void_p), T, groups.ctypes.data_as(C.c_void_p), C.byref(n))
+    if rc:
+        raise PrtError("prt_weld_corners failed (%d): %s" % (rc, load_library().prt_last_global_error().decode()), rc)
+    return groups, int(n.value)
+
+
 def scene_arrays(desc):
     """numpy views (no copies: `desc`'s owner must stay alive) of a SceneDesc's triangle buffers: vertices and normals float32 [3T, 4],
     primitive_indices uint64 [T], nodes [bvh_node_count] of _capi.BVH_NODE_DTYPE"""
@@ -360,6 +374,31 @@ class Renderer:
         count = C.c_uint32(0)
         self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
         self.bvh_node_count = int(count.value)
+
+    def set_smooth_normals(self, groups, n_groups=None, weighting="unit", crease_cos=LOADER_CREASE_COS):
+        """prt_set_smooth_normals: the smoothing topology of the uploaded mesh -- groups uint32 [3T], one id per corner (weld_corners gives the
+        loader's); n_groups None = the largest id + 1; weighting "unit" (the loader's rule) or "area".  From then on update_vertices and
+        rebuild_bvh with normals None generate the normals from the new vertices on the device (prt.h).  groups None turns it off"""
+        if groups is None:
+            self._chk(self.lib.prt_set_smooth_normals(self.ctx, None, 0, 0, C.c_float(0.0)), "prt_set_smooth_normals")
+            return
+        g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        if g.size < 3 * getattr(self, "triangle_count", 0):
+            raise ValueError("set_smooth_normals: needs %d group ids" % (3 * getattr(self, "triangle_count", 0)))
+        if isinstance(weighting, str):
+            if weighting not in NORMALS_WEIGHTINGS:
+                raise ValueError("unknown weighting %r (one of %s)" % (weighting, ", ".join(NORMALS_WEIGHTINGS)))
+            weighting = NORMALS_WEIGHTINGS[weighting]
+        if n_groups is None:
+            n_groups = int(g.max()) + 1 if g.size else 0
+        self._chk(self.lib.prt_set_smooth_normals(self.ctx, g.ctypes.data_as(C.c_void_p), int(n_groups), int(weighting), C.c_float(crease_cos)),
+                  "prt_set_smooth_normals")
+
+    def read_normals(self):
+        """prt_read_normals: float32 [3T, 4], the current normal records in corner order (lane 3 = 0; zeros for a triangle no leaf holds)"""
+        out = np.zeros((3 * getattr(self, "triangle_count", 0), 4), dtype=np.float32)
+        self._chk(self.lib.prt_read_normals(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_normals")
+        return out
 
     def read_bvh(self):
         """prt_read_bvh: (nodes [node_count] of _capi.BVH_NODE_DTYPE, primitive_indices uint64 [T]): the current tree in the reference's layout,

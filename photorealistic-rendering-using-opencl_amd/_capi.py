@@ -108,6 +108,10 @@ PATH_STATE_DTYPE = [("origin", "<f4", 4), ("dir", "<f4", 4), ("time", "<f4"), ("
 # numpy view of the 36-byte prt_bvh_node (BvhNode above)
 BVH_NODE_DTYPE = [("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)]
 
+# prt_set_smooth_normals: the weightings by name and the loader's crease (PRT_NORMALS_*, PRT_LOADER_CREASE_COS of include/prt.h)
+NORMALS_WEIGHTINGS = {"unit": 0, "area": 1}
+LOADER_CREASE_COS = -0.99619470
+
 # (name, restype, argtypes) of every symbol include/prt.h declares
 PRT_API = [
     ("prt_create", C.c_int, [C.c_int, C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -119,6 +123,9 @@ PRT_API = [
     ("prt_rebuild_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_rebuild_bvh_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_weld_corners", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("prt_set_smooth_normals", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]),
+    ("prt_read_normals", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_set_camera", C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     ("prt_upload_envmap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("prt_resize", C.c_int, [C.c_void_p, C.c_int, C.c_int]),

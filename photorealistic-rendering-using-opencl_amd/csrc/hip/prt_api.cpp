@@ -7,6 +7,7 @@
 
 #include "prt_ctx.h"
 #include "pt_filter.h"
+#include "pt_normals.h"
 #include "pt_pack.h"
 #include "pt_variant.h"
 
@@ -114,6 +115,7 @@ static void free_scene(prt_ctx* c) {
     c->build_T = 0;
     c->cap_pairs = c->cap_slots = c->cap_prev = 0;
     c->rebuilt = false;
+    free_smooth(c);
 }
 
 extern "C" void prt_destroy(prt_ctx* c) {
@@ -320,6 +322,16 @@ extern "C" int prt_env_cdf(const float* rgb, int w, int h, float* rows, float* c
     build_env_cdf(rgb, w, h, r, c);
     std::memcpy(rows, r.data(), r.size() * sizeof(float));
     std::memcpy(cols, c.data(), c.size() * sizeof(float));
+    return PRT_OK;
+}
+
+// host only, as prt_env_cdf: no device, no context (the rule: pt_normals.h normals_weld)
+extern "C" int prt_weld_corners(const float* vertices, uint32_t T, uint32_t* corner_group, uint32_t* n_groups) {
+    if (!vertices || !corner_group || !n_groups || T == 0) { g_global_error = "prt_weld_corners: bad arguments"; return PRT_ERR_INVALID_ARGUMENT; }
+    if (!normals_weld(vertices, T, corner_group, n_groups)) {
+        g_global_error = "prt_weld_corners: a vertex with a non-finite x, y or z";
+        return PRT_ERR_INVALID_ARGUMENT;
+    }
     return PRT_OK;
 }
 

@@ -1,9 +1,12 @@
 // prt_api_scene.cpp -- the scene calls of the C ABI (include/prt.h): upload, vertex updates with a refit, rebuilds, the tree's read-backs,
-// motion on / off.
+// motion on / off, smooth normals.
+#include <cmath>
+#include <new>
 #include <utility>
 
 #include "prt_ctx.h"
 #include "pt_build.h"
+#include "pt_normals.h"
 #include "pt_pack.h"
 #include "pt_refit.h"
 
@@ -27,6 +30,7 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     c->snap_valid = false;
     c->cap_prev = 0;
     c->rebuilt = false;
+    free_smooth(c);                                  // (the smoothing topology is the old mesh's: T may have changed)
     c->n_slots = ps.slot_vtx.size();
     c->cap_pairs = ps.pairs.empty() ? 1 : ps.pairs.size();         // (what upload() below allocates, in records)
     c->cap_slots = ps.tg.empty() ? 1 : ps.tg.size();
@@ -113,6 +117,19 @@ static int stage_vertices(prt_ctx* c, const float* vertices, const float* normal
     return PRT_OK;
 }
 
+// smooth normals on and no normals given (prt.h prt_set_smooth_normals): the normals of the new vertices into the context's own buffer, two
+// launches on the context's stream; the caller passes the buffer on as if it had been given.  Called once the finite-vertex check has passed:
+// only scratch of the context is written
+static const float* generate_normals(prt_ctx* c, const float* v) {
+    SmoothTables t;
+    t.corner_group = static_cast<const uint32_t*>(c->d_sm_group); t.group_first = static_cast<const uint32_t*>(c->d_sm_first);
+    t.member_face = static_cast<const uint32_t*>(c->d_sm_member);
+    t.face_f = c->d_sm_face_f; t.face_r = c->smooth_weighting == PRT_NORMALS_AREA ? c->d_sm_face_r : nullptr;
+    t.n_tris = c->n_tris; t.crease_cos = c->smooth_crease;
+    launch_smooth_normals(t, v, static_cast<float*>(c->d_sm_nrm), c->stream);
+    return static_cast<const float*>(c->d_sm_nrm);
+}
+
 extern "C" int prt_update_vertices_device(prt_ctx* c, const void* d_vertices, const void* d_normals) {
     CTX_CHECK(c);
     int rc = refit_prepare(c, d_vertices, "prt_update_vertices_device");
@@ -149,6 +166,7 @@ extern "C" int prt_update_vertices_device(prt_ctx* c, const void* d_vertices, co
     c->guides_valid = false;
     forget_tile_orders(c);
     c->refitted = true;
+    if (c->smooth && !n) n = generate_normals(c, v);
     launch_refit(t, v, n, static_cast<NodePair*>(c->d_pairs), static_cast<TriGeom*>(c->d_tri_geom), static_cast<TriNrm*>(c->d_tri_nrm),
                  static_cast<float*>(c->d_refit_root), c->stream);
     HIPCHK(c, hipGetLastError());
@@ -208,7 +226,8 @@ extern "C" int prt_rebuild_bvh_device(prt_ctx* c, const void* d_vertices, const 
     if (!max_leaf) max_leaf = PT_BUILD_DEFAULT_LEAF;
     const uint32_t T = c->n_tris;
     const bool leaf_root = T <= max_leaf;
-    const bool carry_nrm = d_normals == nullptr;
+    const bool generate = c->smooth && d_normals == nullptr;       // (smooth normals: a normal for every corner, nothing to carry)
+    const bool carry_nrm = d_normals == nullptr && !generate;
     // the new tables: one slot per triangle, and room for the T - 1 pairs of a tree of single-triangle leaves
     if (int rc = table_limits(c, "prt_rebuild_bvh", T, T > 1u ? T - 1u : 1u)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -263,6 +282,7 @@ extern "C" int prt_rebuild_bvh_device(prt_ctx* c, const void* d_vertices, const 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (bad[0]) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_rebuild_bvh: a vertex with a non-finite x, y or z (the scene is unchanged)");
     if (bad[1]) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_rebuild_bvh: normals == NULL, and the current tree holds no normals for some triangle (the scene is unchanged)");
+    if (generate) n = generate_normals(c, v);
     // rules 1 - 7, then the one small copy the host needs
     HIPCHK(c, launch_build_tree(w, v, T, max_leaf, static_cast<NodePair*>(sp.pairs), static_cast<uint32_t*>(sp.slot_vtx), static_cast<uint32_t*>(sp.level_pairs), c->stream));
     BuildHeader h;
@@ -377,6 +397,84 @@ extern "C" int prt_set_motion(prt_ctx* c, int enable) {
         free_dev(c->d_tri_prev);
         c->cap_prev = 0;
         c->snap_valid = false;
+    }
+    return PRT_OK;
+}
+
+// ---- smooth shading normals regenerated from new vertices (prt.h prt_set_smooth_normals; pt_normals.hip) ---------------------------------------
+extern "C" int prt_set_smooth_normals(prt_ctx* c, const uint32_t* corner_group, uint32_t n_groups, uint32_t weighting, float crease_cos) {
+    CTX_CHECK(c);
+    if (!c->have_scene || c->n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_smooth_normals: no scene with triangles uploaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!corner_group) {                                   // off: nothing of the scene changes, the buffers go
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        free_smooth(c);
+        return PRT_OK;
+    }
+    // every refusal before anything of the topology in force is touched
+    if (n_groups == 0) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: n_groups is 0 (the topology in force stays)");
+    if (weighting != PRT_NORMALS_UNIT && weighting != PRT_NORMALS_AREA)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: unknown weighting (the topology in force stays)");
+    if (!std::isfinite(crease_cos)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: crease_cos is not finite (the topology in force stays)");
+    const uint32_t T = c->n_tris;
+    if (T > PRT_MAX_TRIANGLE_SLOTS)
+        return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_smooth_normals: more than PRT_MAX_TRIANGLE_SLOTS triangles (corners are addressed by 32-bit indices)");
+    std::vector<uint32_t> group_first, member_face;
+    bool ids_ok = false;
+    try { ids_ok = normals_group_table(corner_group, T, n_groups, group_first, member_face); }
+    catch (const std::bad_alloc&) { return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_smooth_normals: no host memory for a table of n_groups + 1 entries (the topology in force stays)"); }
+    if (!ids_ok) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: a group id >= n_groups (the topology in force stays)");
+    // everything a generation will ever need, into buffers of their own: a failure here leaves the topology in force as it was
+    const size_t corners = 3 * (size_t)T;
+    void* nb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};       // group, first, member, face_f, face_r, nrm
+    const size_t bytes[6] = {corners * 4, group_first.size() * 4, corners * 4, (size_t)T * 16, weighting == PRT_NORMALS_AREA ? (size_t)T * 16 : 0, corners * 16};
+    const void* src[6] = {corner_group, group_first.data(), member_face.data(), nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 6 && e == hipSuccess; ++k) {
+        if (!bytes[k]) continue;
+        e = hipMalloc(&nb[k], bytes[k]);
+        if (e == hipSuccess && src[k]) e = hipMemcpy(nb[k], src[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        for (void*& p : nb) free_dev(p);
+        c->err = std::string("prt_set_smooth_normals: ") + hipGetErrorString(e);
+        return PRT_ERR_HIP;
+    }
+    free_smooth(c);
+    c->d_sm_group = nb[0]; c->d_sm_first = nb[1]; c->d_sm_member = nb[2]; c->d_sm_face_f = nb[3]; c->d_sm_face_r = nb[4]; c->d_sm_nrm = nb[5];
+    c->smooth_weighting = weighting; c->smooth_crease = crease_cos;
+    c->smooth = true;
+    return PRT_OK;
+}
+
+extern "C" int prt_read_normals(prt_ctx* c, float* normals) {
+    CTX_CHECK(c);
+    if (!c->have_scene) return fail(c, PRT_ERR_NOT_READY, "prt_read_normals: no scene uploaded");
+    if (!normals) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_normals: null pointer");
+    const size_t T = c->n_tris;
+    if (!T) return PRT_OK;
+    std::memset(normals, 0, 3 * T * 4 * sizeof(float));
+    if (!c->n_slots) return PRT_OK;
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    // the slot table: the uploaded tree's on the host, a rebuilt tree's on the device only
+    std::vector<uint32_t> sv;
+    if (c->rebuilt) {
+        sv.resize(c->n_slots);
+        HIPCHK(c, hipMemcpy(sv.data(), c->d_slot_vtx, sv.size() * 4, hipMemcpyDeviceToHost));
+    }
+    const std::vector<uint32_t>& slot_vtx = c->rebuilt ? sv : c->slot_vtx;
+    std::vector<TriNrm> tn(c->n_slots);
+    HIPCHK(c, hipMemcpy(tn.data(), c->d_tri_nrm, tn.size() * sizeof(TriNrm), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < slot_vtx.size() && s < tn.size(); ++s) {
+        const size_t fv = slot_vtx[s];
+        if (fv + 3 > 3 * T) continue;
+        const float* rec = reinterpret_cast<const float*>(&tn[s]);
+        for (int k = 0; k < 3; ++k) {
+            float* o = normals + 4 * (fv + k);
+            o[0] = rec[4 * k]; o[1] = rec[4 * k + 1]; o[2] = rec[4 * k + 2]; o[3] = 0.0f;
+        }
     }
     return PRT_OK;
 }

@@ -162,6 +162,14 @@ struct prt_ctx {
     bool snap_valid = false;
     float4* d_motion = nullptr;
     bool motion_valid = false;
+    // prt_set_smooth_normals (pt_normals.hip): the smoothing topology of the uploaded mesh on the device -- the group of every corner, the
+    // group-to-members table -- and what a generation writes: the face buffer (d_sm_face_r for the area weighting only) and the generated
+    // normals (float4[3T]).  All allocated by prt_set_smooth_normals, freed by turning it off, by prt_upload_scene and with the scene
+    bool smooth = false;
+    uint32_t smooth_weighting = 0;
+    float smooth_crease = 0.0f;
+    void* d_sm_group = nullptr; void* d_sm_first = nullptr; void* d_sm_member = nullptr;
+    void* d_sm_face_f = nullptr; void* d_sm_face_r = nullptr; void* d_sm_nrm = nullptr;
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -172,6 +180,13 @@ inline int fail(prt_ctx* ctx, int code, const std::string& msg) { ctx->err = msg
 
 template <typename T>
 void free_dev(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+// prt_set_smooth_normals off: the topology and the generation's buffers go
+inline void free_smooth(prt_ctx* c) {
+    free_dev(c->d_sm_group); free_dev(c->d_sm_first); free_dev(c->d_sm_member);
+    free_dev(c->d_sm_face_f); free_dev(c->d_sm_face_r); free_dev(c->d_sm_nrm);
+    c->smooth = false;
+}
 
 // measured tile orders are the scene's, the view's and the frame's: whatever changes one of them forgets them
 inline void forget_tile_orders(prt_ctx* c) { for (int j = 0; j < prt_ctx::MAX_SUB; ++j) c->have_order[j] = false; }

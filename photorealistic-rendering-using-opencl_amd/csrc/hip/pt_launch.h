@@ -108,6 +108,18 @@ void launch_refit_check(const float* vertices, size_t n_vertices, uint32_t* flag
 // into root6 (device, 6 floats)
 void launch_refit(const RefitTables& t, const float* vertices, const float* normals, NodePair* pairs, TriGeom* tri_geom, TriNrm* tri_nrm,
                   float* root6, hipStream_t stream);
+// pt_normals.hip.  prt_set_smooth_normals: the topology on the device and the face buffer (all device memory)
+struct SmoothTables {
+    const uint32_t* corner_group;   // 3 n_tris: the group of every corner
+    const uint32_t* group_first;    // n_groups + 1: group g is member_face[group_first[g] .. group_first[g + 1])
+    const uint32_t* member_face;    // 3 n_tris: the faces of the groups' corners, ascending corner order within a group
+    void* face_f;                   // n_tris x 16 bytes {f, l}: written by the face kernel, gathered by the corner kernel
+    void* face_r;                   // n_tris x 16 bytes {r, 0} for the area weighting, null for the unit weighting
+    uint32_t n_tris;
+    float crease_cos;
+};
+// the face records of `vertices`, then one normal per corner into `normals` (device, float4[3 n_tris], 16-byte aligned): two launches
+void launch_smooth_normals(const SmoothTables& t, const float* vertices, float* normals, hipStream_t stream);
 // pt_build.hip.  prt_rebuild_bvh: the scratch of one build over T triangles, carved out of one device allocation of the context
 struct BuildNode;
 struct BuildExtent;

@@ -13,6 +13,10 @@ With --phase motion (prt_set_motion): what the motion mode adds, two contexts (m
 --calls rounds: an update with and without the snapshot copy (a small guide render between the timed calls consumes the snapshot, so every
 timed update of the "on" arm takes one), prt_render_guides (4 samples) at 1920x1080 with the motion instance and with the plain one, and
 prt_denoise_temporal with and without the plane.
+With --phase normals (prt_set_smooth_normals): an update of the scene's mesh from device buffers with GENERATED normals (normals NULL, the
+topology set; unit and area weighting) against the same update with the caller's device normals -- the existing path, the baseline --, the
+arms alternated call by call on contexts of the same scene, medians over --calls rounds, each call complete on return; and the kernels of one
+generated update from a rocprofv3 run of its own (--phase normals-kernels).  Both times and their ratio are reported; there is no pass mark.
 Kernel times: from `rocprofv3 --kernel-trace --stats` in a run of its own (this script with --phase kernels).  One JSON document on stdout
 (and into --out).
 
@@ -219,6 +223,107 @@ def motion_phase(prt, name, rounds, width=1920, height=1080):
     return out
 
 
+def normals_phase(prt, name, rounds):
+    """the cost of generated normals on scene `name`: update_vertices from device buffers, {caller's normals, generated unit, generated area}"""
+    import torch
+    scene = _scene(prt, name)
+    a = prt.scene_arrays(scene.desc)
+    v0, n0 = a["vertices"].copy(), a["normals"].copy()
+    t0 = time.perf_counter()
+    groups, n_groups = prt.weld_corners(v0)
+    weld_ms = 1e3 * (time.perf_counter() - t0)
+    valence = np.bincount(groups)
+    cfg = scene.config()
+    dn = torch.from_numpy(n0).cuda()
+    dv = [torch.from_numpy(deform(v0, 0.01, phase=0.05 * k)).cuda() for k in range(2)]
+    torch.cuda.synchronize()
+    ctx, set_ms = {}, {}
+    for arm in ("unit", "area"):
+        r = prt.Renderer(cfg, device=0)
+        r.upload_scene(scene)
+        t0 = time.perf_counter()
+        r.set_smooth_normals(groups, n_groups, arm)
+        set_ms[arm] = round(1e3 * (time.perf_counter() - t0), 3)
+        ctx[arm] = r
+    arms = {"explicit": (ctx["unit"], dn), "generated_unit": (ctx["unit"], None), "generated_area": (ctx["area"], None)}
+    for r, n in arms.values():                                             # (the first update uploads the tables; first launches load code)
+        for k in range(2):
+            r.update_vertices(dv[k], n)
+    t = {arm: [] for arm in arms}
+    names = list(arms)
+    for k in range(rounds):
+        for arm in names[k % 3:] + names[:k % 3]:                          # (the arms alternate, the order rotates)
+            r, n = arms[arm]
+            t0 = time.perf_counter()
+            r.update_vertices(dv[k % 2], n)
+            t[arm].append(1e3 * (time.perf_counter() - t0))
+    ctx["unit"].update_vertices(dv[0], None)
+    gen = ctx["unit"].read_normals()
+    ctx["unit"].update_vertices(dv[0], None)
+    same = bool(np.array_equal(gen.view(np.uint32), ctx["unit"].read_normals().view(np.uint32)))      # (the same call again: the same bits)
+    for r in ctx.values():
+        r.close()
+    out = {"triangles": int(scene.desc.triangle_count), "groups": int(n_groups), "rounds": rounds,
+           "valence": {"min": int(valence.min()), "median": float(np.median(valence)), "max": int(valence.max()),
+                       "sum_of_squares": int((valence.astype(np.int64) ** 2).sum())},
+           "weld_corners_host_ms": round(weld_ms, 2), "set_smooth_normals_ms": set_ms,
+           "device_bytes": {"unit": 88 * int(scene.desc.triangle_count) + 4 * (n_groups + 1), "area": 104 * int(scene.desc.triangle_count) + 4 * (n_groups + 1)},
+           "generated_normals_unit_length": bool(np.abs(np.linalg.norm(gen[:, :3].astype(np.float64), axis=1) - 1).max() < 1e-5), "stable": same}
+    for arm, v in t.items():
+        out[arm] = {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(min(v)), 4), "max_ms": round(float(max(v)), 4)}
+    for arm in ("generated_unit", "generated_area"):
+        out[arm]["over_explicit_median"] = round(out[arm]["median_ms"] / out["explicit"]["median_ms"], 3)
+        out[arm]["minus_explicit_median_ms"] = round(out[arm]["median_ms"] - out["explicit"]["median_ms"], 4)
+    return out
+
+
+def normals_kernels_phase(prt, names):
+    """the launches rocprofv3 times: KERNEL_CALLS device updates with generated normals (unit weighting) per scene"""
+    import torch
+    for name in names:
+        scene = _scene(prt, name)
+        a = prt.scene_arrays(scene.desc)
+        r = prt.Renderer(scene.config(), device=0)
+        r.upload_scene(scene)
+        r.set_smooth_normals(*prt.weld_corners(a["vertices"]))
+        dv = torch.from_numpy(deform(a["vertices"], 0.01)).cuda()
+        torch.cuda.synchronize()
+        for _ in range(KERNEL_CALLS):
+            r.update_vertices(dv, None)
+        r.close()
+
+
+def normals_kernel_times(names, timeout):
+    """per scene: the durations of the kernels of one generated update (best of the calls after the first), by kernel"""
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "normals", "--",
+               sys.executable, os.path.abspath(__file__), "--phase", "normals-kernels", "--scenes", ",".join(names)]
+        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
+        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+        assert traces, "rocprofv3 wrote no kernel trace"
+        with open(traces[0]) as fh:
+            rows = [(row["Kernel_Name"], int(row["Start_Timestamp"]), int(row["End_Timestamp"])) for row in csv.DictReader(fh)]
+    rows = sorted((r for r in rows if "refit_" in r[0] or "normals_" in r[0]), key=lambda r: r[1])
+    starts = [i for i, r in enumerate(rows) if "refit_check" in r[0]]
+    assert len(starts) == KERNEL_CALLS * len(names), (len(starts), len(rows))
+    out = {}
+    for s, name in enumerate(names):
+        best = None
+        for c in range(1, KERNEL_CALLS):
+            i = starts[s * KERNEL_CALLS + c]
+            j = starts[s * KERNEL_CALLS + c + 1] if s * KERNEL_CALLS + c + 1 < len(starts) else len(rows)
+            one = rows[i:j]
+            us = lambda key: round(sum(e - b for n, b, e in one if key in n) / 1e3, 2)
+            rec = {"check_us": us("refit_check"), "normals_face_us": us("normals_face"), "normals_corner_us": us("normals_corner"),
+                   "refit_tri_us": us("refit_tri"), "refit_levels_busy_us": round(us("refit_level") + us("refit_root_leaf"), 2),
+                   "face_to_root_span_us": round((one[-1][2] - one[1][1]) / 1e3, 2) if len(one) > 1 else 0.0}
+            if best is None or rec["face_to_root_span_us"] < best["face_to_root_span_us"]:
+                best = rec
+        out[name] = best
+    out["note"] = "kernel durations of one prt_update_vertices_device call with generated normals (best of %d), rocprofv3 --kernel-trace --stats" % (KERNEL_CALLS - 1)
+    return out
+
+
 def kernels_phase(prt, names):
     """the launches rocprofv3 times: KERNEL_CALLS device updates (with normals) per scene"""
     import torch
@@ -272,7 +377,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="cornell_coat,cornell_dragon")
     ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--phase", default="all", choices=["all", "rates", "kernels", "motion"])
+    ap.add_argument("--phase", default="all", choices=["all", "rates", "kernels", "motion", "normals", "normals-kernels"])
     ap.add_argument("--rocprof-timeout", type=int, default=300)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -280,6 +385,21 @@ def main():
     names = a.scenes.split(",")
     if a.phase == "kernels":
         kernels_phase(prt, names)
+        return
+    if a.phase == "normals-kernels":
+        normals_kernels_phase(prt, names)
+        return
+    if a.phase == "normals":
+        doc = {"build_id": prt.build_id(), "normals": {name: normals_phase(prt, name, a.calls) for name in names}}
+        try:
+            doc["kernel_time"] = normals_kernel_times(names, a.rocprof_timeout)
+        except (subprocess.SubprocessError, AssertionError, KeyError, OSError) as e:
+            doc["kernel_time"] = {"error": repr(e)}
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(text + "\n")
         return
     if a.phase == "motion":
         doc = {"build_id": prt.build_id(), "motion": {name: motion_phase(prt, name, a.calls) for name in names}}
