@@ -183,11 +183,11 @@ int prt_upload_scene(prt_ctx* ctx, const prt_scene_desc* scene);
  * prt_render_guides, prt_denoise_temporal.  Without motion (prt_set_motion, below: off by default) the reprojection treats every surface as if it
  * had stood still: its depth and normal tests reject most surfaces that moved (their history restarts), and where they happen to pass the
  * history of another surface point is blended in.  With motion on, the guide render also says where each pixel's point of the mesh was
- * before the update and the reprojection looks there: the history follows the deforming mesh.  What still does not follow: spheres, quads
- * and SDF primitives (prt_upload_scene moves them: no history across it), surfaces seen through mirrors or glass (the virtual point behind a
+ * before the update and the reprojection looks there: the history follows the deforming mesh (and, through prt_update_primitives below, a
+ * moving sphere, quad or SDF primitive).  What still does not follow: surfaces seen through mirrors or glass (the virtual point behind a
  * delta chain carries no motion), and a surface that turns by more than cos_n between two frames (the normal test compares the current normal
  * with the one stored in the previous frame; previous-frame normals are out of scope) -- those restart.  prt_reset_history empties it.  Spheres,
- * quads, SDF primitives and materials are not touched: moving them stays prt_upload_scene's job.  The tables a refit needs (4 bytes per slot
+ * quads, SDF primitives and materials are not touched: prt_update_primitives (below) moves the former three.  The tables a refit needs (4 bytes per slot
  * and per inner node) go to the device with the first update: a static scene costs no device memory.
  * Refused, each leaving the scene exactly as it was: PRT_ERR_NOT_READY without a scene or with T == 0; PRT_ERR_INVALID_ARGUMENT for null
  * `vertices`, a misaligned device pointer, or any non-finite x, y or z among the 3T vertices (the loaders refuse those too: a NaN box hides
@@ -201,6 +201,31 @@ int prt_upload_scene(prt_ctx* ctx, const prt_scene_desc* scene);
 int prt_update_vertices(prt_ctx* ctx, const float* vertices, const float* normals);
 int prt_update_vertices_device(prt_ctx* ctx, const void* d_vertices, const void* d_normals);
 int prt_read_bvh_bounds(prt_ctx* ctx, float* bounds6);
+
+/* Moving spheres, quads and SDF primitives: new prt_mesh records into the uploaded scene, in place (no counterpart in the reference).  `count`
+ * must equal object_count[7] of the last prt_upload_scene; record i is mesh i of that upload: spheres first, then SDF primitives, then quads.
+ *   prt_update_primitives          host memory: staged through a device buffer of the context (allocated on first use), then the device path.
+ *   prt_update_primitives_device   device memory of the context's device, 16-byte aligned, count x 256 bytes; ordered on the context's stream,
+ *                                  complete on return (the caller's buffer may be reused then).
+ * Only geometry is read -- sphere: pos[0..2], joker[0] (radius); SDF primitive: pos[0..2], joker[0..3]; quad: joker[0..12] (base, edge0, edge1,
+ * normal, area, as the caller gives them) -- and t, which must equal the uploaded record's: kind and SDF sub-type are fixed.  mat, the
+ * paddings and the other joker entries are not read; the materials table is not touched.  The resulting sphere, SDF and quad tables are, byte
+ * for byte, what prt_upload_scene of the same scene with these meshes makes (the quad's anchor = base - (edge0 + edge1) * 0.5f, dot(edge0,
+ * edge0), dot(edge1, edge1) and their half-ulp bounds included): a render after the call is bit-identical to a fresh context that uploads the
+ * moved scene; tile, row-block and rank contexts that each call it stay bit-identical in union to one whole-frame context.
+ * Lifetime: that of prt_update_vertices.  The guides go stale and measured tile orders are forgotten; the path state, the framebuffer, both
+ * temporal histories, the refit and rebuild tables, the smoothing topology and a pending triangle snapshot are kept.  The loop per displayed
+ * frame: update, prt_reset, render, prt_render_guides, prt_denoise_temporal.  A scene without triangles, or without one or two of the three
+ * kinds, is accepted.  The staging tables (and, with motion on, the previous tables) are allocated by the first call: a scene that never
+ * moves a primitive pays nothing.
+ * Refused, each leaving the scene and a pending snapshot exactly as they were: PRT_ERR_NOT_READY without a scene; PRT_ERR_INVALID_ARGUMENT for
+ * a wrong count, a null pointer, a misaligned device pointer, a record whose t differs from the uploaded one, or a non-finite value in a field
+ * that is read (a non-finite value in a field that is not read is not looked at).  The records are packed and checked on the device into
+ * staging tables; the host reads the check's flag before anything live is overwritten.  count == 0 on a scene without primitives succeeds and
+ * does nothing.
+ * With prt_set_motion on, an accepted update keeps the three tables as they were (see "Snapshot" under prt_set_motion). */
+int prt_update_primitives(prt_ctx* ctx, const prt_mesh* meshes, uint32_t count);
+int prt_update_primitives_device(prt_ctx* ctx, const void* d_meshes, uint32_t count);
 
 /* Deforming geometry, second door: new vertices into the uploaded scene and a NEW TREE over all T triangles, built on the device in Morton order
  * (no counterpart in the reference).  Arguments, alignment and staging are those of prt_update_vertices / prt_update_vertices_device; the call
@@ -412,7 +437,21 @@ int prt_read_guides(prt_ctx* ctx, float* out8);
  *     quads and SDF primitives --, with (slot, u, v) that hit, f32, no contraction, per component:
  *         q(rec) = (rec.p0 - rec.e1 * u) + rec.e2 * v       (p1 = p0 - e1, p2 = p0 + e2; u weighs vertex 1, v vertex 2, as the hit's normal)
  *         d_s    = q(tri_prev[slot]) - q(tri_geom[slot])    (where the point was, minus where it is; exactly 0 for an unchanged record)
- *     Hits on spheres, quads and SDF primitives, hits behind a mirror or glass chain and misses contribute nothing.
+ *     Triangle hits contribute only while a triangle snapshot is pending.
+ *   Primitive snapshot: with motion on, an accepted prt_update_primitives / prt_update_primitives_device keeps the sphere, SDF and quad tables
+ *     as they were -- after every refusal is decided, and only when no primitive snapshot is pending (the oldest wins).  prt_render_guides
+ *     consumes it; prt_upload_scene and turning motion off drop it.  It is independent of the triangle snapshot.
+ *   Per guide sample s whose FIRST hit is a sphere, a quad or an SDF primitive (mesh index >= 0) of a non-delta material, while a primitive
+ *     snapshot is pending, with p the hit position (ray.pos), f32, no contraction, IEEE divides and square root, per component:
+ *         sphere i:         w = p - c_cur, h = w / sqrt((w.x w.x + w.y w.y) + w.z w.z);  d_s = (c_prev - c_cur) + h * (r_prev - r_cur)
+ *         quad j:           w = p - anchor_cur, a = dot(w, e0_cur) / e0e0_cur, b = dot(w, e1_cur) / e1e1_cur (dot(x, y) = (x.x y.x + x.y y.y) + x.z y.z;
+ *                           the quad test measures from anchor, not base);  q(rec) = (rec.anchor + rec.edge0 * a) + rec.edge1 * b;
+ *                           d_s = q(prev) - q(cur): translation, rotation and resizing of the card are carried
+ *         SDF primitive k:  d_s = pos_prev - pos_cur: only translation is carried, a parameter change carries no motion
+ *     Each is exactly +0 for an unchanged record.  Primitive hits contribute only while a primitive snapshot is pending: after
+ *     prt_update_vertices alone primitive pixels read as zeros, after prt_update_primitives alone triangle pixels do, after both both carry
+ *     motion.  A mirror or glass sphere that moves carries no motion.
+ *     Hits behind a mirror or glass chain and misses contribute nothing.
  *   Per pixel: D = (sum of d_s in sample order) / (float)hits (IEEE division; hits = the guides' own hit count: the mean over the hits, as the
  *     guides' depth), m = (float)contributing_samples * (1 / samples).  hits == 0, or no snapshot pending: D = 0, m = 0.
  *   The eight guide floats are the same bits with motion on and off; tiles and row blocks work as for the guides (global coordinates: the
@@ -423,7 +462,7 @@ int prt_read_guides(prt_ctx* ctx, float* out8);
  *   current normal against the stored one: a surface that turns by more than cos_n restarts), the blend.  Every other pixel, and a call
  *   without a plane, takes the expressions of prt_denoise_temporal as they stand: a plane of zeros gives the same bits as no plane.
  * prt_set_motion: default 0.  A change makes the guides stale and keeps both histories; a call with the value in force does nothing.  PRT_ERR_UNSUPPORTED with a debug view.  A scene without
- *   triangles is accepted: its planes are zeros.
+ *   triangles is accepted: its planes are zeros unless a primitive moved.
  * prt_read_motion: width * rows * 4 floats, framebuffer order.  PRT_ERR_NOT_READY while motion is off or there are no valid guides rendered
  *   with motion on; PRT_ERR_INVALID_ARGUMENT for a null pointer or a context without a frame size.
  * prt_export_motion: the plane of the frame part (whole frame, tile or row blocks) into device memory of the caller, ordered on the

@@ -325,6 +325,7 @@ class Renderer:
         desc = scene.desc if isinstance(scene, HostScene) else scene
         self._chk(self.lib.prt_upload_scene(self.ctx, C.byref(desc)), "prt_upload_scene")
         self.triangle_count = int(desc.triangle_count)
+        self.mesh_count = int(desc.object_count[7])
         self.bvh_node_count = int(desc.bvh_node_count) if desc.triangle_count else 0
 
     def update_vertices(self, vertices, normals=None):
@@ -346,6 +347,35 @@ class Renderer:
         pv = self._device_ptr(vertices, floats, "update_vertices")
         pn = None if normals is None else self._device_ptr(normals, floats, "update_vertices")
         self._chk(self.lib.prt_update_vertices_device(self.ctx, pv, pn), "prt_update_vertices_device")
+
+    def update_primitives(self, meshes, device=False, count=None):
+        """prt_update_primitives / prt_update_primitives_device: the prt_mesh records (256 bytes each, all object_count[7] of them, in the
+        uploaded order) of the moved spheres, SDF primitives and quads into the uploaded scene (prt.h).  Host door: the Mesh array of a
+        HostScene.desc (a ctypes array or pointer), or a numpy array / view of count x 256 bytes.  device=True, a torch tensor or an integer
+        address: the device door (count x 256 bytes, 16-byte aligned; work queued on torch's current stream is waited for)"""
+        count = int(getattr(self, "mesh_count", 0)) if count is None else int(count)     # (count: the uploaded scene's, unless given)
+        nbytes = count * C.sizeof(_capi.Mesh)
+        if hasattr(meshes, "data_ptr"):
+            import torch
+            if not meshes.is_contiguous() or meshes.numel() * meshes.element_size() < nbytes:
+                raise ValueError("update_primitives: needs a contiguous tensor of at least %d bytes" % nbytes)
+            torch.cuda.current_stream(meshes.device).synchronize()
+            self._chk(self.lib.prt_update_primitives_device(self.ctx, C.c_void_p(meshes.data_ptr()), count), "prt_update_primitives_device")
+            return
+        if device:
+            self._chk(self.lib.prt_update_primitives_device(self.ctx, C.c_void_p(int(meshes)) if meshes is not None else None, count),
+                      "prt_update_primitives_device")
+            return
+        if isinstance(meshes, np.ndarray):
+            m = np.ascontiguousarray(meshes)
+            if m.nbytes < nbytes:
+                raise ValueError("update_primitives: needs %d bytes of prt_mesh records" % nbytes)
+            ptr = m.ctypes.data_as(C.c_void_p)
+        elif meshes is None or isinstance(meshes, (int, C.c_void_p)):
+            ptr = meshes
+        else:
+            ptr = C.cast(meshes, C.c_void_p)               # a ctypes array of Mesh, or a pointer to one
+        self._chk(self.lib.prt_update_primitives(self.ctx, ptr, count), "prt_update_primitives")
 
     def read_bvh_bounds(self):
         """prt_read_bvh_bounds: float32 [bvh_node_count, 6] = min_x max_x min_y max_y min_z max_z per node of the uploaded tree, in its numbering"""

@@ -119,6 +119,8 @@ PRT_API = [
     ("prt_upload_scene", C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     ("prt_update_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_update_vertices_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_update_primitives", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("prt_update_primitives_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_read_bvh_bounds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_rebuild_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_rebuild_bvh_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),

@@ -116,6 +116,7 @@ static void free_scene(prt_ctx* c) {
     c->cap_pairs = c->cap_slots = c->cap_prev = 0;
     c->rebuilt = false;
     free_smooth(c);
+    free_prims(c, true);
 }
 
 extern "C" void prt_destroy(prt_ctx* c) {

@@ -6,6 +6,7 @@
 #include <thread>
 
 #include "prt_ctx.h"
+#include "pt_prims.h"
 
 static int ensure_seeds(prt_ctx* c, const int32_t* seed_pairs, size_t n_frames) {
     if (!n_frames) return PRT_OK;
@@ -379,15 +380,23 @@ extern "C" int prt_render_guides(prt_ctx* c, uint32_t samples) {
     const bool snap = c->motion && c->snap_valid && c->d_tri_prev;
     // the motion instances only where there is a snapshot to measure from; no update since the last guide render: the plain kernels and a
     // plane of zeros
-    if (snap) launch_guides_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides,
+    // ... and the primitive-motion instances only while a primitive snapshot is pending (prt_update_primitives), with the triangle term only
+    // while a triangle snapshot is pending too: the two snapshots are independent of each other
+    const bool prim_snap = c->motion && c->prim_snap_valid && c->d_spheres_prev && c->d_sdfs_prev && c->d_quads_prev;
+    if (prim_snap) {
+        const PrimPrev prims{static_cast<const DevSphere*>(c->d_spheres_prev), static_cast<const DevSdf*>(c->d_sdfs_prev), static_cast<const DevQuad*>(c->d_quads_prev)};
+        launch_guides_prim_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides,
+                                  snap ? static_cast<const TriGeom*>(c->d_tri_prev) : nullptr, prims, c->d_motion, c->stream);
+    } else if (snap) launch_guides_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides,
                                    static_cast<const TriGeom*>(c->d_tri_prev), c->d_motion, c->stream);
     else launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides, c->stream);
     HIPCHK(c, hipGetLastError());
-    if (c->motion && !snap) HIPCHK(c, hipMemsetAsync(c->d_motion, 0, c->npix * sizeof(float4), c->stream));
+    if (c->motion && !snap && !prim_snap) HIPCHK(c, hipMemsetAsync(c->d_motion, 0, c->npix * sizeof(float4), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->guides_valid = true;
     if (c->motion) {
         c->snap_valid = false;                         // consumed: the next plane is measured from the geometry these guides saw
+        c->prim_snap_valid = false;
         c->motion_valid = true;
     }
     return PRT_OK;

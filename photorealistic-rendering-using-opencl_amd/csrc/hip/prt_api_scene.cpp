@@ -31,6 +31,9 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
     c->cap_prev = 0;
     c->rebuilt = false;
     free_smooth(c);                                  // (the smoothing topology is the old mesh's: T may have changed)
+    free_prims(c, true);                             // (the primitive snapshot, types and staging tables are the old scene's)
+    c->mesh_t.resize(s->object_count[7]);
+    for (uint32_t i = 0; i < s->object_count[7]; ++i) c->mesh_t[i] = s->meshes[i].t;
     c->n_slots = ps.slot_vtx.size();
     c->cap_pairs = ps.pairs.empty() ? 1 : ps.pairs.size();         // (what upload() below allocates, in records)
     c->cap_slots = ps.tg.empty() ? 1 : ps.tg.size();
@@ -180,6 +183,89 @@ extern "C" int prt_update_vertices(prt_ctx* c, const float* vertices, const floa
     if (!rc) rc = stage_vertices(c, vertices, normals);
     if (rc) return rc;
     return prt_update_vertices_device(c, c->d_stage_vtx, normals ? c->d_stage_nrm : nullptr);
+}
+
+// ---- moving spheres, SDF primitives and quads: new prt_mesh records into the uploaded tables (prt.h prt_update_primitives; pt_prims.hip) --------
+// the refusals both variants share; *nothing: count == 0 on a scene without primitives (the call succeeds and does nothing)
+static int prims_checks(prt_ctx* c, const void* meshes, uint32_t count, const char* who, bool* nothing) {
+    const std::string w(who);
+    *nothing = false;
+    if (!c->have_scene) return fail(c, PRT_ERR_NOT_READY, w + ": no scene uploaded");
+    if (count != c->sc.n_meshes) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": count is not object_count[7] of the uploaded scene (the scene is unchanged)");
+    if (count == 0) { *nothing = true; return PRT_OK; }
+    if (!meshes) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null meshes");
+    return PRT_OK;
+}
+
+// what the first update allocates: the types table behind the flag word, and the staging tables
+static int prims_tables(prt_ctx* c) {
+    if (c->d_prim_types) return PRT_OK;
+    const size_t n_sph = c->sc.n_spheres ? c->sc.n_spheres : 1, n_sdf = c->sc.n_sdfs ? c->sc.n_sdfs : 1, n_quad = c->sc.n_quads ? c->sc.n_quads : 1;
+    if (!c->d_stage_spheres) HIPCHK(c, hipMalloc(&c->d_stage_spheres, n_sph * sizeof(DevSphere)));
+    if (!c->d_stage_sdfs) HIPCHK(c, hipMalloc(&c->d_stage_sdfs, n_sdf * sizeof(DevSdf)));
+    if (!c->d_stage_quads) HIPCHK(c, hipMalloc(&c->d_stage_quads, n_quad * sizeof(DevQuad)));
+    void* types = nullptr;
+    HIPCHK(c, hipMalloc(&types, 16 + c->mesh_t.size()));
+    hipError_t e = hipMemcpy(static_cast<char*>(types) + 16, c->mesh_t.data(), c->mesh_t.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { free_dev(types); HIPCHK(c, e); }
+    c->d_prim_types = types;
+    return PRT_OK;
+}
+
+extern "C" int prt_update_primitives_device(prt_ctx* c, const void* d_meshes, uint32_t count) {
+    CTX_CHECK(c);
+    bool nothing = false;
+    if (int rc = prims_checks(c, d_meshes, count, "prt_update_primitives_device", &nothing)) return rc;
+    if (nothing) return PRT_OK;
+    if (!aligned16(d_meshes)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_update_primitives_device: the device buffer must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = prims_tables(c)) return rc;
+    const size_t sph_bytes = c->sc.n_spheres * sizeof(DevSphere), sdf_bytes = c->sc.n_sdfs * sizeof(DevSdf), quad_bytes = c->sc.n_quads * sizeof(DevQuad);
+    // the snapshot's tables before any refusal is decided: an allocation failure leaves the scene and a pending snapshot as they were
+    if (c->motion && !c->prim_snap_valid) {
+        if (!c->d_spheres_prev) HIPCHK(c, hipMalloc(&c->d_spheres_prev, sph_bytes ? sph_bytes : sizeof(DevSphere)));
+        if (!c->d_sdfs_prev) HIPCHK(c, hipMalloc(&c->d_sdfs_prev, sdf_bytes ? sdf_bytes : sizeof(DevSdf)));
+        if (!c->d_quads_prev) HIPCHK(c, hipMalloc(&c->d_quads_prev, quad_bytes ? quad_bytes : sizeof(DevQuad)));
+    }
+    // the pack and its check into the staging tables: the flag is read before anything live is overwritten
+    uint32_t* flag = static_cast<uint32_t*>(c->d_prim_types);
+    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    launch_prims_pack(d_meshes, count, c->sc.n_spheres, c->sc.n_sdfs, static_cast<const uint8_t*>(c->d_prim_types) + 16,
+                      static_cast<DevSphere*>(c->d_stage_spheres), static_cast<DevSdf*>(c->d_stage_sdfs), static_cast<DevQuad*>(c->d_stage_quads), flag,
+                      c->stream);
+    HIPCHK(c, hipGetLastError());
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_update_primitives: a record whose t differs from the uploaded one, or a non-finite value in a field that is read (the scene is unchanged)");
+    // motion (prt.h prt_set_motion): the tables as they are go to the snapshot before they are overwritten -- unless one is pending already:
+    // the oldest wins.  Every refusal is behind us
+    if (c->motion && !c->prim_snap_valid) {
+        if (sph_bytes) HIPCHK(c, hipMemcpyAsync(c->d_spheres_prev, c->d_spheres, sph_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (sdf_bytes) HIPCHK(c, hipMemcpyAsync(c->d_sdfs_prev, c->d_sdfs, sdf_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (quad_bytes) HIPCHK(c, hipMemcpyAsync(c->d_quads_prev, c->d_quads, quad_bytes, hipMemcpyDeviceToDevice, c->stream));
+        c->prim_snap_valid = true;
+    }
+    // what a primary ray sees changes: the lifetime of prt_update_vertices
+    c->guides_valid = false;
+    forget_tile_orders(c);
+    if (sph_bytes) HIPCHK(c, hipMemcpyAsync(c->d_spheres, c->d_stage_spheres, sph_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (sdf_bytes) HIPCHK(c, hipMemcpyAsync(c->d_sdfs, c->d_stage_sdfs, sdf_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (quad_bytes) HIPCHK(c, hipMemcpyAsync(c->d_quads, c->d_stage_quads, quad_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // the caller's buffer may be reused on return
+    return PRT_OK;
+}
+
+extern "C" int prt_update_primitives(prt_ctx* c, const prt_mesh* meshes, uint32_t count) {
+    CTX_CHECK(c);
+    bool nothing = false;
+    if (int rc = prims_checks(c, meshes, count, "prt_update_primitives", &nothing)) return rc;
+    if (nothing) return PRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)count * sizeof(prt_mesh);
+    if (!c->d_stage_meshes) HIPCHK(c, hipMalloc(&c->d_stage_meshes, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->d_stage_meshes, meshes, bytes, hipMemcpyHostToDevice, c->stream));
+    return prt_update_primitives_device(c, c->d_stage_meshes, count);
 }
 
 extern "C" int prt_read_bvh_bounds(prt_ctx* c, float* bounds6) {
@@ -397,6 +483,7 @@ extern "C" int prt_set_motion(prt_ctx* c, int enable) {
         free_dev(c->d_tri_prev);
         c->cap_prev = 0;
         c->snap_valid = false;
+        free_prims(c, false);
     }
     return PRT_OK;
 }

@@ -162,6 +162,15 @@ struct prt_ctx {
     bool snap_valid = false;
     float4* d_motion = nullptr;
     bool motion_valid = false;
+    // prt_update_primitives (pt_prims.hip).  mesh_t: t of every uploaded prt_mesh (host).  All of the rest is allocated by the first update and
+    // freed with the scene: d_prim_types {the pack kernel's flag word, 12 bytes of padding, mesh_t}; the staging tables the pack kernel writes
+    // (sized as the live ones) and d_stage_meshes, the host variant's records; with motion on, the tables as they were before the first
+    // update since the last guide render (d_*_prev) -- prim_snap_valid: such a snapshot is pending, independent of the triangles' snap_valid
+    std::vector<uint8_t> mesh_t;
+    void* d_prim_types = nullptr;
+    void* d_stage_spheres = nullptr; void* d_stage_sdfs = nullptr; void* d_stage_quads = nullptr; void* d_stage_meshes = nullptr;
+    void* d_spheres_prev = nullptr; void* d_sdfs_prev = nullptr; void* d_quads_prev = nullptr;
+    bool prim_snap_valid = false;
     // prt_set_smooth_normals (pt_normals.hip): the smoothing topology of the uploaded mesh on the device -- the group of every corner, the
     // group-to-members table -- and what a generation writes: the face buffer (d_sm_face_r for the area weighting only) and the generated
     // normals (float4[3T]).  All allocated by prt_set_smooth_normals, freed by turning it off, by prt_upload_scene and with the scene
@@ -186,6 +195,14 @@ inline void free_smooth(prt_ctx* c) {
     free_dev(c->d_sm_group); free_dev(c->d_sm_first); free_dev(c->d_sm_member);
     free_dev(c->d_sm_face_f); free_dev(c->d_sm_face_r); free_dev(c->d_sm_nrm);
     c->smooth = false;
+}
+
+// prt_update_primitives: the primitive snapshot (motion off, a new scene), and with `all` everything else the first update allocated
+inline void free_prims(prt_ctx* c, bool all) {
+    free_dev(c->d_spheres_prev); free_dev(c->d_sdfs_prev); free_dev(c->d_quads_prev);
+    c->prim_snap_valid = false;
+    if (!all) return;
+    free_dev(c->d_prim_types); free_dev(c->d_stage_spheres); free_dev(c->d_stage_sdfs); free_dev(c->d_stage_quads); free_dev(c->d_stage_meshes);
 }
 
 // measured tile orders are the scene's, the view's and the frame's: whatever changes one of them forgets them

@@ -3,6 +3,8 @@
 //
 //   guide_kernel<SDF>   K guide samples per pixel (pt_guides.h), one lane per pixel, 8x8 tiles per 64-lane wave
 //   guide_motion_kernel<SDF>, filtered_guides_motion_kernel   the same, and the motion plane (pt_motion.h; prt.h prt_set_motion)
+//   guide_prim_motion_kernel<SDF, TRI>, filtered_guides_prim_motion_kernel<TRI>   the motion plane with a primitive snapshot pending (pt_prims.h;
+//                       prt.h prt_update_primitives), with (TRI) or without the triangle term
 //   dn_var_kernel       {rgb, v} per pixel: the framebuffer colour and the luminance variance of its mean (stats plane or 5x5 moments)
 //   dn_gauss_kernel     3x3 Gaussian of v (one per pass)
 //   dn_atrous_kernel    one a-trous pass: 5x5 taps at step 2^i, weights from normal, depth, albedo and luminance; ping-pongs {rgb, v}
@@ -12,6 +14,7 @@
 #include "pt_guides.h"
 #include "pt_launch.h"
 #include "pt_motion.h"
+#include "pt_prims.h"
 
 namespace prt {
 using namespace dev;
@@ -20,9 +23,12 @@ using namespace dev;
 // FILTER: the sample offsets warped by the context's pixel filter (prt.h prt_set_pixel_filter; filtered_guides_kernel)
 // MOTION: also the motion plane {D, m} of the pixel, from the triangle records before the update(s) (tri_prev: an argument of its own, DevScene
 // is the render kernels' kernarg block) and sc.tri_geom; the eight guide floats are the other instances' bit for bit
-template <bool SDF, bool FILTER, bool MOTION>
+// PRIM: the plane also carries the first hits on spheres, SDF primitives and quads, from the tables before the update(s) (prims) and
+// sc.spheres / sc.sdfs / sc.quads: the records of the lane's own hit, read per lane.  MOTION then says whether a triangle snapshot is pending
+// too: without one the triangle term is not compiled in
+template <bool SDF, bool FILTER, bool MOTION, bool PRIM = false>
 PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* __restrict__ out,
-                        const TriGeom* __restrict__ tri_prev, float4* __restrict__ motion) {
+                        const TriGeom* __restrict__ tri_prev, float4* __restrict__ motion, const PrimPrev prims = PrimPrev{nullptr, nullptr, nullptr}) {
     const int tiles_x = (fa.width + 7) / 8;
     const int lane = threadIdx.x & 63;
     const int lx = (int)(blockIdx.x % (unsigned)tiles_x) * 8 + (lane & 7);
@@ -54,6 +60,10 @@ PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArg
             if (dot(g.normal, g.normal) == dot(g.normal, g.normal)) nsum = nsum + g.normal;     // (a degenerate mesh normal is NaN: left out)
             if constexpr (MOTION)
                 if (g.direct_triangle) motion_sum_add(msum, motion_displacement(tri_prev, sc.tri_geom, g.slot, g.u, g.v));
+            if constexpr (PRIM)
+                if (g.direct_prim)
+                    motion_sum_add(msum, prims_displacement(prims, sc.spheres, sc.sdfs, sc.quads, sc.n_spheres, SDF ? sc.n_sdfs : 0u, sc.quad_mesh_base,
+                                                            (unsigned)g.mid, g.pos.x, g.pos.y, g.pos.z));
         }
     }
     const float inv_k = 1.0f / (float)samples;
@@ -62,7 +72,7 @@ PT_DEV void guide_pixel(const DevScene& sc, const DevCamera& cam, const FrameArg
     const size_t id = (size_t)ly * (size_t)fa.width + (size_t)lx;
     out[2 * id] = make_float4(albedo.x * inv_k, albedo.y * inv_k, albedo.z * inv_k, (float)hits * inv_k);
     out[2 * id + 1] = make_float4(n.x, n.y, n.z, hits ? zsum / (float)hits : 0.0f);
-    if constexpr (MOTION) {
+    if constexpr (MOTION || PRIM) {
         const MotionQuad m = motion_pixel(msum, hits, samples);
         motion[id] = make_float4(m.x, m.y, m.z, m.w);
     }
@@ -88,6 +98,20 @@ __global__ __launch_bounds__(64) void filtered_guides_motion_kernel(const DevSce
                                                                     float4* __restrict__ out, const TriGeom* __restrict__ tri_prev,
                                                                     float4* __restrict__ motion) {
     guide_pixel<false, true, true>(sc, cam, fa, samples, out, tri_prev, motion);
+}
+
+// the primitive-motion instances (TRI: a triangle snapshot is pending as well): plain, SDF, pixel filter
+template <bool SDF, bool TRI>
+__global__ __launch_bounds__(64) void guide_prim_motion_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
+                                                               float4* __restrict__ out, const TriGeom* __restrict__ tri_prev, const PrimPrev prims,
+                                                               float4* __restrict__ motion) {
+    guide_pixel<SDF, false, TRI, true>(sc, cam, fa, samples, out, tri_prev, motion, prims);
+}
+template <bool TRI>
+__global__ __launch_bounds__(64) void filtered_guides_prim_motion_kernel(const DevScene sc, const DevCamera cam, const FrameArgs fa, unsigned samples,
+                                                                         float4* __restrict__ out, const TriGeom* __restrict__ tri_prev,
+                                                                         const PrimPrev prims, float4* __restrict__ motion) {
+    guide_pixel<false, true, TRI, true>(sc, cam, fa, samples, out, tri_prev, motion, prims);
 }
 
 // one launcher for the plain and the motion instances (MOTION: tri_prev and motion are the two further kernel arguments)
@@ -125,6 +149,34 @@ void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa
 void launch_guides_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
                           float4* motion, hipStream_t stream) {
     launch_guides_m<true>(sc, cam, fa, samples, out, tri_prev, motion, stream);
+}
+
+// the launcher of the primitive-motion instances
+template <bool SDF, bool FILTER, bool TRI>
+static void launch_guides_p(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                            const PrimPrev& prims, float4* motion, hipStream_t stream) {
+    const size_t lds = (size_t)sc.stack_levels * 64 * sizeof(unsigned);
+    static size_t lds_attr = 0;
+    const void* k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_prim_motion_kernel<TRI>) : reinterpret_cast<const void*>(&guide_prim_motion_kernel<SDF, TRI>);
+    if (lds > 65536u && lds > lds_attr) {
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        lds_attr = lds;
+    }
+    const unsigned tiles = (unsigned)(((fa.width + 7) / 8) * ((fa.rows + 7) / 8));
+    if constexpr (FILTER) hipLaunchKernelGGL((filtered_guides_prim_motion_kernel<TRI>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, prims, motion);
+    else hipLaunchKernelGGL((guide_prim_motion_kernel<SDF, TRI>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, prims, motion);
+}
+template <bool TRI>
+static void launch_guides_pt(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                             const PrimPrev& prims, float4* motion, hipStream_t stream) {
+    if (fa.filter_kind != PRT_FILTER_NONE) launch_guides_p<false, true, TRI>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
+    else if (sc.n_sdfs) launch_guides_p<true, false, TRI>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
+    else launch_guides_p<false, false, TRI>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
+}
+void launch_guides_prim_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                               const PrimPrev& prims, float4* motion, hipStream_t stream) {
+    if (tri_prev) launch_guides_pt<true>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
+    else launch_guides_pt<false>(sc, cam, fa, samples, out, nullptr, prims, motion, stream);
 }
 
 // ---- the filter ----------------------------------------------------------------------------------------------------------------------

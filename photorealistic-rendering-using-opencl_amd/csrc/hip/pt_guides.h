@@ -79,7 +79,8 @@ PT_DEV f3 clamp01(f3 c) {
 
 // direct_triangle: the hit that gives the values is the ray's FIRST (no delta event before it) and a mesh triangle (the one that wins
 // finish_closest: mesh_id == -1); then {slot, u, v} name it (prt.h prt_set_motion: the samples that carry motion)
-struct GuideSample { f3 albedo, normal; float depth; bool hit; unsigned slot; float u, v; bool direct_triangle; };
+// direct_prim: the FIRST hit is a sphere, an SDF primitive or a quad (mesh_id >= 0); then {mid, pos} name it (prt.h prt_update_primitives)
+struct GuideSample { f3 albedo, normal; float depth; bool hit; unsigned slot; float u, v; bool direct_triangle; bool direct_prim; int mid; f3 pos; };
 
 // one guide sample along `ray` (prt.h: the delta chain, the per-hit values, the miss)
 template <bool SDF>
@@ -87,6 +88,7 @@ PT_DEV GuideSample guide_sample(const DevScene& sc, Ray ray, const TravStack& st
     GuideSample g;
     g.normal = splat(0.0f); g.depth = 0.0f; g.hit = false;
     g.slot = 0u; g.u = 0.0f; g.v = 0.0f; g.direct_triangle = false;
+    g.direct_prim = false; g.mid = -1; g.pos = splat(0.0f);
     f3 tint = splat(1.0f);
     float dist = 0.0f;
     for (int events = 0;; ++events) {
@@ -108,6 +110,8 @@ PT_DEV GuideSample guide_sample(const DevScene& sc, Ray ray, const TravStack& st
             g.hit = true;
             g.direct_triangle = events == 0 && mid == -1;
             g.slot = th.slot; g.u = th.u; g.v = th.v;
+            g.direct_prim = events == 0 && mid >= 0;
+            g.mid = mid; g.pos = ray.pos;
             return g;
         }
         const f3 n = ray.normal;                                  // the shading normal as finish_closest leaves it (what bsdf sampling frames)

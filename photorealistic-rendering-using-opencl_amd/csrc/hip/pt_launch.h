@@ -61,6 +61,11 @@ void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa
 // sc.tri_geom) of the geometry before the update(s): the motion instances of the guide kernels
 void launch_guides_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
                           float4* motion, hipStream_t stream);
+// ... with a primitive snapshot pending (prt.h prt_update_primitives): prims the sphere / SDF / quad tables before the update(s) (pt_prims.h);
+// tri_prev null = no triangle snapshot pending: the instances without the triangle term
+struct PrimPrev;
+void launch_guides_prim_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                               const PrimPrev& prims, float4* motion, hipStream_t stream);
 void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                     const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
 // ... its pieces: dn_var_kernel's {rgb, v} into out; a-trous pass i (step 2^i, its Gaussian into g first) from `in` into `out`, with the
@@ -108,6 +113,11 @@ void launch_refit_check(const float* vertices, size_t n_vertices, uint32_t* flag
 // into root6 (device, 6 floats)
 void launch_refit(const RefitTables& t, const float* vertices, const float* normals, NodePair* pairs, TriGeom* tri_geom, TriNrm* tri_nrm,
                   float* root6, hipStream_t stream);
+// pt_prims.hip.  prt_update_primitives: `count` prt_mesh records (device, 16-byte aligned; n_spheres spheres, then n_sdfs SDF primitives, then
+// quads) into the three tables, and 1 into *flag (device; the caller zeroes it first) if a record's t differs from types[i] or a field that
+// is read is not finite
+void launch_prims_pack(const void* meshes, uint32_t count, uint32_t n_spheres, uint32_t n_sdfs, const uint8_t* types, DevSphere* spheres,
+                       DevSdf* sdfs, DevQuad* quads, uint32_t* flag, hipStream_t stream);
 // pt_normals.hip.  prt_set_smooth_normals: the topology on the device and the face buffer (all device memory)
 struct SmoothTables {
     const uint32_t* corner_group;   // 3 n_tris: the group of every corner
