@@ -714,6 +714,57 @@ int prt_set_walk_min_lanes(prt_ctx* ctx, uint32_t lanes);
  *                               call sees a launch end without a report (PRT_ERR_HIP, state unusable until prt_reset) */
 int prt_set_option(prt_ctx* ctx, const char* name, int value);
 
+/* ---- Ray queries (no counterpart in the reference): closest hit, occlusion and pixel picking against the uploaded scene as it is NOW --
+ * after every prt_update_vertices, prt_rebuild_bvh and prt_update_primitives -- without a render.  What is under the mouse (to choose the
+ * sphere or the triangle to move), how far away the middle of the picture is (to set focalDistance), whether two points see each other.
+ *
+ * A cast sees exactly what a path segment of the render sees; the code is the render's (csrc/hip/pt_device.h, pt_cast.h):
+ *
+ * Closest hit, per valid ray:  limit = min(tmax, 20.0f)  (20 is the reference's INF, the farthest hit a ray of the render has);  ray_pre;
+ *   walk_begin(sc, false, ray, limit, ...) and the walk run to its end;  finish_closest, with ray.normal = 0 before the call as the guides set it.
+ *   The ray is a hit when the final t < limit.
+ * Hit record:  t, pos, normal and backside (flags bit 0) are as finish_closest leaves them, the flip of the normal of a non-transmissive
+ *   material towards the ray included (as in the reference, a triangle's material is looked up one record in front of the mesh table for
+ *   this: in a scene whose config has a dielectric kind active the normal of a triangle hit is never turned, in every other scene it
+ *   always faces the ray).  id is finish_closest's mesh id: i >= 0 = meshes[i] of the upload (a sphere, an SDF primitive or a
+ *   quad), PRT_HIT_TRIANGLE for a triangle of the mesh.  For a triangle u, v are its barycentrics (the hit is p0 (1 - u - v) + p1 u + p2 v)
+ *   and tri its index in the caller's vertex arrays -- vertices 3 tri .. 3 tri + 2, the number the refit tables hold for the slot
+ *   (slot_vtx[slot] / 3): it survives prt_rebuild_bvh.  For every other kind of hit u, v and tri are 0.  A miss has id = PRT_HIT_MISS and
+ *   every other word 0.
+ * Directions:  the direction is used as given, it is not normalised, and t is in units of its length.  The triangle, box and quad tests
+ *   hold for any length; the sphere and SDF tests assume a UNIT direction, as the render's rays have it.
+ * Occlusion:  the render's shadow(): the any-hit walk with limit as above (1 = a triangle in (eps, limit)), and when the tree did not
+ *   occlude, finish_shadow(origin, dir, limit): spheres, SDF primitives (shadow_marching_steps), quads.  eps = 1e-5.
+ * Invalid rays:  a ray whose origin or direction has a non-finite component, whose direction is all zeros, or whose tmax is NaN or <= 0 is
+ *   never walked: the casts report a miss for it, the occlusion tests 0.  The call itself succeeds.
+ * prt_cast_pixels:  the ray of pixel (x, y), full-frame coordinates in framebuffer order (y as the rows of prt_read_framebuffer and of the guides): the centre ray of the pixel
+ *   through the middle of the lens -- the guides' camera ray at offset 0 with the aperture point at the camera's position; for a pinhole
+ *   camera sample 0 of prt_render_guides --, tmax = 20.  The rays are generated on the device and go through the same kernel.  Needs a
+ *   camera and a frame size; a pixel outside [0, width) x [0, full_height) is reported as a miss.
+ *
+ * Every call reads the scene tables only.  It writes nothing of the context: path state, framebuffer, statistics plane, guides and their
+ * validity, both histories, pending motion snapshots and measured tile orders stay as they are.  It is ordered on the context's stream and
+ * complete on return, as prt_update_vertices_device is.  The host variants stage through buffers of the context, grown on demand and freed
+ * by prt_destroy; the device variants take device memory, 16-byte aligned (rays: n x 32 bytes; hits: n x 48 bytes; out: n x 4 bytes).
+ * Works on every uploaded tree, those prt_update_vertices refuses for their depth included, and needs neither camera nor frame size
+ * (prt_cast_pixels does).
+ * Refusals (the output is untouched):  PRT_ERR_NOT_READY without a scene, after a render call that failed half-way, and for prt_cast_pixels
+ * without a camera or a frame size;  PRT_ERR_INVALID_ARGUMENT for a null pointer with n > 0, a misaligned device pointer and n > 2^26.
+ * n == 0 succeeds and does nothing. */
+#define PRT_HIT_MISS (-2)
+#define PRT_HIT_TRIANGLE (-1)
+typedef struct prt_ray { float origin[3]; float tmax; float dir[3]; float _pad; } prt_ray;   /* 32 bytes */
+typedef struct prt_hit {                                                                      /* 48 bytes */
+    float t, u, v; uint32_t tri;        /* tri: triangle index in the caller's vertex arrays (vertices 3 tri .. 3 tri + 2) */
+    float normal[3]; int32_t id;        /* id: PRT_HIT_MISS (-2), PRT_HIT_TRIANGLE (-1), or i >= 0 = meshes[i] of the upload */
+    float pos[3]; uint32_t flags;       /* bit 0: backside */
+} prt_hit;
+int prt_cast_rays(prt_ctx* ctx, const prt_ray* rays, uint32_t n, prt_hit* hits);                  /* host memory */
+int prt_cast_rays_device(prt_ctx* ctx, const void* d_rays, uint32_t n, void* d_hits);             /* device memory, 16-byte aligned */
+int prt_occluded(prt_ctx* ctx, const prt_ray* rays, uint32_t n, uint32_t* out);                   /* 1 = something in (eps, limit) */
+int prt_occluded_device(prt_ctx* ctx, const void* d_rays, uint32_t n, void* d_out);
+int prt_cast_pixels(prt_ctx* ctx, const int32_t* xy, uint32_t n, prt_hit* hits);                  /* n (x, y) pairs, full-frame coordinates */
+
 /* What this library was built from (no counterpart in the reference): a hash of the content of every source, header and compiler flag
  * of libprt.so, compiled in by the build (photorealistic-rendering-using-opencl_amd/build.py source_build_id(); a development variant of
  * tools/build_variant.sh reads "variant-<name>-<hash>").  bench.py prints it as `build_id` and refuses to time a library whose id is

@@ -441,6 +441,48 @@ class Renderer:
             self._chk(self.lib.prt_read_bvh(self.ctx, nodes.ctypes.data_as(C.c_void_p), C.byref(count), prims.ctypes.data_as(C.c_void_p)), "prt_read_bvh")
         return nodes, prims
 
+    def _query(self, name, rays, out, words):
+        """prt_cast_rays / prt_occluded and their device variants: rays a float32 [n, 8] numpy array (host door) or a tensor on this context's
+        device (device door: work queued on torch's current stream is waited for; `out` a float32 tensor of n x words elements, or None for a
+        new one)"""
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if rays.dim() != 2 or rays.shape[1] != _capi.RAY_FLOATS:
+                raise ValueError("%s: needs a [n, 8] float32 tensor (prt_ray: origin, tmax, dir, pad)" % name)
+            n = int(rays.shape[0])
+            if out is None:
+                out = torch.zeros((n, words) if words > 1 else (n,), dtype=torch.float32, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()
+            self._chk(getattr(self.lib, name + "_device")(self.ctx, self._device_ptr(rays, n * _capi.RAY_FLOATS, name), n,
+                                                          self._device_ptr(out, n * words, name)), name + "_device")
+            return out
+        r = np.ascontiguousarray(rays, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != _capi.RAY_FLOATS:
+            raise ValueError("%s: needs a float32 array [n, 8] (prt_ray: origin, tmax, dir, pad)" % name)
+        host = np.zeros(len(r) * words, dtype=np.uint32)
+        self._chk(getattr(self.lib, name)(self.ctx, r.ctypes.data_as(C.c_void_p), len(r), host.ctypes.data_as(C.c_void_p)), name)
+        return host
+
+    def cast_rays(self, rays, out=None):
+        """prt_cast_rays / prt_cast_rays_device: the closest hit of every ray against the scene as it is now (prt.h "Ray queries").  rays
+        float32 [n, 8] = {origin.xyz, tmax, dir.xyz, pad}.  A numpy array returns a structured array of _capi.HIT_DTYPE (t, u, v, tri, normal,
+        id, pos, flags); a tensor on this device writes the records (12 words each) into `out` (float32 [n, 12], or a new tensor) and returns it"""
+        res = self._query("prt_cast_rays", rays, out, _capi.HIT_FLOATS)
+        return res.view(np.dtype(_capi.HIT_DTYPE)) if isinstance(res, np.ndarray) else res
+
+    def occluded(self, rays, out=None):
+        """prt_occluded / prt_occluded_device: 1 per ray with something in (eps, tmax), else 0.  numpy in: uint32 [n] out; a tensor in: the
+        flags as the words of a float32 [n] tensor (view it as int32)"""
+        return self._query("prt_occluded", rays, out, 1)
+
+    def cast_pixels(self, xy):
+        """prt_cast_pixels: the hit of the centre ray of every pixel (x, y) of xy (int32 [n, 2], full-frame coordinates, framebuffer order):
+        a structured array of _capi.HIT_DTYPE.  Needs a camera and a frame size"""
+        p = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        host = np.zeros(len(p), dtype=np.dtype(_capi.HIT_DTYPE))
+        self._chk(self.lib.prt_cast_pixels(self.ctx, p.ctypes.data_as(C.c_void_p), len(p), host.ctypes.data_as(C.c_void_p)), "prt_cast_pixels")
+        return host
+
     def set_camera(self, cam):
         self._chk(self.lib.prt_set_camera(self.ctx, C.byref(cam)), "prt_set_camera")
 

@@ -108,6 +108,11 @@ PATH_STATE_DTYPE = [("origin", "<f4", 4), ("dir", "<f4", 4), ("time", "<f4"), ("
 # numpy view of the 36-byte prt_bvh_node (BvhNode above)
 BVH_NODE_DTYPE = [("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)]
 
+# numpy views of prt_ray (32 bytes; as float32 [n, 8]: origin, tmax, dir, pad) and prt_hit (48 bytes) of the ray queries (include/prt.h)
+RAY_FLOATS, HIT_FLOATS = 8, 12
+HIT_DTYPE = [("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"), ("normal", "<f4", 3), ("id", "<i4"), ("pos", "<f4", 3), ("flags", "<u4")]
+HIT_MISS, HIT_TRIANGLE = -2, -1
+
 # prt_set_smooth_normals: the weightings by name and the loader's crease (PRT_NORMALS_*, PRT_LOADER_CREASE_COS of include/prt.h)
 NORMALS_WEIGHTINGS = {"unit": 0, "area": 1}
 LOADER_CREASE_COS = -0.99619470
@@ -121,6 +126,11 @@ PRT_API = [
     ("prt_update_vertices_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_update_primitives", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_update_primitives_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("prt_cast_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("prt_cast_rays_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("prt_occluded", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("prt_occluded_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("prt_cast_pixels", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("prt_read_bvh_bounds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_rebuild_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_rebuild_bvh_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),

@@ -143,6 +143,7 @@ extern "C" void prt_destroy(prt_ctx* c) {
     free_dev(c->d_counters);
     free_dev(c->d_filter_tab);
     free_dev(c->d_rec);
+    free_dev(c->d_cast_rays); free_dev(c->d_cast_out);
     free_dev(c->rec_hist.planes);
     free_dev(c->rec_hist.guides);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

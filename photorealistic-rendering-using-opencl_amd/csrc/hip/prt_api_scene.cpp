@@ -75,8 +75,6 @@ extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
 
 // ---- deforming geometry: new vertices into the uploaded tree (prt.h prt_update_vertices; pt_refit.hip) ----------------------------------------
 
-static int refit_tables(prt_ctx* c);
-
 // the size limits of the tables a refit or a rebuild writes and the render kernels read by 32-bit offsets (prt.h PRT_MAX_*; pt_layout.h)
 static int table_limits(prt_ctx* c, const std::string& who, uint64_t slots, uint64_t pairs) {
     const char* m = table_limit_error(slots, pairs, (uint64_t)c->sc.n_meshes + 2u);
@@ -96,7 +94,7 @@ static int refit_prepare(prt_ctx* c, const void* vertices, const char* who) {
 }
 
 // the tables of the uploaded tree on the device (a rebuilt tree's are there from its build)
-static int refit_tables(prt_ctx* c) {
+int refit_tables(prt_ctx* c) {
     if (!c->refit_ready) {
         int rc;
         if ((rc = upload(c, c->d_slot_vtx, c->slot_vtx)) || (rc = upload(c, c->d_level_pairs, c->level_pairs))) return rc;

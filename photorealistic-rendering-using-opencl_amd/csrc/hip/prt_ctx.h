@@ -1,6 +1,7 @@
 // prt_ctx.h -- the context behind the C ABI of include/prt.h and what the files that implement it share (internal: not installed).
 // The entry points by call group: prt_api.cpp (context, frame, camera, map, options, read-backs, selftests), prt_api_scene.cpp (upload,
-// refit, rebuild), prt_api_render.cpp (the render drivers, guides, motion), prt_api_denoise.cpp (the filter, both histories, the records).
+// refit, rebuild), prt_api_render.cpp (the render drivers, guides, motion), prt_api_denoise.cpp (the filter, both histories, the records),
+// prt_api_query.cpp (ray queries).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -179,6 +180,11 @@ struct prt_ctx {
     float smooth_crease = 0.0f;
     void* d_sm_group = nullptr; void* d_sm_first = nullptr; void* d_sm_member = nullptr;
     void* d_sm_face_f = nullptr; void* d_sm_face_r = nullptr; void* d_sm_nrm = nullptr;
+    // prt_cast_rays / prt_occluded / prt_cast_pixels (pt_cast.hip): the host variants' staging buffers -- rays (32 bytes each; prt_cast_pixels
+    // puts its (x, y) pairs behind the rays it generates) and results (48 bytes each).  Not the scene's and not the frame's: grown on demand,
+    // freed by prt_destroy alone
+    void* d_cast_rays = nullptr; void* d_cast_out = nullptr;
+    size_t cast_rays_cap = 0, cast_out_cap = 0;
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PRT_ERR_INVALID_ARGUMENT; } while (0)
@@ -216,6 +222,10 @@ int upload(prt_ctx* c, void*& dst, const std::vector<T>& src) {
     if (!src.empty()) HIPCHK(c, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return PRT_OK;
 }
+
+// the tables of the uploaded tree on the device -- slot_vtx, level_pairs, the root's box -- unless an update or a rebuild has put them there
+// (prt_api_scene.cpp; the ray queries share slot_vtx with the refit)
+int refit_tables(prt_ctx* c);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -157,5 +157,11 @@ hipError_t launch_build_tree(const BuildWork& w, const float* vertices, uint32_t
 // per new slot: TriNrm from the triangle's old slot (carry_nrm) and the motion snapshot in the new slot order (prev_new non-null; pt_build.h)
 void launch_build_carry(const BuildWork& w, const uint32_t* slot_vtx, uint32_t n_slots, bool carry_nrm, const TriNrm* nrm_old, TriNrm* nrm_new,
                         const TriGeom* prev_old, const TriGeom* geom_new, TriGeom* prev_new, hipStream_t stream);
+// pt_cast.hip.  prt_cast_rays / prt_occluded: n prt_ray records (device, 16-byte aligned) through the scene; any_hit false: one prt_hit per
+// ray into out (48 bytes each, 16-byte aligned), true: one uint32 per ray.  slot_vtx: the first caller vertex of every slot's triangle
+// (device; null for a scene without triangles).  The instance is chosen by sc.n_sdfs
+void launch_cast(const DevScene& sc, bool any_hit, const void* rays, uint32_t n, const uint32_t* slot_vtx, void* out, hipStream_t stream);
+// prt_cast_pixels: the rays of the n pixels xy (device, n (x, y) pairs) of a width x full_height frame into rays (n prt_ray records)
+void launch_cast_pixel_rays(const DevCamera& cam, int width, int full_height, const int32_t* xy, uint32_t n, void* rays, hipStream_t stream);
 
 }  // namespace prt

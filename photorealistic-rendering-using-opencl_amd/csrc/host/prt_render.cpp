@@ -104,6 +104,8 @@ int main(int argc, char** argv) {
     float orbit_yaw = 0.0f;                                        // -orbit-yaw RAD: ... RAD of yaw apart
     std::string filter = "none";                                   // -filter NAME: the pixel filter (prt_set_pixel_filter)
     float filter_radius = PRT_FILTER_DEFAULT_RADIUS;               // -filter-radius R
+    bool pick = false;                                             // -pick X,Y: print the hit of that pixel (prt_cast_pixels) and render nothing
+    int pick_x = 0, pick_y = 0;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -131,6 +133,10 @@ int main(int argc, char** argv) {
         else if (a == "-orbit-yaw") orbit_yaw = (float)std::atof(next());
         else if (a == "-filter") filter = next();
         else if (a == "-filter-radius") filter_radius = (float)std::atof(next());
+        else if (a == "-pick") {
+            if (std::sscanf(next(), "%d,%d", &pick_x, &pick_y) != 2) { std::fprintf(stderr, "-pick: needs X,Y (full-frame pixel coordinates, framebuffer order)\n"); return 2; }
+            pick = true;
+        }
     }
     static const char* const filter_names[] = {"none", "box", "tent", "gaussian", "blackman-harris"};
     uint32_t filter_kind = 5;
@@ -191,6 +197,16 @@ int main(int argc, char** argv) {
         }
         CHECK(prt_resize(ctx, window_width, window_height));       // cl_flattenI, :451
         if (filter_kind != PRT_FILTER_NONE) CHECK(prt_set_pixel_filter(ctx, filter_kind, filter_radius));
+        if (pick) {                                                // one line on stdout: what is under that pixel (%.9g: the floats round-trip)
+            const int32_t xy[2] = {pick_x, pick_y};
+            prt_hit h;
+            CHECK(prt_cast_pixels(ctx, xy, 1, &h));
+            std::printf("pick %d,%d: id=%d tri=%u t=%.9g pos=%.9g,%.9g,%.9g normal=%.9g,%.9g,%.9g u=%.9g v=%.9g backside=%u\n", pick_x, pick_y, (int)h.id,
+                        (unsigned)h.tri, (double)h.t, (double)h.pos[0], (double)h.pos[1], (double)h.pos[2], (double)h.normal[0], (double)h.normal[1],
+                        (double)h.normal[2], (double)h.u, (double)h.v, (unsigned)(h.flags & 1u));
+            prt_destroy(ctx);
+            return 0;
+        }
 
         const unsigned max_frames = frames ? frames : spp * (unsigned)(cfg.max_bounces > 8 ? cfg.max_bounces : 8) + 64;
         std::vector<int32_t> seeds((size_t)max_frames * 2);
