@@ -326,7 +326,7 @@ int prt_read_normals(prt_ctx* ctx, float* normals /* float4[3T] */);
 int prt_set_camera(prt_ctx* ctx, const prt_camera* cam);
 
 /* cl_env_map, src/main.cpp:433-437 + include/GL/cl_gl_interop.h:71-86: RGB float, row 0 first.
- * Without a call the map is a 1x1 black texel. */
+ * Without a call the map is a 1x1 black texel.  The map is the context's, not the scene's: it survives prt_upload_scene. */
 int prt_upload_envmap(prt_ctx* ctx, const float* rgb, int width, int height);
 
 /* cl_flattenI = W*H*112 bytes, src/main.cpp:451; output texture tex0.  Implies prt_reset. */

@@ -143,7 +143,11 @@ struct prt_ctx {
     // one (node 0 the root, the children of pair k nodes 2k + 1 and 2k + 2).  up_nodes / up_prims: the caller's tree as uploaded, for
     // prt_read_bvh.  A rebuild writes into the `spare` set of buffers and swaps it with the live one at its end; cap_*: what the live buffers
     // hold.  d_build: the build's scratch (BuildWork bw over build_T triangles).  Spare set and scratch are allocated by the first rebuild and
-    // freed with the scene
+    // OUTLIVE the scene: prt_upload_scene frees the live set (and with it the refit tables, the staging buffers, the snapshot and the primitive
+    // tables below) but keeps the spare set and the scratch for the next scene's rebuilds -- prt_destroy alone frees them.  Nothing in them is
+    // read before it is written: a rebuild sizes the spare set by spare.cap_* (grown when the new T needs more, kept when it needs less), the
+    // scratch by build_T (laid out again whenever T differs), and the live capacities cap_* are set by every upload to what it allocated
+    // (tests/test_call_sequences.py: uploads of fewer and of more triangles between rebuilds)
     size_t n_slots = 0;
     bool rebuilt = false;
     std::vector<prt_bvh_node> up_nodes;
