@@ -42,8 +42,8 @@ extern "C" int prt_create(int device, const prt_config* cfg, prt_ctx** out) {
     c->cfg = *cfg;
     if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), (4 + 2 * prt_ctx::MAX_SUB) * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(c->d_counters, 0, (4 + 2 * prt_ctx::MAX_SUB) * sizeof(unsigned long long))) != hipSuccess ||
+        (e = c->ctx.counters.alloc(4 + 2 * prt_ctx::MAX_SUB)) != hipSuccess ||
+        (e = hipMemset(c->ctx.counters, 0, (4 + 2 * prt_ctx::MAX_SUB) * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipHostMalloc(reinterpret_cast<void**>(&c->h_unfinished), (prt_ctx::MAX_SUB + 1) * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming)) != hipSuccess) {
         g_global_error = std::string("prt_create: ") + hipGetErrorString(e);
@@ -77,48 +77,6 @@ extern "C" int prt_create(int device, const prt_config* cfg, prt_ctx** out) {
     return PRT_OK;
 }
 
-static void free_frame(prt_ctx* c) {
-    free_dev(c->S.q0);
-    free_dev(c->S.q1);
-    free_dev(c->S.q2);
-    free_dev(c->S.q3);
-    free_dev(c->S.q4);
-    free_dev(c->fb);
-    free_dev(c->d_adapt);
-    free_dev(c->d_live);
-    free_dev(c->d_live_aux);
-    free_dev(c->d_guides);
-    free_dev(c->d_dn);
-    free_dev(c->d_dn_g);
-    free_dev(c->hist.planes);
-    free_dev(c->hist.guides);
-    free_dev(c->d_motion);
-    c->motion_valid = false;
-    c->guides_valid = false;
-    c->hist.valid = false;
-    for (int j = 0; j < prt_ctx::MAX_SUB; ++j) {
-        free_dev(c->d_tile_order[j]);
-        free_dev(c->d_tile_cost[j]);
-    }
-    forget_tile_orders(c);
-}
-static void free_scene(prt_ctx* c) {
-    free_dev(c->d_pairs); free_dev(c->d_tri_geom); free_dev(c->d_tri_nrm);
-    free_dev(c->d_spheres); free_dev(c->d_quads); free_dev(c->d_sdfs); free_dev(c->d_mats); free_dev(c->d_light_tab);
-    free_dev(c->d_slot_vtx); free_dev(c->d_level_pairs); free_dev(c->d_refit_root); free_dev(c->d_stage_vtx); free_dev(c->d_stage_nrm);
-    c->refit_ready = c->refitted = false;
-    free_dev(c->d_tri_prev);
-    c->snap_valid = false;
-    free_dev(c->spare.pairs); free_dev(c->spare.tri_geom); free_dev(c->spare.tri_nrm); free_dev(c->spare.slot_vtx); free_dev(c->spare.level_pairs);
-    free_dev(c->spare.root); free_dev(c->spare.tri_prev); free_dev(c->d_build);
-    c->spare = prt_ctx::TreeSet{};
-    c->build_T = 0;
-    c->cap_pairs = c->cap_slots = c->cap_prev = 0;
-    c->rebuilt = false;
-    free_smooth(c);
-    free_prims(c, true);
-}
-
 extern "C" void prt_destroy(prt_ctx* c) {
 #ifdef PT_PHASE_CLOCKS
     if (c) { (void)hipDeviceSynchronize(); prt::dump_phase_clocks(); }
@@ -136,20 +94,10 @@ extern "C" void prt_destroy(prt_ctx* c) {
     }
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->h_unfinished) (void)hipHostFree(c->h_unfinished);
-    free_frame(c);
-    free_scene(c);
-    free_dev(c->d_env); free_dev(c->d_env_rows); free_dev(c->d_env_cols);
-    free_dev(c->d_seeds);
-    free_dev(c->d_counters);
-    free_dev(c->d_filter_tab);
-    free_dev(c->d_rec);
-    free_dev(c->d_cast_rays); free_dev(c->d_cast_out);
-    free_dev(c->rec_hist.planes);
-    free_dev(c->rec_hist.guides);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                                   // (every device buffer: the context's device is the current one)
 }
 
 extern "C" int prt_set_camera(prt_ctx* c, const prt_camera* cam) {
@@ -157,8 +105,25 @@ extern "C" int prt_set_camera(prt_ctx* c, const prt_camera* cam) {
     if (!cam) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_camera: null camera");
     make_dev_camera(*cam, c->cam);
     c->have_cam = true;
-    c->guides_valid = false;
+    c->frame.guides_valid = false;
     forget_tile_orders(c);      // (tile costs are the view's)
+    return PRT_OK;
+}
+
+// the map and, for prt_config::env_importance_sampling, its sampling density (pt_kernels.hip build_env_cdf)
+static int env_tables(prt_ctx* c, const float* rgb, int w, int h) {
+    CtxBuffers& x = c->ctx;
+    x.env_rows.reset(); x.env_cols.reset();
+    x.env_w = w; x.env_h = h;
+    const size_t n = (size_t)w * h * 3;
+    HIPCHK(c, x.env.alloc(n));
+    HIPCHK(c, hipMemcpy(x.env, rgb, n * sizeof(float), hipMemcpyHostToDevice));
+    if (c->cfg.env_importance_sampling) {
+        std::vector<float> rows, cols;
+        build_env_cdf(rgb, w, h, rows, cols);
+        HIPCHK(c, x.env_rows.upload(rows));
+        HIPCHK(c, x.env_cols.upload(cols));
+    }
     return PRT_OK;
 }
 
@@ -171,26 +136,11 @@ extern "C" int prt_upload_envmap(prt_ctx* c, const float* rgb, int w, int h) {
         return fail(c, PRT_ERR_UNSUPPORTED, "prt_upload_envmap: a side of more than 16777215 texels (PRT_MAX_ENV_SIDE: the texel index is a 24-bit multiply)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->guides_valid = false;
-    c->hist.valid = false;
-    free_dev(c->d_env);
-    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-    HIPCHK(c, hipMalloc(&c->d_env, bytes));
-    HIPCHK(c, hipMemcpy(c->d_env, rgb, bytes, hipMemcpyHostToDevice));
-    c->sc.env = static_cast<const float*>(c->d_env);
-    c->sc.env_w = w; c->sc.env_h = h;
-    free_dev(c->d_env_rows); free_dev(c->d_env_cols);
-    c->sc.env_cdf_rows = c->sc.env_cdf_cols = nullptr;
-    if (c->cfg.env_importance_sampling) {                       // the map's sampling density (pt_kernels.hip build_env_cdf)
-        std::vector<float> rows, cols;
-        build_env_cdf(rgb, w, h, rows, cols);
-        int rc = upload(c, c->d_env_rows, rows);
-        if (!rc) rc = upload(c, c->d_env_cols, cols);
-        if (rc) return rc;
-        c->sc.env_cdf_rows = static_cast<const float*>(c->d_env_rows);
-        c->sc.env_cdf_cols = static_cast<const float*>(c->d_env_cols);
-    }
-    return PRT_OK;
+    c->frame.guides_valid = false;
+    c->frame.hist.valid = false;
+    const int rc = env_tables(c, rgb, w, h);
+    bind(c);
+    return rc;
 }
 
 static int alloc_frame(prt_ctx* c, int width, int full_height, int row0, int rows);
@@ -220,21 +170,22 @@ static int alloc_frame(prt_ctx* c, int width, int full_height, int row0, int row
     // the context has no frame until every plane of the new one exists: a failed (re)allocation must leave it NOT READY,
     // never "ready" with null planes
     c->have_size = false;
-    free_frame(c);
+    c->frame = Frame{};
     c->npix = 0;
     const size_t npix = (size_t)width * (size_t)rows;
-    hipError_t e = hipSuccess;
-    void** planes[6] = {reinterpret_cast<void**>(&c->S.q0), reinterpret_cast<void**>(&c->S.q1), reinterpret_cast<void**>(&c->S.q2),
-                        reinterpret_cast<void**>(&c->S.q3), reinterpret_cast<void**>(&c->S.q4), reinterpret_cast<void**>(&c->fb)};
-    for (int k = 0; k < 6 && e == hipSuccess; ++k) e = hipMalloc(planes[k], npix * 16);
+    Frame& f = c->frame;
+    DevBuf<float4>* planes[5] = {&f.q0, &f.q1, &f.q2, &f.q3, &f.fb};
+    hipError_t e = f.q4.alloc(npix);
+    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = planes[k]->alloc(npix);
     const size_t n_tiles_alloc = (size_t)render_tile_count(width, rows);
     for (int j = 0; j < c->n_sub && c->n_sub > 1 && e == hipSuccess; ++j) {
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_tile_order[j]), n_tiles_alloc * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tile_cost[j]), n_tiles_alloc * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(c->d_tile_cost[j], 0, n_tiles_alloc * sizeof(uint32_t));    // (a forced 5-wave build reports no costs: all equal then)
+        e = f.tile_order[j].alloc(n_tiles_alloc);
+        if (e == hipSuccess) e = f.tile_cost[j].alloc(n_tiles_alloc);
+        if (e == hipSuccess) e = hipMemset(f.tile_cost[j], 0, n_tiles_alloc * sizeof(uint32_t));    // (a forced 5-wave build reports no costs: all equal then)
     }
+    if (e != hipSuccess) c->frame = Frame{};
+    bind(c);
     if (e != hipSuccess) {
-        free_frame(c);
         (void)hipGetLastError();
         c->err = std::string("prt frame allocation (") + std::to_string(width) + " x " + std::to_string(rows) + "): " + hipGetErrorString(e);
         return PRT_ERR_HIP;
@@ -258,10 +209,10 @@ extern "C" int prt_reset(prt_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->S.q2, 0, c->npix * 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->S.q3, 0, c->npix * 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->S.q4, 0, c->npix * 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->fb, 0, c->npix * 16, c->stream));
-    if (c->d_adapt) HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, c->npix * sizeof(float2), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->frame.fb, 0, c->npix * 16, c->stream));
+    if (c->frame.adapt) HIPCHK(c, hipMemsetAsync(c->frame.adapt, 0, c->npix * sizeof(float2), c->stream));
     c->fresh = true;
-    c->stats_valid = false;
+    c->frame.stats_valid = false;
     return PRT_OK;
 }
 
@@ -293,12 +244,12 @@ extern "C" int prt_set_pixel_filter(prt_ctx* c, uint32_t kind, float radius) {
     if (kind >= PRT_FILTER_GAUSSIAN) {
         float tab[PT_FILTER_TAB + 1];
         build_filter_table(kind, r, tab);
-        if (!c->d_filter_tab) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_filter_tab), sizeof(tab)));
-        HIPCHK(c, hipMemcpy(c->d_filter_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        HIPCHK(c, c->ctx.filter_tab.first_use(PT_FILTER_TAB + 1));
+        HIPCHK(c, hipMemcpy(c->ctx.filter_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
     c->filter_kind = kind;
     c->filter_r = r;
-    c->guides_valid = false;                               // (the temporal history is kept, as by prt_set_camera)
+    c->frame.guides_valid = false;                               // (the temporal history is kept, as by prt_set_camera)
     return c->have_size ? prt_reset(c) : PRT_OK;
 }
 
@@ -407,7 +358,7 @@ extern "C" int prt_read_framebuffer(prt_ctx* c, float* rgba) {
     if (!rgba || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_framebuffer: bad arguments");
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpy(rgba, c->fb, c->npix * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rgba, c->frame.fb, c->npix * 16, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -415,13 +366,11 @@ extern "C" int prt_tonemap_rgba8(prt_ctx* c, uint8_t* rgba) {
     CTX_CHECK(c);
     if (!rgba || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_tonemap_rgba8: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    unsigned char* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), c->npix * 4));
-    launch_tonemap(c->fb, d, frame_args(c, 1, 0, nullptr, 0, false), c->stream);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(rgba, d, c->npix * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIPCHK(c, e);
+    DevBuf<unsigned char> d;
+    HIPCHK(c, d.alloc(c->npix * 4));
+    launch_tonemap(c->frame.fb, d, frame_args(c, 1, 0, nullptr, 0, false), c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(rgba, d, c->npix * 4, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -429,7 +378,7 @@ extern "C" int prt_copy_framebuffer_to_device(prt_ctx* c, void* device_rgba) {
     CTX_CHECK(c);
     if (!device_rgba || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_copy_framebuffer_to_device: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(device_rgba, c->fb, c->npix * 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(device_rgba, c->frame.fb, c->npix * 16, hipMemcpyDeviceToDevice, c->stream));
     // on a caller's stream (prt_set_stream) the copy is ordered like any other work of the caller; the context's own
     // stream is private and non-blocking, nothing of the caller's could wait for it: finish the copy before returning
     if (c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -440,13 +389,11 @@ extern "C" int prt_read_state(prt_ctx* c, prt_path_state* state) {
     CTX_CHECK(c);
     if (!state || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_state: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    prt_path_state* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), c->npix * sizeof(prt_path_state)));
+    DevBuf<prt_path_state> d;
+    HIPCHK(c, d.alloc(c->npix));
     launch_state_to_rtd(c->S, d, c->npix, c->stream);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(state, d, c->npix * sizeof(prt_path_state), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIPCHK(c, e);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(state, d, c->npix * sizeof(prt_path_state), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -454,15 +401,14 @@ extern "C" int prt_write_state(prt_ctx* c, const prt_path_state* state) {
     CTX_CHECK(c);
     if (!state || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_write_state: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    prt_path_state* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), c->npix * sizeof(prt_path_state)));
-    hipError_t e = hipMemcpy(d, state, c->npix * sizeof(prt_path_state), hipMemcpyHostToDevice);
-    if (e == hipSuccess) { launch_rtd_to_state(d, c->S, c->fb, c->npix, c->stream); e = hipStreamSynchronize(c->stream); }
-    (void)hipFree(d);
-    HIPCHK(c, e);
+    DevBuf<prt_path_state> d;
+    HIPCHK(c, d.alloc(c->npix));
+    HIPCHK(c, hipMemcpy(d, state, c->npix * sizeof(prt_path_state), hipMemcpyHostToDevice));
+    launch_rtd_to_state(d, c->S, c->frame.fb, c->npix, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->state_undefined = false;
     c->fresh = false;
-    c->stats_valid = false;
+    c->frame.stats_valid = false;
     return PRT_OK;
 }
 
@@ -487,10 +433,10 @@ extern "C" int prt_query_counts(prt_ctx* c, uint32_t spp, prt_stats* out) {
     CTX_CHECK(c);
     if (!out || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_query_counts: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemsetAsync(c->d_counters + 1, 0, 3 * sizeof(unsigned long long), c->stream));
-    launch_count(c->S, c->npix, spp, c->d_counters + 1, c->stream);
+    HIPCHK(c, hipMemsetAsync(c->ctx.counters + 1, 0, 3 * sizeof(unsigned long long), c->stream));
+    launch_count(c->S, c->npix, spp, c->ctx.counters + 1, c->stream);
     unsigned long long h[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, c->d_counters + 1, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h, c->ctx.counters + 1, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     int rc = prt_synchronize(c);
     if (rc) return rc;
     c->stats.samples = h[0]; c->stats.segments = h[1]; c->stats.finished_pixels = h[2];
@@ -502,19 +448,16 @@ extern "C" int prt_selftest_math(prt_ctx* c, int fn, const float* a, const float
     CTX_CHECK(c);
     if (!a || !b || !out || n <= 0) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_math: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
+    DevBuf<float> da, db, dout;
     const size_t bytes = (size_t)n * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&da), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&db), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), bytes);
-    if (e == hipSuccess) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) { launch_selftest_math(fn, da, db, dout, n, c->stream); e = hipStreamSynchronize(c->stream); }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-    if (da) (void)hipFree(da);
-    if (db) (void)hipFree(db);
-    if (dout) (void)hipFree(dout);
-    HIPCHK(c, e);
+    HIPCHK(c, da.alloc(n));
+    HIPCHK(c, db.alloc(n));
+    HIPCHK(c, dout.alloc(n));
+    HIPCHK(c, hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
+    launch_selftest_math(fn, da, db, dout, n, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -522,7 +465,7 @@ extern "C" int prt_selftest_fn(prt_ctx* c, int fn, const float* params, const fl
     CTX_CHECK(c);
     if (!params || !in || !out || n <= 0 || fn < 1 || fn > 14) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: bad arguments");
     const bool env_fn = fn == 13 || fn == 14;                  // environment importance sampling on the uploaded map (pt_selftest.h selftest_env)
-    if (env_fn && !(c->sc.env_cdf_rows && c->sc.env_cdf_cols && c->d_env))
+    if (env_fn && !(c->sc.env_cdf_rows && c->sc.env_cdf_cols && c->ctx.env))
         return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: fn 13 / 14 need a map uploaded to a context created with env_importance_sampling");
     HIPCHK(c, hipSetDevice(c->device));
     float tab[PT_FILTER_TAB + 1] = {};
@@ -533,27 +476,20 @@ extern "C" int prt_selftest_fn(prt_ctx* c, int fn, const float* params, const fl
         if (!filter_radius(kind, params[1], r) || kind == PRT_FILTER_NONE) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_selftest_fn: fn 12 needs a filter kind and radius");
         if (kind >= PRT_FILTER_GAUSSIAN) build_filter_table(kind, r, tab);
     }
-    float *dp = nullptr, *di = nullptr, *dout = nullptr;
+    DevBuf<float> dp, di, dout, dtab;
     const size_t bytes = (size_t)n * 32 * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dp), 80 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&di), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), bytes);
-    if (e == hipSuccess) e = hipMemcpy(dp, params, 80 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(di, in, bytes, hipMemcpyHostToDevice);
-    float* dtab = nullptr;
-    if (e == hipSuccess && fn == 12) e = hipMalloc(reinterpret_cast<void**>(&dtab), sizeof(tab));
-    if (e == hipSuccess && fn == 12) e = hipMemcpy(dtab, tab, sizeof(tab), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        if (fn == 12) launch_selftest_filter(kind, r, kind >= PRT_FILTER_GAUSSIAN ? dtab : nullptr, di, dout, n, c->stream);
-        else if (env_fn) launch_selftest_env(fn, c->sc.env, c->sc.env_w, c->sc.env_h, c->sc.env_cdf_rows, c->sc.env_cdf_cols, di, dout, n, c->stream);
-        else launch_selftest_fn(fn, dp, di, dout, n, c->stream);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (dtab) (void)hipFree(dtab);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-    if (dp) (void)hipFree(dp);
-    if (di) (void)hipFree(di);
-    if (dout) (void)hipFree(dout);
-    HIPCHK(c, e);
+    HIPCHK(c, dp.alloc(80));
+    HIPCHK(c, di.alloc((size_t)n * 32));
+    HIPCHK(c, dout.alloc((size_t)n * 32));
+    HIPCHK(c, hipMemcpy(dp, params, 80 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(di, in, bytes, hipMemcpyHostToDevice));
+    if (fn == 12) {
+        HIPCHK(c, dtab.alloc(PT_FILTER_TAB + 1));
+        HIPCHK(c, hipMemcpy(dtab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        launch_selftest_filter(kind, r, kind >= PRT_FILTER_GAUSSIAN ? dtab.get() : nullptr, di, dout, n, c->stream);
+    } else if (env_fn) launch_selftest_env(fn, c->sc.env, c->sc.env_w, c->sc.env_h, c->sc.env_cdf_rows, c->sc.env_cdf_cols, di, dout, n, c->stream);
+    else launch_selftest_fn(fn, dp, di, dout, n, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return PRT_OK;
 }

@@ -42,9 +42,9 @@ static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* w
     if (c->row0 != 0 || c->rows != c->full_height || c->n_parts != 1)
         return fail(c, PRT_ERR_UNSUPPORTED, w + ": the filter needs the whole frame (tile and row-block contexts are refused)");
     if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, w + ": a debug view is not a picture to filter");
-    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, w + ": no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (!c->frame.guides_valid) return fail(c, PRT_ERR_NOT_READY, w + ": no guides for this scene, camera, map and frame (prt_render_guides)");
     if (c->fresh) return fail(c, PRT_ERR_NOT_READY, w + ": nothing rendered since the reset");
-    const bool stats = c->stats_valid && c->d_adapt;
+    const bool stats = c->frame.stats_valid && c->frame.adapt;
     if (p.var_source == PRT_DENOISE_VAR_STATS && !stats)
         return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs the last render since the reset to be prt_render_adaptive");
     *spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL || (p.var_source == PRT_DENOISE_VAR_AUTO && !stats);
@@ -60,13 +60,11 @@ static int records_output(prt_ctx* c, const float4* out, int W, int H, void* dev
     if (rgba8) {
         FrameArgs fa = frame_args(c, 1, 0, nullptr, 0, false);
         fa.width = W; fa.full_height = H; fa.row0 = 0; fa.rows = H; fa.block_rows = 1; fa.n_parts = 1; fa.part = 0;
-        unsigned char* d = nullptr;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), npix * 4));
+        DevBuf<unsigned char> d;
+        HIPCHK(c, d.alloc(npix * 4));
         launch_tonemap(out, d, fa, c->stream);
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(rgba8, d, npix * 4, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        HIPCHK(c, e);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(rgba8, d, npix * 4, hipMemcpyDeviceToHost));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (rgba) HIPCHK(c, hipMemcpy(rgba, out, npix * 16, hipMemcpyDeviceToHost));
@@ -105,6 +103,20 @@ static int read_history_planes(prt_ctx* c, const History& h, size_t npix, float*
     return PRT_OK;
 }
 
+// the filter's buffers of the context's frame, on first use: two ping-pong planes and the output plane in dn, the Gaussian of v in dn_g
+static int filter_buffers(prt_ctx* c) {
+    HIPCHK(c, c->frame.dn.first_use(3 * c->npix));
+    HIPCHK(c, c->frame.dn_g.first_use(c->npix));
+    return PRT_OK;
+}
+// the two buffers of an npix-pixel history, on first use; anew: whatever it holds goes first (the record history at a new size)
+static int history_buffers(prt_ctx* c, History& h, size_t npix, bool anew) {
+    if (anew) h = History{};
+    HIPCHK(c, h.planes.first_use(4 * npix));
+    HIPCHK(c, h.guides.first_use(2 * npix));
+    return PRT_OK;
+}
+
 extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* rgba, uint8_t* rgba8) {
     CTX_CHECK(c);
     const prt_denoise_params p = params ? *params : default_denoise_params();
@@ -112,10 +124,9 @@ extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* 
     int rc = denoise_checks(c, p, "prt_denoise", &spatial);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
-    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
-    float4* out = c->d_dn + 2 * c->npix;
-    launch_denoise(c->fb, c->S.q4, c->d_adapt, spatial, c->d_guides, c->width, c->rows, p, c->d_dn, c->d_dn + c->npix, c->d_dn_g, out, c->stream);
+    if ((rc = filter_buffers(c))) return rc;
+    float4* out = c->frame.dn + 2 * c->npix;
+    launch_denoise(c->frame.fb, c->S.q4, c->frame.adapt, spatial, c->frame.guides, c->width, c->rows, p, c->frame.dn, c->frame.dn + c->npix, c->frame.dn_g, out, c->stream);
     HIPCHK(c, hipGetLastError());
     return records_output(c, out, c->width, c->rows, nullptr, rgba, rgba8);
 }
@@ -130,34 +141,30 @@ extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatia
     rc = denoise_checks(c, p, "prt_denoise_temporal", &spatial_var);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_dn) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn), c->npix * 3 * sizeof(float4)));
-    if (!c->d_dn_g) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_dn_g), c->npix * sizeof(float)));
-    // (a history without one of its buffers is empty: free_frame clears hist.valid, and only history_commit, which needs both, sets it)
-    if (!c->hist.planes) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->hist.planes), c->npix * 4 * sizeof(float4)));
-    if (!c->hist.guides) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->hist.guides), c->npix * 2 * sizeof(float4)));
-    const TemporalHistory h = history_begin(c->hist, c->npix);
-    float4* out = c->d_dn + 2 * c->npix;
+    if ((rc = filter_buffers(c)) || (rc = history_buffers(c, c->frame.hist, c->npix, false))) return rc;
+    const TemporalHistory h = history_begin(c->frame.hist, c->npix);
+    float4* out = c->frame.dn + 2 * c->npix;
     // the context's motion plane when motion is on and the plane is the valid guides' own (prt.h)
-    const float4* motion = (c->motion && c->motion_valid) ? c->d_motion : nullptr;
-    launch_denoise_temporal(c->fb, c->S.q4, c->d_adapt, spatial_var, c->d_guides, c->width, c->rows, p, t, c->cam, h, c->d_dn,
-                            c->d_dn + c->npix, c->d_dn_g, out, c->stream, motion);
+    const float4* motion = (c->motion && c->frame.motion_valid) ? c->frame.motion : nullptr;
+    launch_denoise_temporal(c->frame.fb, c->S.q4, c->frame.adapt, spatial_var, c->frame.guides, c->width, c->rows, p, t, c->cam, h, c->frame.dn,
+                            c->frame.dn + c->npix, c->frame.dn_g, out, c->stream, motion);
     HIPCHK(c, hipGetLastError());
-    if ((rc = history_commit(c, c->hist, c->d_guides, c->npix, c->cam))) return rc;
+    if ((rc = history_commit(c, c->frame.hist, c->frame.guides, c->npix, c->cam))) return rc;
     return records_output(c, out, c->width, c->rows, nullptr, rgba, rgba8);
 }
 
 extern "C" int prt_read_history(prt_ctx* c, float* out8) {
     CTX_CHECK(c);
     if (!out8 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_history: bad arguments");
-    if (!c->hist.valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_history: the history is empty (prt_denoise_temporal)");
+    if (!c->frame.hist.valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_history: the history is empty (prt_denoise_temporal)");
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    return read_history_planes(c, c->hist, c->npix, out8);
+    return read_history_planes(c, c->frame.hist, c->npix, out8);
 }
 
 extern "C" int prt_reset_history(prt_ctx* c) {
     CTX_CHECK(c);
-    c->hist.valid = false;
+    c->frame.hist.valid = false;
     return PRT_OK;
 }
 
@@ -168,11 +175,11 @@ extern "C" int prt_export_denoise_inputs(prt_ctx* c, void* device_records) {
         return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_export_denoise_inputs: bad arguments (a 16-byte aligned device pointer, a context with a frame size)");
     if (c->state_undefined) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: an earlier render call failed half-way; prt_reset or prt_write_state first");
     if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_export_denoise_inputs: a debug view is not a picture to filter");
-    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (!c->frame.guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: no guides for this scene, camera, map and frame (prt_render_guides)");
     if (c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: nothing rendered since the reset");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool stats = c->stats_valid && c->d_adapt;
-    launch_records_export(c->fb, c->S.q4, stats ? c->d_adapt : nullptr, c->d_guides, c->width, c->rows, static_cast<float4*>(device_records), c->stream);
+    const bool stats = c->frame.stats_valid && c->frame.adapt;
+    launch_records_export(c->frame.fb, c->S.q4, stats ? c->frame.adapt : nullptr, c->frame.guides, c->width, c->rows, static_cast<float4*>(device_records), c->stream);
     HIPCHK(c, hipGetLastError());
     // (prt_copy_framebuffer_to_device: on a caller's stream the records are ordered like the caller's other work; the context's own stream is
     // private: finish before returning)
@@ -188,13 +195,8 @@ static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params
         return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": needs width >= 1, height >= 1 and 16-byte aligned device pointers (records not null)");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = (size_t)W * (size_t)H;
-    if (c->rec_cap < npix) {
-        free_dev(c->d_rec);
-        c->rec_cap = 0;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_rec), npix * (6 * sizeof(float4) + sizeof(float)) + sizeof(unsigned)));
-        c->rec_cap = npix;
-    }
-    float4* fb = c->d_rec;
+    HIPCHK(c, c->ctx.rec.reserve(npix * (6 * sizeof(float4) + sizeof(float)) + sizeof(unsigned)));
+    float4* fb = reinterpret_cast<float4*>(c->ctx.rec.get());
     float4* guides = fb + npix;
     float4* buf0 = fb + 3 * npix;
     float4* buf1 = fb + 4 * npix;
@@ -226,15 +228,9 @@ static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params
         HIPCHK(c, hipGetLastError());
         return records_output(c, out, W, H, device_rgba, rgba, rgba8);
     }
-    History& rh = c->rec_hist;
-    if (!rh.planes || !rh.guides || c->rec_hist_w != W || c->rec_hist_h != H) {
-        rh.valid = false;
-        free_dev(rh.planes);
-        free_dev(rh.guides);
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&rh.planes), npix * 4 * sizeof(float4)));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&rh.guides), npix * 2 * sizeof(float4)));
-        c->rec_hist_w = W; c->rec_hist_h = H;
-    }
+    History& rh = c->ctx.rec_hist;
+    if (int rc = history_buffers(c, rh, npix, !rh.planes || !rh.guides || c->ctx.rec_hist_w != W || c->ctx.rec_hist_h != H)) return rc;
+    c->ctx.rec_hist_w = W; c->ctx.rec_hist_h = H;
     DevCamera dc;
     make_dev_camera(*cam, dc);
     const TemporalHistory h = history_begin(rh, npix);
@@ -274,18 +270,18 @@ extern "C" int prt_denoise_records_temporal(prt_ctx* c, const prt_denoise_params
 
 extern "C" int prt_reset_records_history(prt_ctx* c) {
     CTX_CHECK(c);
-    c->rec_hist.valid = false;
+    c->ctx.rec_hist.valid = false;
     return PRT_OK;
 }
 
 extern "C" int prt_read_records_history(prt_ctx* c, int width, int height, float* out8) {
     CTX_CHECK(c);
     if (!out8 || width < 1 || height < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: bad arguments");
-    if (!c->rec_hist.valid || !c->rec_hist.planes)
+    if (!c->ctx.rec_hist.valid || !c->ctx.rec_hist.planes)
         return fail(c, PRT_ERR_NOT_READY, "prt_read_records_history: the record history is empty (prt_denoise_records_temporal)");
-    if (width != c->rec_hist_w || height != c->rec_hist_h)
+    if (width != c->ctx.rec_hist_w || height != c->ctx.rec_hist_h)
         return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: the record history has another size");
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    return read_history_planes(c, c->rec_hist, (size_t)width * (size_t)height, out8);
+    return read_history_planes(c, c->ctx.rec_hist, (size_t)width * (size_t)height, out8);
 }

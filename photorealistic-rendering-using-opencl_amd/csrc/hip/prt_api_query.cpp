@@ -23,22 +23,10 @@ static int query_checks(prt_ctx* c, const char* who, bool need_frame, const void
 
 // slot_vtx on the device with the first query if no update has put it there (a scene without triangles needs none), then the launch
 static int cast_launch(prt_ctx* c, bool any_hit, const void* d_rays, uint32_t n, void* d_out) {
-    const uint32_t* slot_vtx = nullptr;
-    if (c->n_tris) {
+    if (c->scene.n_tris)
         if (int rc = refit_tables(c)) return rc;
-        slot_vtx = static_cast<const uint32_t*>(c->d_slot_vtx);
-    }
-    launch_cast(c->sc, any_hit, d_rays, n, slot_vtx, d_out, c->stream);
+    launch_cast(c->sc, any_hit, d_rays, n, c->scene.tree.slot_vtx, d_out, c->stream);
     HIPCHK(c, hipGetLastError());
-    return PRT_OK;
-}
-
-static int grow(prt_ctx* c, void*& buf, size_t& cap, size_t bytes) {
-    if (cap >= bytes) return PRT_OK;
-    free_dev(buf);
-    cap = 0;
-    HIPCHK(c, hipMalloc(&buf, bytes));
-    cap = bytes;
     return PRT_OK;
 }
 
@@ -58,13 +46,13 @@ static int cast_host(prt_ctx* c, const char* who, bool any_hit, const prt_ray* r
     if (nothing) return PRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t out_bytes = (size_t)n * (any_hit ? sizeof(uint32_t) : sizeof(prt_hit));
-    int rc;
-    if ((rc = grow(c, c->d_cast_rays, c->cast_rays_cap, (size_t)n * sizeof(prt_ray))) || (rc = grow(c, c->d_cast_out, c->cast_out_cap, out_bytes))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_cast_rays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, c->stream));
-    if ((rc = cast_launch(c, any_hit, c->d_cast_rays, n, c->d_cast_out))) return rc;
+    HIPCHK(c, c->ctx.cast_rays.reserve((size_t)n * sizeof(prt_ray)));
+    HIPCHK(c, c->ctx.cast_out.reserve(out_bytes));
+    HIPCHK(c, hipMemcpyAsync(c->ctx.cast_rays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, c->stream));
+    if (int rc = cast_launch(c, any_hit, c->ctx.cast_rays, n, c->ctx.cast_out)) return rc;
     // (into the caller's memory only once the launch has succeeded)
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->d_cast_out, out_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->ctx.cast_out, out_bytes, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -96,14 +84,14 @@ extern "C" int prt_cast_pixels(prt_ctx* c, const int32_t* xy, uint32_t n, prt_hi
     HIPCHK(c, hipSetDevice(c->device));
     // the staging buffer holds the n rays the generator writes and, behind them, the n (x, y) pairs it reads
     const size_t ray_bytes = (size_t)n * sizeof(prt_ray), xy_bytes = (size_t)n * 2 * sizeof(int32_t), out_bytes = (size_t)n * sizeof(prt_hit);
-    int rc;
-    if ((rc = grow(c, c->d_cast_rays, c->cast_rays_cap, ray_bytes + xy_bytes)) || (rc = grow(c, c->d_cast_out, c->cast_out_cap, out_bytes))) return rc;
-    int32_t* d_xy = reinterpret_cast<int32_t*>(static_cast<char*>(c->d_cast_rays) + ray_bytes);
+    HIPCHK(c, c->ctx.cast_rays.reserve(ray_bytes + xy_bytes));
+    HIPCHK(c, c->ctx.cast_out.reserve(out_bytes));
+    int32_t* d_xy = reinterpret_cast<int32_t*>(c->ctx.cast_rays + ray_bytes);
     HIPCHK(c, hipMemcpyAsync(d_xy, xy, xy_bytes, hipMemcpyHostToDevice, c->stream));
-    launch_cast_pixel_rays(c->cam, c->width, c->full_height, d_xy, n, c->d_cast_rays, c->stream);
+    launch_cast_pixel_rays(c->cam, c->width, c->full_height, d_xy, n, c->ctx.cast_rays, c->stream);
     HIPCHK(c, hipGetLastError());
-    if ((rc = cast_launch(c, false, c->d_cast_rays, n, c->d_cast_out))) return rc;
+    if (int rc = cast_launch(c, false, c->ctx.cast_rays, n, c->ctx.cast_out)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(hits, c->d_cast_out, out_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hits, c->ctx.cast_out, out_bytes, hipMemcpyDeviceToHost));
     return PRT_OK;
 }

@@ -10,13 +10,8 @@
 
 static int ensure_seeds(prt_ctx* c, const int32_t* seed_pairs, size_t n_frames) {
     if (!n_frames) return PRT_OK;
-    if (c->seeds_cap < n_frames) {
-        free_dev(c->d_seeds);
-        c->seeds_cap = 0;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_seeds), n_frames * 2 * sizeof(int32_t)));
-        c->seeds_cap = n_frames;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_seeds, seed_pairs, n_frames * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->ctx.seeds.reserve(2 * n_frames));
+    HIPCHK(c, hipMemcpyAsync(c->ctx.seeds, seed_pairs, n_frames * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // caller may free seed_pairs on return
     return PRT_OK;
 }
@@ -25,9 +20,9 @@ static int ensure_seeds(prt_ctx* c, const int32_t* seed_pairs, size_t n_frames) 
 // `stream`, which must be idle -- every caller has just waited for the one launch that was in flight on it); 0 if nothing has been rendered yet
 static float inverse_mean_path_length(prt_ctx* c, uint32_t spp, hipStream_t stream) {
     unsigned long long h[3] = {0, 0, 0};
-    if (hipMemsetAsync(c->d_counters + 1, 0, 3 * sizeof(unsigned long long), stream) != hipSuccess) return 0.0f;
-    launch_count(c->S, c->npix, spp, c->d_counters + 1, stream);
-    if (hipMemcpyAsync(h, c->d_counters + 1, sizeof(h), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return 0.0f;
+    if (hipMemsetAsync(c->ctx.counters + 1, 0, 3 * sizeof(unsigned long long), stream) != hipSuccess) return 0.0f;
+    launch_count(c->S, c->npix, spp, c->ctx.counters + 1, stream);
+    if (hipMemcpyAsync(h, c->ctx.counters + 1, sizeof(h), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return 0.0f;
     // (the reference IS the mean: 0.9 / 1.15 / 1.3 / 1.5 / 2 x the mean were all slower)
     return (h[0] && h[1]) ? (float)((double)h[0] / (double)h[1]) : 0.0f;
 }
@@ -78,10 +73,10 @@ struct Run {
     // streams start behind everything already queued on the caller's stream
     int fork(bool zero) {
         c->fresh = false;
-        c->stats_valid = false;
+        c->frame.stats_valid = false;
         c->stats.concurrent = (uint32_t)K;
         HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        if (zero) HIPCHK(c, hipMemsetAsync(c->d_counters + 4, 0, 2 * prt_ctx::MAX_SUB * sizeof(unsigned long long), c->stream));
+        if (zero) HIPCHK(c, hipMemsetAsync(c->ctx.counters + 4, 0, 2 * prt_ctx::MAX_SUB * sizeof(unsigned long long), c->stream));
         if (K > 1) HIPCHK(c, hipEventRecord(c->fork_ev, c->stream));
         for (int j = 0; j < K && K > 1; ++j) HIPCHK(c, hipStreamWaitEvent(c->sub_stream[j], c->fork_ev, 0));
         return PRT_OK;
@@ -90,7 +85,7 @@ struct Run {
     // must not run ahead of them and the context must stay usable
     int abort(int code, const std::string& msg) {
         for (int j = 0; j < K; ++j) (void)hipStreamSynchronize(stream_of(j));
-        (void)hipMemsetAsync(c->d_counters + 4, 0, 2 * prt_ctx::MAX_SUB * sizeof(unsigned long long), c->stream);
+        (void)hipMemsetAsync(c->ctx.counters + 4, 0, 2 * prt_ctx::MAX_SUB * sizeof(unsigned long long), c->stream);
         (void)hipStreamSynchronize(c->stream);
         (void)hipGetLastError();
         c->state_undefined = true;
@@ -100,7 +95,7 @@ struct Run {
     // the launch that takes the frames behind f: at most `step` of them (n), with the seeds of all that are left (run-ahead)
     FrameArgs window(uint32_t f, uint32_t& n) const {
         n = (max_frames - f < step) ? max_frames - f : step;
-        FrameArgs fa = frame_args(c, 1 + f, n, c->d_seeds + 2 * (size_t)f, spp, true);
+        FrameArgs fa = frame_args(c, 1 + f, n, c->ctx.seeds + 2 * (size_t)f, spp, true);
         fa.seed_frames = max_frames - f; fa.run_ahead = c->run_ahead;
         fa.pace_inv_ref = pacing ? pace_inv_ref : 0.0f;
         return fa;
@@ -109,11 +104,11 @@ struct Run {
     // device counters, so there is no copy or fill kernel between launches (with the other stream's kernel filling the chip those waited
     // ~1.7 ms for a wave slot) and the HIP events around a launch time the kernel alone
     int launch_part(int j, FrameArgs fa) {
-        fa.unfinished = c->d_counters + 4 + 2 * j;
+        fa.unfinished = c->ctx.counters + 4 + 2 * j;
         fa.unfinished_host = c->h_unfinished + (c->test_drop_report ? prt_ctx::MAX_SUB : j);      // (tests: the report goes astray)
         c->h_unfinished[j] = ~0ull;
         if (K > 1) SUBCHK(*this, hipEventRecord(c->sub_ev0[j], stream_of(j)));
-        c->last = c->last_sub[j] = launch_render(c->sc, c->cam, c->S, fa, c->fb, stream_of(j), c->lo);
+        c->last = c->last_sub[j] = launch_render(c->sc, c->cam, c->S, fa, c->frame.fb, stream_of(j), c->lo);
         if (K > 1) SUBCHK(*this, hipEventRecord(c->sub_ev[j], stream_of(j)));
         ++c->stats.launches;
         return PRT_OK;
@@ -159,9 +154,9 @@ extern "C" int prt_render_frames(prt_ctx* c, uint32_t first_frame, uint32_t n_fr
     for (uint32_t f = 0; f < n_frames; f += run.step) {
         const uint32_t n = (n_frames - f < run.step) ? n_frames - f : run.step;
         for (int j = 0; j < K; ++j) {
-            FrameArgs fa = frame_args(c, first_frame + f, n, c->d_seeds + 2 * (size_t)f, 0, false);
+            FrameArgs fa = frame_args(c, first_frame + f, n, c->ctx.seeds + 2 * (size_t)f, 0, false);
             fa.tile_first = (uint32_t)j; fa.tile_stride = (uint32_t)K;
-            c->last = launch_render(c->sc, c->cam, c->S, fa, c->fb, run.stream_of(j), c->lo);
+            c->last = launch_render(c->sc, c->cam, c->S, fa, c->frame.fb, run.stream_of(j), c->lo);
             ++c->stats.launches;
         }
     }
@@ -183,12 +178,12 @@ extern "C" int prt_render_spp(prt_ctx* c, uint32_t spp, uint32_t max_frames, con
         unsigned long long unfinished = 1;
         while (f < max_frames && unfinished) {
             uint32_t n;
-            HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long), c->stream));
+            HIPCHK(c, hipMemsetAsync(c->ctx.counters, 0, sizeof(unsigned long long), c->stream));
             const FrameArgs fa = run.window(f, n);
-            c->last = launch_render(c->sc, c->cam, c->S, fa, c->fb, c->stream, c->lo);
+            c->last = launch_render(c->sc, c->cam, c->S, fa, c->frame.fb, c->stream, c->lo);
             ++c->stats.launches;
             f += n;
-            HIPCHK(c, hipMemcpyAsync(&unfinished, c->d_counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&unfinished, c->ctx.counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (run.pacing && run.pace_inv_ref == 0.0f && unfinished) run.pace_inv_ref = inverse_mean_path_length(c, spp, c->stream);
         }
@@ -211,12 +206,12 @@ extern "C" int prt_render_spp(prt_ctx* c, uint32_t spp, uint32_t max_frames, con
                     uint32_t n;
                     FrameArgs fa = run.window(fj[j], n);
                     fa.tile_first = (uint32_t)j; fa.tile_stride = (uint32_t)K;
-                    if (sorting && c->d_tile_cost[j]) {
-                        fa.tile_order = c->have_order[j] ? c->d_tile_order[j] : nullptr;
-                        fa.tile_cost = (!c->have_order[j] && retired[j] == 0u) ? c->d_tile_cost[j] : nullptr;
+                    if (sorting && c->frame.tile_cost[j]) {
+                        fa.tile_order = c->frame.have_order[j] ? c->frame.tile_order[j] : nullptr;
+                        fa.tile_cost = (!c->frame.have_order[j] && retired[j] == 0u) ? c->frame.tile_cost[j] : nullptr;
                     }
                     // (a tile's cost is the maximum over its waves -- atomicMax in the kernel: the measuring launch starts from zero)
-                    if (fa.tile_cost) SUBCHK(run, hipMemsetAsync(c->d_tile_cost[j], 0, (size_t)n_tiles * sizeof(uint32_t), c->sub_stream[j]));
+                    if (fa.tile_cost) SUBCHK(run, hipMemsetAsync(c->frame.tile_cost[j], 0, (size_t)n_tiles * sizeof(uint32_t), c->sub_stream[j]));
                     if ((rc = run.launch_part(j, fa))) return rc;
                     fj[j] += n;
                     in_flight[j] = true;
@@ -231,18 +226,18 @@ extern "C" int prt_render_spp(prt_ctx* c, uint32_t spp, uint32_t max_frames, con
                     if (c->launch_log) std::snprintf(tag, sizeof(tag), "launch: part %d #%u", j, retired[j]);
                     unsigned long long left;
                     if ((rc = run.retire_part(j, left, tag))) return rc;
-                    if (sorting && c->d_tile_cost[j] && !c->have_order[j] && retired[j] == 0u && !c->last_sub[j].scatter && n_tiles > (unsigned)j) {
+                    if (sorting && c->frame.tile_cost[j] && !c->frame.have_order[j] && retired[j] == 0u && !c->last_sub[j].scatter && n_tiles > (unsigned)j) {
                         // launch 0 of this sub-part is over and its stream idle: its tiles by run time, longest first, for every launch from here on
                         const unsigned grid = (n_tiles - (unsigned)j + (unsigned)K - 1u) / (unsigned)K;
                         c->h_tile_cost.resize(grid); c->h_tile_order.resize(grid);
-                        SUBCHK(run, hipMemcpyAsync(c->h_tile_cost.data(), c->d_tile_cost[j], grid * sizeof(uint32_t), hipMemcpyDeviceToHost, c->sub_stream[j]));
+                        SUBCHK(run, hipMemcpyAsync(c->h_tile_cost.data(), c->frame.tile_cost[j], grid * sizeof(uint32_t), hipMemcpyDeviceToHost, c->sub_stream[j]));
                         SUBCHK(run, hipStreamSynchronize(c->sub_stream[j]));
                         for (unsigned k = 0; k < grid; ++k) c->h_tile_order[k] = k;
                         const uint32_t* cost = c->h_tile_cost.data();
                         std::stable_sort(c->h_tile_order.begin(), c->h_tile_order.end(), [cost](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-                        SUBCHK(run, hipMemcpyAsync(c->d_tile_order[j], c->h_tile_order.data(), grid * sizeof(uint32_t), hipMemcpyHostToDevice, c->sub_stream[j]));
+                        SUBCHK(run, hipMemcpyAsync(c->frame.tile_order[j], c->h_tile_order.data(), grid * sizeof(uint32_t), hipMemcpyHostToDevice, c->sub_stream[j]));
                         SUBCHK(run, hipStreamSynchronize(c->sub_stream[j]));      // (the host vector is reused by the other sub-part)
-                        c->have_order[j] = true;
+                        c->frame.have_order[j] = true;
                     }
                     // the frame's mean path length, once per render (this sub-part's stream is idle: its launch has just retired)
                     if (run.pacing && run.pace_inv_ref == 0.0f && left) run.pace_inv_ref = inverse_mean_path_length(c, spp, c->sub_stream[j]);
@@ -282,14 +277,14 @@ extern "C" int prt_render_adaptive(prt_ctx* c, const prt_adaptive* a, uint32_t m
     Run run{c, "prt_render_adaptive", a->max_spp, max_frames};
     if ((rc = run.begin(seed_pairs, 8ull * a->max_spp))) return rc;
     const unsigned n_waves = (unsigned)((c->npix + 63) / 64);
-    if (!c->d_adapt) {
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_adapt), c->npix * sizeof(float2)));
-        HIPCHK(c, hipMemsetAsync(c->d_adapt, 0, c->npix * sizeof(float2), c->stream));
+    if (!c->frame.adapt) {
+        HIPCHK(c, c->frame.adapt.alloc(c->npix));
+        HIPCHK(c, hipMemsetAsync(c->frame.adapt, 0, c->npix * sizeof(float2), c->stream));
     }
-    if (!c->d_live) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_live), c->npix * sizeof(uint32_t)));
-    if (!c->d_live_aux) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_live_aux), (n_waves + 1) * sizeof(uint32_t)));
+    HIPCHK(c, c->frame.live.first_use(c->npix));
+    HIPCHK(c, c->frame.live_aux.first_use(n_waves + 1));
     if ((rc = run.fork(true))) return rc;
-    c->stats_valid = true;                       // (prt_denoise PRT_DENOISE_VAR_STATS)
+    c->frame.stats_valid = true;                       // (prt_denoise PRT_DENOISE_VAR_STATS)
     const int K = run.K;
     const unsigned n_tiles = render_tile_count(c->width, c->rows);
     bool done[prt_ctx::MAX_SUB] = {false, false, false, false};     // tile rounds: every pixel of the sub-part's tiles is frozen
@@ -301,9 +296,9 @@ extern "C" int prt_render_adaptive(prt_ctx* c, const prt_adaptive* a, uint32_t m
     while (f < max_frames && live) {
         if (c->compact && live * 100ull < (unsigned long long)c->npix * (unsigned)c->compact_below && (!list_mode || 2ull * live < list_count)) {
             // (every stream is idle: the last round has been waited for)
-            launch_live_list(c->S, c->npix, a->max_spp, c->d_live_aux, c->d_live, c->d_live_aux + n_waves, c->stream);
+            launch_live_list(c->S, c->npix, a->max_spp, c->frame.live_aux, c->frame.live, c->frame.live_aux + n_waves, c->stream);
             uint32_t cnt = 0;
-            SUBCHK(run, hipMemcpyAsync(&cnt, c->d_live_aux + n_waves, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+            SUBCHK(run, hipMemcpyAsync(&cnt, c->frame.live_aux + n_waves, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
             SUBCHK(run, hipStreamSynchronize(c->stream));
             if (cnt != live) return run.abort(PRT_ERR_HIP, "prt_render_adaptive: the live-pixel list disagrees with the launches' reports");
             list_count = cnt; list_mode = true;
@@ -314,11 +309,11 @@ extern "C" int prt_render_adaptive(prt_ctx* c, const prt_adaptive* a, uint32_t m
         uint32_t n = 0;
         for (int j = 0; j < K; ++j) {
             FrameArgs fa = run.window(f, n);
-            fa.adapt = c->d_adapt; fa.min_spp = a->min_spp; fa.rel_err = a->rel_err; fa.abs_floor = a->abs_floor;
+            fa.adapt = c->frame.adapt; fa.min_spp = a->min_spp; fa.rel_err = a->rel_err; fa.abs_floor = a->abs_floor;
             if (list_mode) {
                 const uint32_t start = (uint32_t)j * chunk;
                 if (start >= list_count) continue;
-                fa.live = c->d_live + start;
+                fa.live = c->frame.live + start;
                 fa.live_count = std::min(chunk, list_count - start);
                 c->arep.list_lanes += 64ull * ((fa.live_count + 63u) / 64u);
                 ++c->arep.list_launches;
@@ -355,8 +350,8 @@ extern "C" int prt_read_adaptive_stats(prt_ctx* c, float* out2) {
     if (!out2 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_adaptive_stats: bad arguments");
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    if (!c->d_adapt) { std::memset(out2, 0, c->npix * 2 * sizeof(float)); return PRT_OK; }    // (no adaptive render since the frame was made)
-    HIPCHK(c, hipMemcpy(out2, c->d_adapt, c->npix * sizeof(float2), hipMemcpyDeviceToHost));
+    if (!c->frame.adapt) { std::memset(out2, 0, c->npix * 2 * sizeof(float)); return PRT_OK; }    // (no adaptive render since the frame was made)
+    HIPCHK(c, hipMemcpy(out2, c->frame.adapt, c->npix * sizeof(float2), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -373,31 +368,31 @@ extern "C" int prt_render_guides(prt_ctx* c, uint32_t samples) {
     if (rc) return rc;
     if (samples < 1 || samples > 64) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_render_guides: samples must be 1 .. 64");
     HIPCHK(c, hipSetDevice(c->device));
-    c->guides_valid = false;
-    c->motion_valid = false;
-    if (!c->d_guides) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_guides), c->npix * 2 * sizeof(float4)));
-    if (c->motion && !c->d_motion) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_motion), c->npix * sizeof(float4)));
-    const bool snap = c->motion && c->snap_valid && c->d_tri_prev;
+    c->frame.guides_valid = false;
+    c->frame.motion_valid = false;
+    HIPCHK(c, c->frame.guides.first_use(2 * c->npix));
+    if (c->motion) HIPCHK(c, c->frame.motion.first_use(c->npix));
+    const bool snap = c->motion && c->scene.snap.snap_valid && c->scene.snap.tri_prev;
     // the motion instances only where there is a snapshot to measure from; no update since the last guide render: the plain kernels and a
     // plane of zeros
     // ... and the primitive-motion instances only while a primitive snapshot is pending (prt_update_primitives), with the triangle term only
     // while a triangle snapshot is pending too: the two snapshots are independent of each other
-    const bool prim_snap = c->motion && c->prim_snap_valid && c->d_spheres_prev && c->d_sdfs_prev && c->d_quads_prev;
+    const bool prim_snap = c->motion && c->scene.snap.prim_snap_valid && c->scene.snap.spheres_prev && c->scene.snap.sdfs_prev && c->scene.snap.quads_prev;
     if (prim_snap) {
-        const PrimPrev prims{static_cast<const DevSphere*>(c->d_spheres_prev), static_cast<const DevSdf*>(c->d_sdfs_prev), static_cast<const DevQuad*>(c->d_quads_prev)};
-        launch_guides_prim_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides,
-                                  snap ? static_cast<const TriGeom*>(c->d_tri_prev) : nullptr, prims, c->d_motion, c->stream);
-    } else if (snap) launch_guides_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides,
-                                   static_cast<const TriGeom*>(c->d_tri_prev), c->d_motion, c->stream);
-    else launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->d_guides, c->stream);
+        const PrimPrev prims{c->scene.snap.spheres_prev, c->scene.snap.sdfs_prev, c->scene.snap.quads_prev};
+        launch_guides_prim_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides,
+                                  snap ? c->scene.snap.tri_prev.get() : nullptr, prims, c->frame.motion, c->stream);
+    } else if (snap) launch_guides_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides, c->scene.snap.tri_prev,
+                                          c->frame.motion, c->stream);
+    else launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides, c->stream);
     HIPCHK(c, hipGetLastError());
-    if (c->motion && !snap && !prim_snap) HIPCHK(c, hipMemsetAsync(c->d_motion, 0, c->npix * sizeof(float4), c->stream));
+    if (c->motion && !snap && !prim_snap) HIPCHK(c, hipMemsetAsync(c->frame.motion, 0, c->npix * sizeof(float4), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->guides_valid = true;
+    c->frame.guides_valid = true;
     if (c->motion) {
-        c->snap_valid = false;                         // consumed: the next plane is measured from the geometry these guides saw
-        c->prim_snap_valid = false;
-        c->motion_valid = true;
+        c->scene.snap.snap_valid = false;                         // consumed: the next plane is measured from the geometry these guides saw
+        c->scene.snap.prim_snap_valid = false;
+        c->frame.motion_valid = true;
     }
     return PRT_OK;
 }
@@ -405,7 +400,7 @@ extern "C" int prt_render_guides(prt_ctx* c, uint32_t samples) {
 static int motion_ready(prt_ctx* c, const char* who) {
     const std::string w(who);
     if (!c->motion) return fail(c, PRT_ERR_NOT_READY, w + ": motion is off (prt_set_motion)");
-    if (!c->guides_valid || !c->motion_valid || !c->d_motion)
+    if (!c->frame.guides_valid || !c->frame.motion_valid || !c->frame.motion)
         return fail(c, PRT_ERR_NOT_READY, w + ": no guides with a motion plane for this scene, camera, map and frame (prt_render_guides)");
     return PRT_OK;
 }
@@ -416,7 +411,7 @@ extern "C" int prt_read_motion(prt_ctx* c, float* out4) {
     int rc = motion_ready(c, "prt_read_motion");
     if (rc) return rc;
     if ((rc = prt_synchronize(c))) return rc;
-    HIPCHK(c, hipMemcpy(out4, c->d_motion, c->npix * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out4, c->frame.motion, c->npix * sizeof(float4), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -427,7 +422,7 @@ extern "C" int prt_export_motion(prt_ctx* c, void* device_motion) {
     int rc = motion_ready(c, "prt_export_motion");
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(device_motion, c->d_motion, c->npix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(device_motion, c->frame.motion, c->npix * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     if (c->stream == c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));       // (as prt_export_denoise_inputs)
     return PRT_OK;
 }
@@ -435,9 +430,9 @@ extern "C" int prt_export_motion(prt_ctx* c, void* device_motion) {
 extern "C" int prt_read_guides(prt_ctx* c, float* out8) {
     CTX_CHECK(c);
     if (!out8 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_guides: bad arguments");
-    if (!c->guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_guides: no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (!c->frame.guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_guides: no guides for this scene, camera, map and frame (prt_render_guides)");
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpy(out8, c->d_guides, c->npix * 2 * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out8, c->frame.guides, c->npix * 2 * sizeof(float4), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
