@@ -765,6 +765,63 @@ int prt_occluded(prt_ctx* ctx, const prt_ray* rays, uint32_t n, uint32_t* out); 
 int prt_occluded_device(prt_ctx* ctx, const void* d_rays, uint32_t n, void* d_out);
 int prt_cast_pixels(prt_ctx* ctx, const int32_t* xy, uint32_t n, prt_hit* hits);                  /* n (x, y) pairs, full-frame coordinates */
 
+/* Deforming geometry: the mesh POSED on the device from per-frame bone matrices -- linear blend skinning (no counterpart in the reference).
+ * What an animated mesh changes per frame is a handful of 3x4 matrices: the caller gives the rest pose and the per-corner influences once
+ * and from then on a few KB per frame; the library poses the 3T vertices (and normals) with one streaming kernel into buffers of the
+ * context and hands them to the refit or the rebuild it already has.  A rigid part -- a door, a wheel, one group of an OBJ -- is a corner
+ * with weights {1, 0, 0, 0}.  Opt-in: without these calls every bit of every result is what it was.
+ * Corner c = 3i + k is vertex k of triangle i of prt_scene_desc::vertices.  Per corner: four bone indices b_0 .. b_3 (uint16) and four
+ * weights w_0 .. w_3 (float).  A bone matrix M[b] is 12 floats, row-major 3x4: rows {m00 m01 m02 m03}, {m10 ..}, {m20 ..}.
+ * The pose, all f32, no contraction; sqrtf and / correctly rounded.  Per corner with rest position (x, y, z), rest normal (nx, ny, nz), the
+ * influences k = 0 .. 3 in that order:
+ *       A_ij = +0                                               i = 0 .. 2, j = 0 .. 3
+ *       for each k with w_k != 0:   A_ij = A_ij + w_k * M[b_k]_ij
+ *     (a weight of +0 or -0 skips the influence, and its matrix is not read: it may hold NaN.  A rigid part costs one matrix.  A corner
+ *     whose four weights are all zero goes to the origin.  Weights need not sum to 1 and may be negative.)
+ *       p'.x = ((A00*x + A01*y) + A02*z) + A03;   p'.y and p'.z likewise with rows 1 and 2;   lane 3 = 0
+ *       n'.x = (A00*nx + A01*ny) + A02*nz;        n'.y and n'.z likewise
+ *       L = sqrtf((n'.x*n'.x + n'.y*n'.y) + n'.z*n'.z);     normal = L > 0 ? n' / L (per component) : n';     lane 3 = 0
+ *     The normal is exact for blends of rotations with uniform scale and an approximation otherwise (the inverse transpose is out of scope:
+ *     under a shear or a non-uniform scale regenerate the normals with prt_set_smooth_normals instead).  NaN and overflow go through the
+ *     formulas as they stand.
+ * The posed arrays go into buffers of the context, and the call proceeds EXACTLY as if those buffers had been passed to
+ * prt_update_vertices_device (PRT_POSE_REFIT) or to prt_rebuild_bvh_device (PRT_POSE_REBUILD, max_leaf as there): its finite-vertex check
+ * runs on the posed vertices -- a NaN or overflowing matrix under a non-zero weight is refused there, the scene untouched --, and the motion
+ * snapshot rule, the guides going stale, the forgotten tile orders and what is kept are that path's.  With prt_set_smooth_normals on, or
+ * with a skin without rest normals, normals == NULL is passed on: normals are then regenerated, kept or carried as that path defines.
+ * Deterministic: no dependence between lanes, no atomics; tile, row-block and rank contexts that each set the same skin and pose stay
+ * bit-identical in union to one whole-frame context.  The loop per displayed frame: pose, prt_reset, render, prt_render_guides,
+ * prt_denoise_temporal.
+ * prt_set_skin: checks and copies everything to the device and allocates the posed buffers and the matrix table (a pose cannot fail on an
+ *   allocation after the scene has been touched).  Device memory per triangle: 48 bytes of rest vertices, 24 of indices, 48 of weights and
+ *   48 of posed vertices -- 168 bytes --, with rest normals 48 + 48 more: 264 bytes; plus 48 bytes per bone.  Needs an uploaded scene with
+ *   T > 0, else PRT_ERR_NOT_READY.  Refused with PRT_ERR_INVALID_ARGUMENT, each leaving the previous skin in force: a null rest_vertices,
+ *   bone_index or bone_weight; n_bones outside 1 .. 65536; an index >= n_bones, even under a zero weight; a weight that is not finite; a
+ *   rest x, y, z or normal component that is not finite (lane 3 is not looked at).  PRT_ERR_UNSUPPORTED for T > PRT_MAX_TRIANGLE_SLOTS.
+ *   skin == NULL turns the feature off and frees the buffers.  Setting it changes no bit of the scene by itself.  It survives what the
+ *   smoothing topology survives: prt_reset, prt_resize, tile and row-block calls, camera changes, updates, rebuilds and poses;
+ *   prt_upload_scene turns it off (T may have changed).
+ * prt_pose / prt_pose_device: `matrices` is n_bones x 12 floats -- host memory (copied to the context's table on its stream), or device
+ *   memory of the context's device, 16-byte aligned.  Ordered on the context's stream and complete on return (the caller's matrices may be
+ *   reused then).  PRT_ERR_NOT_READY without a skin; PRT_ERR_INVALID_ARGUMENT for null or misaligned matrices or an unknown mode; otherwise
+ *   the refusals of the path it enters, each leaving the scene and a pending snapshot exactly as they were.
+ * prt_read_posed: the posed buffers of the last pose, accepted or refused by its path: float4[3T] each.  PRT_ERR_NOT_READY before the first
+ *   pose of the skin in force; PRT_ERR_INVALID_ARGUMENT for null `vertices`, or for non-null `normals` with a skin without rest normals. */
+typedef struct prt_skin {
+    const float*    rest_vertices;  /* float4[3T], layout of prt_scene_desc::vertices, xyz used */
+    const float*    rest_normals;   /* float4[3T] or NULL */
+    const uint16_t* bone_index;     /* 4 per corner */
+    const float*    bone_weight;    /* 4 per corner */
+    uint32_t        n_bones;        /* 1 .. 65536 */
+    uint32_t        _pad;
+} prt_skin;
+#define PRT_POSE_REFIT   0u   /* then prt_update_vertices_device's path */
+#define PRT_POSE_REBUILD 1u   /* then prt_rebuild_bvh_device's path, max_leaf as there */
+int prt_set_skin(prt_ctx* ctx, const prt_skin* skin /* NULL = off, frees the buffers */);
+int prt_pose(prt_ctx* ctx, const float* matrices /* n_bones x 12, host */, uint32_t mode, uint32_t max_leaf);
+int prt_pose_device(prt_ctx* ctx, const void* d_matrices /* 16-byte aligned */, uint32_t mode, uint32_t max_leaf);
+int prt_read_posed(prt_ctx* ctx, float* vertices /* float4[3T] */, float* normals /* float4[3T], may be NULL */);
+
 /* What this library was built from (no counterpart in the reference): a hash of the content of every source, header and compiler flag
  * of libprt.so, compiled in by the build (photorealistic-rendering-using-opencl_amd/build.py source_build_id(); a development variant of
  * tools/build_variant.sh reads "variant-<name>-<hash>").  bench.py prints it as `build_id` and refuses to time a library whose id is

@@ -327,6 +327,7 @@ class Renderer:
         self.triangle_count = int(desc.triangle_count)
         self.mesh_count = int(desc.object_count[7])
         self.bvh_node_count = int(desc.bvh_node_count) if desc.triangle_count else 0
+        self._skin = None                                  # (the library turns the skin off: T may have changed)
 
     def update_vertices(self, vertices, normals=None):
         """prt_update_vertices / prt_update_vertices_device: new vertices (and normals; None keeps the uploaded ones) for the uploaded scene,
@@ -429,6 +430,56 @@ class Renderer:
         out = np.zeros((3 * getattr(self, "triangle_count", 0), 4), dtype=np.float32)
         self._chk(self.lib.prt_read_normals(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_normals")
         return out
+
+    def set_skin(self, rest_vertices, rest_normals=None, bone_index=None, bone_weight=None, n_bones=0):
+        """prt_set_skin: the rest pose (float32 [3T, 4]; rest_normals None = no normals are posed) and the influences of every corner
+        (bone_index uint16 [3T, 4], bone_weight float32 [3T, 4]) of the uploaded mesh, n_bones 1 .. 65536.  From then on pose() moves the
+        mesh from n_bones 3x4 matrices (prt.h).  rest_vertices None turns it off"""
+        if rest_vertices is None:
+            self._chk(self.lib.prt_set_skin(self.ctx, None), "prt_set_skin")
+            self._skin = None
+            return
+        corners = 3 * getattr(self, "triangle_count", 0)
+        v = np.ascontiguousarray(rest_vertices, dtype=np.float32)
+        n = None if rest_normals is None else np.ascontiguousarray(rest_normals, dtype=np.float32)
+        b = None if bone_index is None else np.ascontiguousarray(bone_index, dtype=np.uint16)
+        w = None if bone_weight is None else np.ascontiguousarray(bone_weight, dtype=np.float32)
+        if any(a is not None and a.size < 4 * corners for a in (v, n, b, w)):
+            raise ValueError("set_skin: needs arrays of at least %d elements" % (4 * corners))
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        skin = _capi.Skin(ptr(v), ptr(n), ptr(b), ptr(w), int(n_bones), 0)
+        self._chk(self.lib.prt_set_skin(self.ctx, C.byref(skin)), "prt_set_skin")
+        self._skin = (int(n_bones), n is not None)
+
+    def pose(self, matrices, rebuild=False, max_leaf=0):
+        """prt_pose / prt_pose_device: the mesh posed on the device from n_bones 3x4 row-major matrices (float32 [n_bones, 12] or [n_bones, 3, 4]),
+        then refitted (rebuild False) or rebuilt (rebuild True, max_leaf as rebuild_bvh).  A numpy array takes the host door; a torch tensor
+        on this context's device (work queued on torch's current stream is waited for) or a device address the device door"""
+        mode = _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
+        floats = 12 * (self._skin[0] if getattr(self, "_skin", None) else 0)
+        if isinstance(matrices, np.ndarray) or matrices is None:
+            m = None if matrices is None else np.ascontiguousarray(matrices, dtype=np.float32)
+            if m is not None and m.size < floats:
+                raise ValueError("pose: needs a float32 array of at least %d elements" % floats)
+            self._chk(self.lib.prt_pose(self.ctx, None if m is None else m.ctypes.data_as(C.c_void_p), mode, int(max_leaf)), "prt_pose")
+        else:
+            if hasattr(matrices, "data_ptr"):
+                import torch
+                torch.cuda.current_stream(matrices.device).synchronize()
+            self._chk(self.lib.prt_pose_device(self.ctx, self._device_ptr(matrices, floats, "pose"), mode, int(max_leaf)), "prt_pose_device")
+        if mode == _capi.POSE_REBUILD:
+            count = C.c_uint32(0)
+            self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
+            self.bvh_node_count = int(count.value)
+
+    def read_posed(self):
+        """prt_read_posed: (vertices, normals) float32 [3T, 4] of the last pose, accepted or refused; normals None for a skin without rest normals"""
+        corners = 3 * getattr(self, "triangle_count", 0)
+        with_normals = bool(getattr(self, "_skin", None) and self._skin[1])
+        v = np.zeros((corners, 4), dtype=np.float32)
+        n = np.zeros((corners, 4), dtype=np.float32) if with_normals else None
+        self._chk(self.lib.prt_read_posed(self.ctx, v.ctypes.data_as(C.c_void_p), None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_read_posed")
+        return v, n
 
     def read_bvh(self):
         """prt_read_bvh: (nodes [node_count] of _capi.BVH_NODE_DTYPE, primitive_indices uint64 [T]): the current tree in the reference's layout,

@@ -117,6 +117,14 @@ HIT_MISS, HIT_TRIANGLE = -2, -1
 NORMALS_WEIGHTINGS = {"unit": 0, "area": 1}
 LOADER_CREASE_COS = -0.99619470
 
+# prt_set_skin / prt_pose: prt_skin and the modes (PRT_POSE_* of include/prt.h)
+class Skin(C.Structure):
+    _fields_ = [("rest_vertices", C.c_void_p), ("rest_normals", C.c_void_p), ("bone_index", C.c_void_p), ("bone_weight", C.c_void_p),
+                ("n_bones", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+POSE_REFIT, POSE_REBUILD = 0, 1
+
 # (name, restype, argtypes) of every symbol include/prt.h declares
 PRT_API = [
     ("prt_create", C.c_int, [C.c_int, C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -138,6 +146,10 @@ PRT_API = [
     ("prt_weld_corners", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("prt_set_smooth_normals", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]),
     ("prt_read_normals", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("prt_set_skin", C.c_int, [C.c_void_p, C.POINTER(Skin)]),
+    ("prt_pose", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("prt_pose_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("prt_read_posed", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_set_camera", C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     ("prt_upload_envmap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("prt_resize", C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -1,5 +1,5 @@
 // prt_api_scene.cpp -- the scene calls of the C ABI (include/prt.h): upload, vertex updates with a refit, rebuilds, the tree's read-backs,
-// motion on / off, smooth normals.
+// motion on / off, smooth normals, the skin and its poses.
 #include <cmath>
 #include <new>
 #include <utility>
@@ -8,6 +8,7 @@
 #include "pt_build.h"
 #include "pt_normals.h"
 #include "pt_pack.h"
+#include "pt_pose.h"
 #include "pt_refit.h"
 
 extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
@@ -479,6 +480,99 @@ extern "C" int prt_set_smooth_normals(prt_ctx* c, const uint32_t* corner_group, 
     sm.weighting = weighting; sm.crease = crease_cos;
     sm.on = true;
     c->scene.smooth = std::move(sm);
+    return PRT_OK;
+}
+
+// ---- the mesh posed on the device from the frame's bone matrices (prt.h prt_set_skin / prt_pose; pt_pose.hip) ----------------------------------
+extern "C" int prt_set_skin(prt_ctx* c, const prt_skin* skin) {
+    CTX_CHECK(c);
+    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_skin: no scene with triangles uploaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!skin) {                                           // off: nothing of the scene changes, the buffers go
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->scene.skin = Skin{};
+        return PRT_OK;
+    }
+    // every refusal before anything of the skin in force is touched
+    const uint32_t T = c->scene.n_tris;
+    if (T > PRT_MAX_TRIANGLE_SLOTS)
+        return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_skin: more than PRT_MAX_TRIANGLE_SLOTS triangles (corners are addressed by 32-bit indices)");
+    if (const char* m = pose_skin_error(skin->rest_vertices, skin->rest_normals, skin->bone_index, skin->bone_weight, skin->n_bones, T))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, std::string("prt_set_skin: ") + m + " (the skin in force stays)");
+    // everything a pose will ever need, into buffers of their own: a failure here leaves the skin in force as it was
+    const size_t corners = 3 * (size_t)T;
+    Skin sk;
+    auto put = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
+    hipError_t e = sk.rest_v.alloc(corners * 4);
+    if (e == hipSuccess) e = put(sk.rest_v, skin->rest_vertices, corners * 16);
+    if (e == hipSuccess && skin->rest_normals) e = sk.rest_n.alloc(corners * 4);
+    if (e == hipSuccess && skin->rest_normals) e = put(sk.rest_n, skin->rest_normals, corners * 16);
+    if (e == hipSuccess) e = sk.index.alloc(corners * 4);
+    if (e == hipSuccess) e = put(sk.index, skin->bone_index, corners * 8);
+    if (e == hipSuccess) e = sk.weight.alloc(corners * 4);
+    if (e == hipSuccess) e = put(sk.weight, skin->bone_weight, corners * 16);
+    if (e == hipSuccess) e = sk.mats.alloc(12 * (size_t)skin->n_bones);
+    if (e == hipSuccess) e = sk.out_v.alloc(corners * 4);
+    if (e == hipSuccess && skin->rest_normals) e = sk.out_n.alloc(corners * 4);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        c->err = std::string("prt_set_skin: ") + hipGetErrorString(e);
+        return PRT_ERR_HIP;
+    }
+    sk.n_bones = skin->n_bones;
+    sk.on = true;
+    c->scene.skin = std::move(sk);
+    return PRT_OK;
+}
+
+// the refusals of both doors that come before the path the pose enters
+static int pose_checks(prt_ctx* c, const void* matrices, uint32_t mode, const char* who) {
+    const std::string w(who);
+    if (!c->have_scene || !c->scene.skin.on) return fail(c, PRT_ERR_NOT_READY, w + ": no skin set (prt_set_skin)");
+    if (!matrices) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null matrices");
+    if (mode != PRT_POSE_REFIT && mode != PRT_POSE_REBUILD) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown mode (the scene is unchanged)");
+    return PRT_OK;
+}
+
+extern "C" int prt_pose_device(prt_ctx* c, const void* d_matrices, uint32_t mode, uint32_t max_leaf) {
+    CTX_CHECK(c);
+    if (int rc = pose_checks(c, d_matrices, mode, "prt_pose_device")) return rc;
+    if (!aligned16(d_matrices)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_pose_device: the matrices must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    Skin& sk = c->scene.skin;
+    // the posed arrays into the skin's own buffers: only scratch of the context is written.  Everything else -- the finite-vertex check, the
+    // snapshot, the guides, the tile orders, the generated normals -- is the entered path's, over these buffers as over a caller's
+    PoseTables t;
+    t.rest_v = sk.rest_v; t.rest_n = sk.rest_n; t.bone_index = sk.index; t.bone_weight = sk.weight; t.n_tris = c->scene.n_tris;
+    launch_pose(t, static_cast<const float*>(d_matrices), sk.out_v, sk.out_n, c->stream);
+    HIPCHK(c, hipGetLastError());
+    sk.posed = true;
+    const float* n = (c->scene.smooth.on || !sk.rest_n) ? nullptr : sk.out_n.get();
+    const int rc = mode == PRT_POSE_REFIT ? prt_update_vertices_device(c, sk.out_v, n) : prt_rebuild_bvh_device(c, sk.out_v, n, max_leaf);
+    if (rc) (void)hipStreamSynchronize(c->stream);         // (a path that refuses before its own wait: the caller's matrices may be reused on return)
+    return rc;
+}
+
+extern "C" int prt_pose(prt_ctx* c, const float* matrices, uint32_t mode, uint32_t max_leaf) {
+    CTX_CHECK(c);
+    if (int rc = pose_checks(c, matrices, mode, "prt_pose")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    Skin& sk = c->scene.skin;
+    HIPCHK(c, hipMemcpyAsync(sk.mats, matrices, 12 * (size_t)sk.n_bones * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return prt_pose_device(c, sk.mats, mode, max_leaf);
+}
+
+extern "C" int prt_read_posed(prt_ctx* c, float* vertices, float* normals) {
+    CTX_CHECK(c);
+    const Skin& sk = c->scene.skin;
+    if (!c->have_scene || !sk.on || !sk.posed) return fail(c, PRT_ERR_NOT_READY, "prt_read_posed: no pose yet (prt_set_skin, prt_pose)");
+    if (!vertices) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_posed: null vertices");
+    if (normals && !sk.rest_n) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_posed: the skin has no rest normals: normals must be NULL");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    const size_t bytes = 3 * (size_t)c->scene.n_tris * 4 * sizeof(float);
+    HIPCHK(c, hipMemcpy(vertices, sk.out_v, bytes, hipMemcpyDeviceToHost));
+    if (normals) HIPCHK(c, hipMemcpy(normals, sk.out_n, bytes, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 

@@ -58,6 +58,16 @@ struct Smooth {
     float crease = 0.0f;
 };
 
+// prt_set_skin (pt_pose.hip): the rest pose (float4[3T]; rest_n empty for a skin without normals), four indices and four weights per corner,
+// the frame's matrices (12 floats per bone: the host door's staging) and what a pose writes -- the posed vertices and normals (float4[3T])
+struct Skin {
+    DevBuf<float> rest_v, rest_n, weight, mats, out_v, out_n;
+    DevBuf<uint16_t> index;
+    uint32_t n_bones = 0;
+    bool on = false;
+    bool posed = false;                            // a pose, accepted or refused, has written out_v (and out_n)
+};
+
 // everything of the uploaded scene: prt_upload_scene starts from a fresh one
 struct Scene {
     TreeSet tree;                                  // slot_vtx, level_pairs and root arrive with the first update, query or rebuild (refit_tables)
@@ -88,6 +98,7 @@ struct Scene {
     DevBuf<prt_mesh> stage_meshes;
     Snapshots snap;                                // also dropped by prt_set_motion(off)
     Smooth smooth;                                 // also dropped by prt_set_smooth_normals(NULL)
+    Skin skin;                                     // also dropped by prt_set_skin(NULL)
 };
 
 // everything of the frame part, with its size: alloc_frame starts from a fresh one.  All but the state planes, fb and the tile buffers are

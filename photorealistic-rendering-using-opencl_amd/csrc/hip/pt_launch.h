@@ -130,6 +130,17 @@ struct SmoothTables {
 };
 // the face records of `vertices`, then one normal per corner into `normals` (device, float4[3 n_tris], 16-byte aligned): two launches
 void launch_smooth_normals(const SmoothTables& t, const float* vertices, float* normals, hipStream_t stream);
+// pt_pose.hip.  prt_set_skin: the rest pose and the per-corner influences on the device (all device memory, 16-byte aligned)
+struct PoseTables {
+    const float* rest_v;            // float4[3 n_tris]
+    const float* rest_n;            // float4[3 n_tris], or null: no normals are posed
+    const uint16_t* bone_index;     // 4 per corner
+    const float* bone_weight;       // 4 per corner
+    uint32_t n_tris;
+};
+// the posed vertices into out_v and, with rest normals, the posed normals into out_n (device, float4[3 n_tris] each, 16-byte aligned) from
+// `matrices` (device, 16-byte aligned, 12 floats per bone): one launch
+void launch_pose(const PoseTables& t, const float* matrices, float* out_v, float* out_n, hipStream_t stream);
 // pt_build.hip.  prt_rebuild_bvh: the scratch of one build over T triangles, carved out of one device allocation of the context
 struct BuildNode;
 struct BuildExtent;
