@@ -1,16 +1,11 @@
 """tests/emu/cast_api.py -- TEST INFRASTRUCTURE: builds and binds tests/emu/libcast_emu.so, the per-ray bodies of the ray queries
 (csrc/hip/pt_cast.h) compiled for the host over a scene packed by pt_pack.cpp (cast_emu.cpp), as emu_api.py does for the lane machine."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-LIB = os.path.join(HERE, "libcast_emu.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import _emu
+from _emu import aligned, ptr, ref
 
 RAY_FLOATS, HIT_WORDS = 8, 12
 # numpy view of prt_hit (include/prt.h)
@@ -18,43 +13,21 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"), 
 assert HIT_DTYPE.itemsize == 48
 GUARD = 0xA5A5A5A5
 
+NAME, SRCS, OPT, DEFINES = "cast_emu", [_emu.src("cast_emu.cpp"), _emu.PACK], "-O2", ("PT_EMU",)
+LIB = _emu.lib_path(NAME)
+PROTOTYPES = {
+    "cast_emu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_int]),
+    "cast_emu_pixel_rays": (None, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cast_emu_root_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def build():
-    srcs = [os.path.join(HERE, "cast_emu.cpp"), os.path.join(PKG, "csrc", "hip", "pt_pack.cpp")]
-    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_cast.h", "pt_guides.h", "pt_device.h", "pt_filter.h", "pt_layout.h", "pt_pack.h")] + \
-        [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    cmd = [HIPCC, "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DPT_EMU", "-x", "hip", "--cuda-host-only",
-           "-Wno-unused-command-line-argument", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc", "hip"),
-           "-I" + os.path.join(PKG, "csrc", "host"), "-shared", "-o", LIB] + srcs
-    subprocess.run(cmd, check=True)
-    return LIB
-
-
-_lib = None
+    return _emu.build_lib(NAME, SRCS, OPT, DEFINES)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.cast_emu.restype = C.c_int
-        _lib.cast_emu.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_int]
-        _lib.cast_emu_pixel_rays.restype = None
-        _lib.cast_emu_pixel_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib.cast_emu_root_box.restype = C.c_int
-        _lib.cast_emu_root_box.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return _lib
-
-
-def aligned(shape, dtype):
-    """a zeroed, 16-byte aligned array (the bodies load and store 16 bytes at a time)"""
-    dtype = np.dtype(dtype)
-    n = int(np.prod(shape)) * dtype.itemsize
-    raw = np.zeros(n + 16, dtype=np.uint8)
-    off = (-raw.ctypes.data) % 16
-    return raw[off:off + n].view(dtype).reshape(shape)
+    return _emu.shared_lib(NAME, SRCS, OPT, DEFINES, PROTOTYPES)
 
 
 def _rays(rays):
@@ -69,8 +42,7 @@ def _run(cfg, desc, any_hit, sched, rays, words):
     out = aligned((n * words + 16,), np.uint32)            # 16 guard words behind the n records
     out[:] = GUARD
     err = C.create_string_buffer(256)
-    rc = lib().cast_emu(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(desc), C.c_void_p), int(any_hit), int(sched),
-                        r.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p), err, 256)
+    rc = lib().cast_emu(ref(cfg), ref(desc), int(any_hit), int(sched), ptr(r), n, ptr(out), err, 256)
     if rc:
         raise RuntimeError("cast_emu failed (%d): %s" % (rc, err.value.decode()))
     assert (out[n * words:] == GUARD).all(), "cast_emu wrote behind its %d records" % n
@@ -91,15 +63,14 @@ def pixel_rays(cam, width, full_height, xy):
     """the rays prt_cast_pixels generates for the (x, y) pairs xy: float32 [n, 8]"""
     xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
     r = aligned((max(len(xy), 1), RAY_FLOATS), np.float32)
-    lib().cast_emu_pixel_rays(C.cast(C.pointer(cam), C.c_void_p), int(width), int(full_height), xy.ctypes.data_as(C.c_void_p), len(xy),
-                              r.ctypes.data_as(C.c_void_p))
+    lib().cast_emu_pixel_rays(ref(cam), int(width), int(full_height), ptr(xy), len(xy), ptr(r))
     return r[:len(xy)].copy()
 
 
 def root_box(cfg, desc):
     """float32 [6] = min_x max_x min_y max_y min_z max_z of the packed tree's root (zeros for a scene without triangles)"""
     box = np.zeros(6, dtype=np.float32)
-    rc = lib().cast_emu_root_box(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(desc), C.c_void_p), box.ctypes.data_as(C.c_void_p))
+    rc = lib().cast_emu_root_box(ref(cfg), ref(desc), ptr(box))
     if rc:
         raise RuntimeError("pack_scene failed (%d)" % rc)
     return box

@@ -1,55 +1,35 @@
 """tests/emu/emu_api.py -- TEST INFRASTRUCTURE: builds and binds tests/emu/libpt_emu.so, the product's device header
 (csrc/hip/pt_device.h) compiled for the host and driven by a wave emulator (pt_emu.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-LIB = os.path.join(HERE, "libpt_emu.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import _emu
+from _emu import ptr, ref
+
+NAME, SRCS, OPT, DEFINES = "pt_emu", [_emu.src("pt_emu.cpp"), _emu.PACK], "-O2", ("PT_EMU",)
+LIB = _emu.lib_path(NAME)
+PROTOTYPES = {
+    "emu_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_void_p,
+                             C.c_uint32, C.c_float, C.c_void_p]),
+    "emu_select_variant": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p)]),
+    "emu_last_variant": (C.c_char_p, []),
+    "emu_variant_row": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    "emu_selftest_fn": (None, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "emu_selftest_env": (None, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+}
 
 
 def build():
-    srcs = [os.path.join(HERE, "pt_emu.cpp"), os.path.join(PKG, "csrc", "hip", "pt_pack.cpp")]
-    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_device.h", "pt_filter.h", "pt_layout.h", "pt_launch.h", "pt_pack.h", "pt_selftest.h", "pt_variant.h")] + \
-        [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    cmd = [HIPCC, "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-DPT_EMU", "-x", "hip", "--cuda-host-only",
-           "-Wno-unused-command-line-argument", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc", "hip"),
-           "-I" + os.path.join(PKG, "csrc", "host"), "-shared", "-o", LIB] + srcs
-    subprocess.run(cmd, check=True)
-    return LIB
-
-
-_lib = None
+    return _emu.build_lib(NAME, SRCS, OPT, DEFINES)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.emu_render.restype = C.c_int
-        _lib.emu_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_void_p,
-                                    C.c_uint32, C.c_float, C.c_void_p]
-        _lib.emu_select_variant.restype = C.c_int
-        _lib.emu_select_variant.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
-                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
-        _lib.emu_last_variant.restype = C.c_char_p
-        _lib.emu_variant_row.restype = C.c_int
-        _lib.emu_variant_row.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
-        _lib.emu_selftest_fn.restype = None
-        _lib.emu_selftest_fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        _lib.emu_selftest_env.restype = None
-        _lib.emu_selftest_env.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    return _lib
+    return _emu.shared_lib(NAME, SRCS, OPT, DEFINES, PROTOTYPES)
 
 
 def select_variant(active_mats, has_medium, n_sdfs, view, pick_random_light, env_is, dist_mask, filter_kind, generic, any_dist):
@@ -79,7 +59,7 @@ def selftest_fn(fn, params, cases):
     params = np.ascontiguousarray(params, dtype=np.float32)
     cases = np.ascontiguousarray(cases, dtype=np.float32)
     out = np.zeros_like(cases)
-    lib().emu_selftest_fn(int(fn), params.ctypes.data_as(C.c_void_p), cases.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cases.shape[0])
+    lib().emu_selftest_fn(int(fn), ptr(params), ptr(cases), ptr(out), cases.shape[0])
     return out
 
 
@@ -89,8 +69,7 @@ def selftest_env(fn, env, cases):
     cases = np.ascontiguousarray(cases, dtype=np.float32)
     assert env.ndim == 3 and env.shape[2] == 3 and cases.ndim == 2 and cases.shape[1] == 32
     out = np.zeros_like(cases)
-    lib().emu_selftest_env(int(fn), env.ctypes.data_as(C.c_void_p), env.shape[1], env.shape[0], cases.ctypes.data_as(C.c_void_p),
-                           out.ctypes.data_as(C.c_void_p), cases.shape[0])
+    lib().emu_selftest_env(int(fn), ptr(env), env.shape[1], env.shape[0], ptr(cases), ptr(out), cases.shape[0])
     return out
 
 
@@ -113,7 +92,7 @@ def render(state_dtype, cfg, desc, camera, W, H, seed_pairs, first_frame=1, stat
     envp, ew, eh = None, 0, 0
     if env is not None:
         env = np.ascontiguousarray(env, dtype=np.float32)
-        envp, eh, ew = env.ctypes.data_as(C.c_void_p), env.shape[0], env.shape[1]
+        envp, eh, ew = ptr(env), env.shape[0], env.shape[1]
     b = blocks if blocks is not None else (1, 1, 0)
     fkind, frad, ftab = 0, 0.0, None
     if pixel_filter is not None:
@@ -122,12 +101,9 @@ def render(state_dtype, cfg, desc, camera, W, H, seed_pairs, first_frame=1, stat
             ftab = np.ascontiguousarray(ftab, dtype=np.float32)
             assert ftab.shape == (257,)
     err = C.create_string_buffer(256)
-    rc = lib().emu_render(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(desc), C.c_void_p), C.cast(C.pointer(camera), C.c_void_p),
-                          envp, ew, eh, W, H, row0, rows, b[0], b[1], b[2], first_frame, n_frames,
-                          seeds.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p), img.ctypes.data_as(C.c_void_p),
-                          spp_limit, walk_min_lanes, sched_seed, err, 256, seed_frames,
-                          ahead.ctypes.data_as(C.c_void_p) if ahead is not None else None,
-                          int(fkind), float(frad), ftab.ctypes.data_as(C.c_void_p) if ftab is not None else None)
+    rc = lib().emu_render(ref(cfg), ref(desc), ref(camera), envp, ew, eh, W, H, row0, rows, b[0], b[1], b[2], first_frame, n_frames,
+                          ptr(seeds), ptr(state), ptr(img), spp_limit, walk_min_lanes, sched_seed, err, 256, seed_frames,
+                          ptr(ahead), int(fkind), float(frad), ptr(ftab))
     if rc:
         e = RuntimeError("emu_render failed (%d): %s" % (rc, err.value.decode()))
         e.code = rc

@@ -1,51 +1,31 @@
 """tests/emu/motion_api.py -- TEST INFRASTRUCTURE: builds and binds tests/emu/libmotion_emu.so, the bodies of the motion plane
 (csrc/hip/pt_motion.h) compiled for the host (motion_emu.cpp), as refit_api.py does for the refit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-LIB = os.path.join(HERE, "libmotion_emu.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import _emu
+from _emu import aligned_copy, ptr
+
+NAME, SRCS, OPT, INCS = "motion_emu", [_emu.src("motion_emu.cpp")], "-O2", (_emu.INCLUDE, _emu.HIP)
+LIB = _emu.lib_path(NAME)
+PROTOTYPES = {
+    "motion_emu_displacement": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "motion_emu_pixel": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+}
 
 
 def build():
-    src = os.path.join(HERE, "motion_emu.cpp")
-    deps = [src] + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_motion.h", "pt_layout.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    cmd = [HIPCC, "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-x", "hip", "--cuda-host-only",
-           "-Wno-unused-command-line-argument", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc", "hip"), "-shared", "-o", LIB, src]
-    subprocess.run(cmd, check=True)
-    return LIB
-
-
-_lib = None
+    return _emu.build_lib(NAME, SRCS, OPT, incs=INCS)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.motion_emu_displacement.restype = None
-        _lib.motion_emu_displacement.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib.motion_emu_pixel.restype = None
-        _lib.motion_emu_pixel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    return _lib
+    return _emu.shared_lib(NAME, SRCS, OPT, prototypes=PROTOTYPES, incs=INCS)
 
 
 def _aligned_records(rec):
     """float32 [n, 12] -> a 16-byte aligned copy (TriGeom is alignas(16))"""
-    rec = np.asarray(rec, dtype=np.float32).reshape(-1, 12)
-    raw = np.zeros(rec.size * 4 + 16, dtype=np.uint8)
-    off = (-raw.ctypes.data) % 16
-    out = raw[off:off + rec.size * 4].view(np.float32).reshape(rec.shape)
-    out[...] = rec
-    return out
+    return aligned_copy(np.asarray(rec, dtype=np.float32).reshape(-1, 12), np.float32)
 
 
 def displacement(prev, cur, slots, uv):
@@ -56,8 +36,7 @@ def displacement(prev, cur, slots, uv):
     uv = np.ascontiguousarray(uv, dtype=np.float32)
     assert slots.size == 0 or int(slots.max()) < len(p) == len(c)
     out = np.zeros((len(slots), 3), dtype=np.float32)
-    lib().motion_emu_displacement(p.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p),
-                                  uv.ctypes.data_as(C.c_void_p), len(slots), out.ctypes.data_as(C.c_void_p))
+    lib().motion_emu_displacement(ptr(p), ptr(c), ptr(slots), ptr(uv), len(slots), ptr(out))
     return out
 
 
@@ -67,6 +46,5 @@ def pixel(d, hit, contributing):
     hit = np.ascontiguousarray(hit, dtype=np.uint8)
     con = np.ascontiguousarray(contributing, dtype=np.uint8)
     out = np.zeros(4, dtype=np.float32)
-    lib().motion_emu_pixel(d.ctypes.data_as(C.c_void_p), hit.ctypes.data_as(C.c_void_p), con.ctypes.data_as(C.c_void_p), len(hit),
-                           out.ctypes.data_as(C.c_void_p))
+    lib().motion_emu_pixel(ptr(d), ptr(hit), ptr(con), len(hit), ptr(out))
     return out

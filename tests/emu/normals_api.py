@@ -1,51 +1,29 @@
 """tests/emu/normals_api.py -- TEST INFRASTRUCTURE: builds and binds tests/emu/libnormals_emu.so, the bodies of the smooth-normal kernels
 (csrc/hip/pt_normals.h) and the host group-table builder compiled for the host with the library's flags and run serially (normals_emu.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-LIB = os.path.join(HERE, "libnormals_emu.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import _emu
+from _emu import aligned, aligned_copy, ptr
 
 UNIT, AREA = 0, 1
 
+NAME, SRCS, OPT = "normals_emu", [_emu.src("normals_emu.cpp")], ("-O3", "-fno-slp-vectorize")
+LIB = _emu.lib_path(NAME)
+PROTOTYPES = {
+    "normals_emu_weld": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "normals_emu_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "normals_emu_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+}
+
 
 def build():
-    srcs = [os.path.join(HERE, "normals_emu.cpp")]
-    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_normals.h", "pt_refit.h", "pt_layout.h")] + \
-        [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    cmd = [HIPCC, "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-x", "hip", "--cuda-host-only",
-           "-Wno-unused-command-line-argument", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc", "hip"),
-           "-I" + os.path.join(PKG, "csrc", "host"), "-shared", "-o", LIB] + srcs
-    subprocess.run(cmd, check=True)
-    return LIB
-
-
-_lib = None
+    return _emu.build_lib(NAME, SRCS, OPT)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.normals_emu_weld.restype = C.c_int
-        _lib.normals_emu_weld.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
-        _lib.normals_emu_table.restype = C.c_int
-        _lib.normals_emu_table.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        _lib.normals_emu_generate.restype = C.c_int
-        _lib.normals_emu_generate.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
-    return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return _emu.shared_lib(NAME, SRCS, OPT, prototypes=PROTOTYPES)
 
 
 def table(groups, n_groups):
@@ -53,25 +31,18 @@ def table(groups, n_groups):
     g = np.ascontiguousarray(groups, dtype=np.uint32)
     T = g.size // 3
     first, member = np.zeros(n_groups + 1, dtype=np.uint32), np.zeros(3 * T, dtype=np.uint32)
-    if lib().normals_emu_table(_p(g), T, n_groups, _p(first), _p(member)):
+    if lib().normals_emu_table(ptr(g), T, n_groups, ptr(first), ptr(member)):
         return None
     return first, member
 
 
 def generate(vertices, groups, n_groups, weighting, crease_cos):
     """the bodies, serially: (normals float32 [3T, 4], face records {f, l} float32 [T, 4]); None for an id >= n_groups"""
-    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    v = aligned_copy(np.asarray(vertices, dtype=np.float32).reshape(-1), np.float32)          # (the bodies load and store float4s)
     g = np.ascontiguousarray(groups, dtype=np.uint32)
     T = v.size // 12
     assert g.size == 3 * T
-    raw = np.zeros(12 * T + 4, dtype=np.float32)                       # (a 16-byte aligned window: the bodies store float4s)
-    off = (-raw.ctypes.data % 16) // 4
-    out, face = raw[off:off + 12 * T].reshape(3 * T, 4), np.zeros((T, 4), dtype=np.float32)
-    if v.ctypes.data % 16:
-        keep = np.zeros(12 * T + 4, dtype=np.float32)
-        o2 = (-keep.ctypes.data % 16) // 4
-        keep[o2:o2 + 12 * T] = v.reshape(-1)
-        v = keep[o2:o2 + 12 * T]
-    if lib().normals_emu_generate(_p(v), T, _p(g), n_groups, weighting, C.c_float(crease_cos), _p(out), _p(face)):
+    out, face = aligned((3 * T, 4), np.float32), np.zeros((T, 4), dtype=np.float32)
+    if lib().normals_emu_generate(ptr(v), T, ptr(g), n_groups, weighting, C.c_float(crease_cos), ptr(out), ptr(face)):
         return None
     return out.copy(), face

@@ -1,59 +1,27 @@
 """tests/emu/pose_api.py -- TEST INFRASTRUCTURE: builds and binds tests/emu/libpose_emu.so, the body of the pose kernel (csrc/hip/pt_pose.h)
 and the checks of prt_set_skin compiled for the host with the library's flags and run serially (pose_emu.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-LIB = os.path.join(HERE, "libpose_emu.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import _emu
+from _emu import aligned_copy as _aligned, ptr
+
+NAME, SRCS, OPT = "pose_emu", [_emu.src("pose_emu.cpp")], ("-O3", "-fno-slp-vectorize")
+LIB = _emu.lib_path(NAME)
+PROTOTYPES = {
+    "pose_emu_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "pose_emu_pose": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pose_emu_max_bones": (C.c_uint32, []),
+}
 
 
 def build():
-    srcs = [os.path.join(HERE, "pose_emu.cpp")]
-    deps = srcs + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_pose.h", "pt_refit.h", "pt_layout.h")] + \
-        [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    cmd = [HIPCC, "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-x", "hip", "--cuda-host-only",
-           "-Wno-unused-command-line-argument", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc", "hip"),
-           "-I" + os.path.join(PKG, "csrc", "host"), "-shared", "-o", LIB] + srcs
-    subprocess.run(cmd, check=True)
-    return LIB
-
-
-_lib = None
+    return _emu.build_lib(NAME, SRCS, OPT)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.pose_emu_check.restype = C.c_int
-        _lib.pose_emu_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
-        _lib.pose_emu_pose.restype = None
-        _lib.pose_emu_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        _lib.pose_emu_max_bones.restype = C.c_uint32
-        _lib.pose_emu_max_bones.argtypes = []
-    return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _aligned(a, dtype):
-    """a 16-byte aligned contiguous copy of `a` (the body loads and stores float4s)"""
-    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
-    raw = np.zeros(a.nbytes + 16, dtype=np.uint8)
-    off = -raw.ctypes.data % 16
-    out = raw[off:off + a.nbytes].view(dtype)
-    out[:] = a
-    return out
+    return _emu.shared_lib(NAME, SRCS, OPT, prototypes=PROTOTYPES)
 
 
 def check(rest_v, rest_n, bone_index, bone_weight, n_bones):
@@ -61,7 +29,7 @@ def check(rest_v, rest_n, bone_index, bone_weight, n_bones):
     v = np.ascontiguousarray(rest_v, dtype=np.float32)
     n = None if rest_n is None else np.ascontiguousarray(rest_n, dtype=np.float32)
     b, w = np.ascontiguousarray(bone_index, dtype=np.uint16), np.ascontiguousarray(bone_weight, dtype=np.float32)
-    return lib().pose_emu_check(_p(v), _p(n), _p(b), _p(w), int(n_bones), v.size // 12) == 0
+    return lib().pose_emu_check(ptr(v), ptr(n), ptr(b), ptr(w), int(n_bones), v.size // 12) == 0
 
 
 def pose(rest_v, rest_n, bone_index, bone_weight, matrices):
@@ -74,5 +42,5 @@ def pose(rest_v, rest_n, bone_index, bone_weight, matrices):
     assert b.size == 4 * corners and w.size == 4 * corners and m.size % 12 == 0 and (n is None or n.size == 4 * corners)
     out_v = _aligned(np.full(4 * corners, np.nan), np.float32)
     out_n = None if n is None else _aligned(np.full(4 * corners, np.nan), np.float32)
-    lib().pose_emu_pose(_p(v), _p(n), _p(b), _p(w), _p(m), corners, _p(out_v), _p(out_n))
+    lib().pose_emu_pose(ptr(v), ptr(n), ptr(b), ptr(w), ptr(m), corners, ptr(out_v), ptr(out_n))
     return out_v.reshape(-1, 4).copy(), None if out_n is None else out_n.reshape(-1, 4).copy()

@@ -1,16 +1,11 @@
 """tests/emu/prims_api.py -- TEST INFRASTRUCTURE: builds and binds tests/emu/libprims_emu.so, the bodies of prt_update_primitives and of the
 primitives' motion (csrc/hip/pt_prims.h) compiled for the host (prims_emu.cpp), as motion_api.py does for the triangles' motion."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-LIB = os.path.join(HERE, "libprims_emu.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import _emu
+from _emu import aligned, ptr
 
 MESH_BYTES = 256
 # numpy view of prt_mesh (include/prt_types.h)
@@ -18,55 +13,30 @@ MESH_DTYPE = np.dtype([("mat", "u1", 64), ("pos", "<f4", 4), ("_pad0", "u1", 48)
 SPHERE_FLOATS, SDF_FLOATS, QUAD_FLOATS = 4, 8, 20          # DevSphere, DevSdf, DevQuad (csrc/hip/pt_layout.h)
 assert MESH_DTYPE.itemsize == MESH_BYTES
 
-
-def _flags(extra=()):
-    return ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-x", "hip", "--cuda-host-only", "-Wno-unused-command-line-argument",
-            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc", "hip")] + list(extra)
+NAME, SRCS, OPT, INCS = "prims_emu", [_emu.src("prims_emu.cpp")], "-O2", (_emu.INCLUDE, _emu.HIP)
+LIB = _emu.lib_path(NAME)
+_DISP = (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p])
+PROTOTYPES = {
+    "prims_emu_pack": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "prims_emu_sphere": _DISP,
+    "prims_emu_quad": _DISP,
+    "prims_emu_sdf": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "prims_emu_pixel": (None, [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+}
 
 
 def build():
-    src = os.path.join(HERE, "prims_emu.cpp")
-    deps = [src] + [os.path.join(PKG, "csrc", "hip", f) for f in ("pt_prims.h", "pt_motion.h", "pt_layout.h")] + \
-        [os.path.join(ROOT, "include", "prt_types.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    subprocess.run([HIPCC] + _flags() + ["-shared", "-o", LIB, src], check=True)
-    return LIB
+    return _emu.build_lib(NAME, SRCS, OPT, incs=INCS)
+
+
+def lib():
+    return _emu.shared_lib(NAME, SRCS, OPT, prototypes=PROTOTYPES, incs=INCS)
 
 
 def build_main(out, sanitize=True):
     """the stand-alone program of prims_emu.cpp (its own main) at `out`, under -fsanitize=address,undefined unless told otherwise"""
     san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run([HIPCC] + _flags(["-DPRIMS_EMU_MAIN"] + san) + ["-o", out, os.path.join(HERE, "prims_emu.cpp")], check=True)
-    return out
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.prims_emu_pack.restype = C.c_uint32
-        _lib.prims_emu_pack.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        for name in ("prims_emu_sphere", "prims_emu_quad"):
-            getattr(_lib, name).restype = None
-            getattr(_lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib.prims_emu_sdf.restype = None
-        _lib.prims_emu_sdf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib.prims_emu_pixel.restype = None
-        _lib.prims_emu_pixel.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_uint32, C.c_void_p]
-    return _lib
-
-
-def aligned(shape, dtype):
-    """a zeroed, 16-byte aligned array (the records are alignas(16))"""
-    dtype = np.dtype(dtype)
-    n = int(np.prod(shape)) * dtype.itemsize
-    raw = np.zeros(n + 16, dtype=np.uint8)
-    off = (-raw.ctypes.data) % 16
-    return raw[off:off + n].view(dtype).reshape(shape)
+    return _emu.program(out, SRCS, OPT, ("PRIMS_EMU_MAIN",), san, incs=INCS)
 
 
 def _al(a, floats):
@@ -74,10 +44,6 @@ def _al(a, floats):
     out = aligned((max(len(a), 1), floats), np.float32)
     out[:len(a)] = a.view(np.float32)
     return out
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def pack(meshes, n_spheres, n_sdfs, types):
@@ -90,7 +56,7 @@ def pack(meshes, n_spheres, n_sdfs, types):
     sph, sdf, quad = aligned((max(n_spheres, 1), 4), np.float32), aligned((max(n_sdfs, 1), 8), np.float32), aligned((max(n_quads, 1), 20), np.float32)
     types = np.ascontiguousarray(types, dtype=np.uint8)
     bad = np.zeros(max(count, 1), dtype=np.uint8)
-    lib().prims_emu_pack(_p(m), count, n_spheres, n_sdfs, _p(types), _p(sph), _p(sdf), _p(quad), _p(bad))
+    lib().prims_emu_pack(ptr(m), count, n_spheres, n_sdfs, ptr(types), ptr(sph), ptr(sdf), ptr(quad), ptr(bad))
     return sph[:n_spheres].copy(), sdf[:n_sdfs].copy(), quad[:n_quads].copy(), bad[:count].astype(bool)
 
 
@@ -99,10 +65,10 @@ def _disp(fn, floats, prev, cur, idx, p):
     idx = np.ascontiguousarray(idx, dtype=np.uint32)
     out = np.zeros((len(idx), 3), dtype=np.float32)
     if p is None:
-        fn(_p(a), _p(b), _p(idx), len(idx), _p(out))
+        fn(ptr(a), ptr(b), ptr(idx), len(idx), ptr(out))
     else:
         p = np.ascontiguousarray(p, dtype=np.float32)
-        fn(_p(a), _p(b), _p(idx), _p(p), len(idx), _p(out))
+        fn(ptr(a), ptr(b), ptr(idx), ptr(p), len(idx), ptr(out))
     return out
 
 
@@ -126,6 +92,6 @@ def pixel(sph, sdf, quad, mid, first, p, tri_d, tri_snap, prim_snap):
     p = np.ascontiguousarray(p, dtype=np.float32)
     tri_d = np.ascontiguousarray(tri_d, dtype=np.float32)
     out = np.zeros(4, dtype=np.float32)
-    lib().prims_emu_pixel(*[_p(x) for x in t], len(sph[0]), len(sdf[0]), _p(mid), _p(first), _p(p), _p(tri_d), int(tri_snap), int(prim_snap), len(mid),
-                          _p(out))
+    lib().prims_emu_pixel(*[ptr(x) for x in t], len(sph[0]), len(sdf[0]), ptr(mid), ptr(first), ptr(p), ptr(tri_d), int(tri_snap), int(prim_snap), len(mid),
+                          ptr(out))
     return out

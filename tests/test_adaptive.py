@@ -11,15 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, VARIANTS, variant_camera, variant_config
+from support import bytes_rows as _bytes, pkg as _pkg
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 HIP = os.path.join(PKG, "csrc", "hip")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("photorealistic-rendering-using-opencl_amd")
 
 
 # ---- the convergence test on the host (no GPU) -----------------------------------------------------------------------------------------
@@ -120,10 +116,6 @@ def _setup(prt, variant, W, H):
     r.set_camera(cam)
     r.resize(W, H)
     return scene, cfg, cam, env, r
-
-
-def _bytes(state):
-    return np.ascontiguousarray(state).view(np.uint8).reshape(state.size, -1)
 
 
 def _bits(img):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bits as _bits, pkg as _pkg, relmse as _relmse
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 HIP = os.path.join(PKG, "csrc", "hip")
@@ -324,11 +325,6 @@ class Caster:
 
 # ---- on the GPU ------------------------------------------------------------------------------------------------------------------------------
 
-def _pkg():
-    import importlib
-    return importlib.import_module("photorealistic-rendering-using-opencl_amd")
-
-
 def _setup(prt, scene_json, W, H, pinhole=True, env=False):
     scene = prt.HostScene(scene_json)
     cfg = scene.config()
@@ -342,10 +338,6 @@ def _setup(prt, scene_json, W, H, pinhole=True, env=False):
     r.set_camera(cam)
     r.resize(W, H)
     return scene, cfg, cam, r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.gpu
@@ -457,10 +449,6 @@ def test_filter_equals_the_formulas(prt):
     assert (_bits(out) == _bits(r.denoise())).all()
     assert r.lib.prt_denoise(r.ctx, C.byref(p), None, None) == 0
     r.close()
-
-
-def _relmse(x, ref):
-    return float(np.mean((x[..., :3] - ref[..., :3]) ** 2 / (ref[..., :3] ** 2 + 1e-2)))
 
 
 @pytest.mark.gpu

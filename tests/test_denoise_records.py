@@ -15,6 +15,7 @@ import pytest
 
 from conftest import ROOT
 from test_denoise import _setup, denoise_ref, spatial_variance, stats_variance
+from support import bits as _bits, to_device as _to_device
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 HIP = os.path.join(PKG, "csrc", "hip")
@@ -80,21 +81,9 @@ SOURCES, PASSES = ("stats", "spatial"), (1, 5)
 SPLITS = [("blocks", 8, 2), ("blocks", 8, 3), ("tiles", (0, 40, 70)), ("tiles", (0, 24, 50, 70)), ("tiles", (0, 1, 70))]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _torch():
     import torch
     return torch
-
-
-def _to_device(a):
-    """a numpy array as a tensor on cuda:0, finished (the library's streams do not wait for torch's)"""
-    torch = _torch()
-    t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-    torch.cuda.synchronize()
-    return t
 
 
 def _export(r):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ALPHA_VARIANTS, variant_config, GOLDEN, ROOT, VARIANTS, VIEW_VARIANTS, variant_camera
+from support import assert_same_render as _same
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
@@ -28,12 +29,6 @@ def _scene(prt, variant, W, H):
     cfg = variant_config(scene, variant)
     cfg.phase_function = phase
     return scene, cfg, variant_camera(prt, variant, W, H), (prt.make_sky(64, 32) if use_env else None)
-
-
-def _same(oracle, s0, i0, s1, i1, what):
-    bad = oracle.state_fields_equal(s0, s1.view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(i0, i1), "%s: framebuffer differs" % what
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))

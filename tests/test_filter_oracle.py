@@ -25,6 +25,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT, VARIANTS, variant_camera, variant_config
 from test_pixel_filter import DEFAULT_R, KINDS, SETS, _quad_scene, sample_u, table, warp
+from support import assert_same_render as _same
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
@@ -100,12 +101,6 @@ def _scene(prt, variant, W, H, pinhole=False):
 def _emu_filter(kind, r):
     T = table(kind, r) if kind in TABLE_KINDS else None
     return (KINDS[kind], r, T), T
-
-
-def _same(oracle, s0, i0, s1, i1, what):
-    bad = oracle.state_fields_equal(s0, s1.view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(i0, i1), "%s: framebuffer differs" % what
 
 
 @pytest.mark.parametrize("kind,r", FILTERS)

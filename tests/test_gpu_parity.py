@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ALPHA_VARIANTS, variant_config, GOLDEN, PKG_NAME, ROOT, VARIANTS, VIEW_VARIANTS, variant_camera
+from support import assert_same_render as _assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +30,6 @@ def _setup(prt, variant, W, H, rows=None, row0=0):
     else:
         r.set_tile(W, H, row0, rows)
     return scene, cfg, cam, env, r
-
-
-def _assert_same(oracle, ostate, oimg, state, img, what):
-    bad = oracle.state_fields_equal(ostate, state.view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(oimg, img), "%s: framebuffer differs" % what
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))

@@ -19,20 +19,13 @@ from test_denoise import EPS, MAT_COND, MAT_DIEL, MAT_ROUGH_COND, MAT_ROUGH_DIEL
 from test_refit import deform
 from test_temporal import _close, camera_basis, centre_dirs, project, temporal_ref
 from test_temporal_records import H0, T_DEFAULTS, W0, World, _plain_records, _unit
+from support import bits as _bits, pkg as _pkg, rodrigues as _rodrigues
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
 PKG = os.path.join(ROOT, PKG_NAME)
 NEW_API = ("prt_set_motion", "prt_read_motion", "prt_export_motion", "prt_denoise_records_temporal_motion")
 f32 = np.float32
-
-
-def _pkg():
-    return importlib.import_module(PKG_NAME)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- no GPU: the API -----------------------------------------------------------------------------------------------------------------------------
@@ -270,10 +263,6 @@ CARD_WAVE = 7.0                 # pixels per period of the card's pattern
 CARD_NOISE = 0.05
 CARD_FRAMES = 8
 MIN_VALID_SHARE = 0.6           # of the card-interior pixels of the last frame: valid history and margin (the mirror: see the test's docstring)
-
-
-def _rodrigues(x, axis, ang):
-    return x * np.cos(ang) + np.cross(axis, x) * np.sin(ang) + axis * (axis @ x) * (1 - np.cos(ang))
 
 
 class MovingWorld(World):

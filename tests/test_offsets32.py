@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import assert_same_render
 
 HIP = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd", "csrc", "hip")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -147,9 +148,7 @@ def _oracle(oracle, case, desc, key, W, H):
 
 
 def _same(oracle, want, state, img, what):
-    bad = oracle.state_fields_equal(want[0], state.view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(want[1], img), "%s: framebuffer differs" % what
+    assert_same_render(oracle, want[0], want[1], state, img, what)
 
 
 def _render(r, prt):

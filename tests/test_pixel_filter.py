@@ -12,16 +12,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bits as _bits, pkg as _pkg
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 KINDS = {"box": 1, "tent": 2, "gaussian": 3, "blackman-harris": 4}
 DEFAULT_R = {"box": 0.5, "tent": 1.0, "gaussian": 1.5, "blackman-harris": 2.0}
 BH = (0.35875, 0.48829, 0.14128, 0.01168)
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("photorealistic-rendering-using-opencl_amd")
 
 
 # ---- prt.h in numpy ----------------------------------------------------------------------------------------------------------------------------
@@ -190,10 +186,6 @@ def _setup(prt, scene_json, W, H, pinhole=False, env=False, cfg_edit=None, text=
     r.set_camera(cam)
     r.resize(W, H)
     return scene, cfg, cam, r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _state_fb(r):

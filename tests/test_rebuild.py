@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import PKG_NAME, ROOT, VARIANTS, variant_camera, variant_config
+from support import assert_same_render as _assert_same, bytes_flat as _bytes
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -184,10 +185,6 @@ def _mirror_build(vertices, max_leaf):
         for ch, (leaf, first, count) in enumerate(rec):
             nodes[2 * k + 1 + ch]["leaf"], nodes[2 * k + 1 + ch]["first"], nodes[2 * k + 1 + ch]["count"] = leaf, first, count
     return mirror_refit(nodes, prims, vertices), prims, deepest + 1, most_two + 1
-
-
-def _bytes(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 def _with(prt, desc, v, n, nodes=None, prims=None, T=None):
@@ -462,12 +459,6 @@ def _oracle_render(oracle, tp, desc, key):
         img.setflags(write=False)
         _oracle_cache[key] = (st, img)
     return _oracle_cache[key]
-
-
-def _assert_same(oracle, ostate, oimg, state, img, what):
-    bad = oracle.state_fields_equal(ostate.view(oracle.PATH_STATE_DTYPE), state.view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(oimg, img), "%s: framebuffer differs" % what
 
 
 def _context(tp, desc=None):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, VARIANTS, variant_camera, variant_config
+from support import assert_same_render as _assert_same, bytes_flat as _bytes
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
@@ -104,10 +105,6 @@ class Case:
         d.bvh_nodes = self.nodes.ctypes.data_as(C.c_void_p)
         self.new_desc = d
         return self
-
-
-def _bytes(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 def _node_bounds(got):
@@ -269,12 +266,6 @@ def _oracle_render(oracle, case, key):
         img.setflags(write=False)
         _oracle_cache[key] = (st, img)
     return _oracle_cache[key]
-
-
-def _assert_same(oracle, ostate, oimg, state, img, what):
-    bad = oracle.state_fields_equal(ostate, state.view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(oimg, img), "%s: framebuffer differs" % what
 
 
 def _context(case, desc=None):

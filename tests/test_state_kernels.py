@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from support import bytes_rows as _bytes
 
 F = np.float32
 U32 = np.uint32
@@ -27,10 +28,6 @@ def _ctx(prt):
 
 def _u32(a):
     return np.ascontiguousarray(a).view(U32)
-
-
-def _bytes(state):
-    return np.ascontiguousarray(state).view(np.uint8).reshape(state.size, -1)
 
 
 def _block_rows(H, B, n_parts, part):

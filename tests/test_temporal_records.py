@@ -18,20 +18,12 @@ from conftest import ROOT
 from test_denoise import denoise_ref, lum, spatial_variance
 from test_denoise_records import _synthetic, _to_device
 from test_temporal import _close, camera_basis, centre_dirs, project, temporal_ref
+from support import bits as _bits, pkg as _pkg
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 NEW_API = ("prt_read_records_history",)
 W0, H0 = 37, 29                          # no multiple of 16, wider than one workgroup
 T_DEFAULTS = dict(alpha_color=0.2, alpha_moments=0.2, tau_z=0.05, cos_n=0.9, history_cap=32)
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("photorealistic-rendering-using-opencl_amd")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- no GPU --------------------------------------------------------------------------------------------------------------------------------

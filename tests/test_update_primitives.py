@@ -21,6 +21,7 @@ from test_motion import D_BOUND as TRI_D_BOUND
 from test_motion import MotionCaster, _bits, _point, temporal_ref_motion, _mirror_history
 from test_refit import deform
 from test_temporal import camera_basis, centre_dirs, project
+from support import assert_same_render, bytes_flat as _bytes, pkg as _pkg, rodrigues as _rodrigues, to_device
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
@@ -29,14 +30,6 @@ NEW_API = ("prt_update_primitives", "prt_update_primitives_device")
 f32 = np.float32
 W, H, FRAMES = 64, 48, 8
 NAN, INF = f32(np.nan), f32(np.inf)
-
-
-def _pkg():
-    return importlib.import_module(PKG_NAME)
-
-
-def _bytes(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 # ---- no GPU: the API ---------------------------------------------------------------------------------------------------------------------------------
@@ -328,12 +321,6 @@ def desc_with(prt, desc, meshes=None, **fields):
     return d
 
 
-def _rodrigues(x, axis, ang):
-    axis = np.asarray(axis, dtype=np.float64)
-    axis = axis / np.linalg.norm(axis)
-    return x * np.cos(ang) + np.cross(axis, x) * np.sin(ang) + axis * (axis @ x) * (1 - np.cos(ang))
-
-
 def move_sphere(m, i, dpos=(0, 0, 0), dr=0.0):
     m["pos"][i, :3] = (m["pos"][i, :3].astype(np.float64) + dpos).astype(f32)
     m["joker"][i, 0] = f32(m["joker"][i, 0] + dr)
@@ -452,16 +439,11 @@ class Moved:
 
 
 def _assert_same(oracle, want, got, what):
-    bad = oracle.state_fields_equal(want[0].view(oracle.PATH_STATE_DTYPE), got[0].view(oracle.PATH_STATE_DTYPE))
-    assert not bad, "%s: path state differs in %s" % (what, bad)
-    assert oracle.images_equal(want[1], got[1]), "%s: framebuffer differs" % what
+    assert_same_render(oracle, want[0], want[1], got[0], got[1], what)
 
 
 def _to_device(meshes):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(meshes).view(np.uint8).copy()).cuda()
-    torch.cuda.synchronize()
-    return t
+    return to_device(np.ascontiguousarray(meshes).view(np.uint8).copy())
 
 
 def _update(r, meshes, door):

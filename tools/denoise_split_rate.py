@@ -10,21 +10,19 @@ One JSON document on stdout (and into --out).
     python tools/denoise_split_rate.py [--width 1920 --height 1080] [--out profiles/r10_denoise_split.json]
 """
 import argparse
-import csv
 import ctypes as C
-import glob
 import importlib
 import json
 import os
 import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _trace import kernel_rows      # noqa: E402
 
 SCENE = "cornell_diffuse.json"
 SPP, GUIDE_K, PASSES, REPS = 16, 4, 5, 5
@@ -72,22 +70,10 @@ def kernels_phase(prt, W, H):
 
 
 def kernel_times(W, H, timeout):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "split", "--",
-               sys.executable, os.path.abspath(__file__), "--phase", "kernels", "--width", str(W), "--height", str(H)]
-        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
-        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        assert traces, "rocprofv3 wrote no kernel trace"
-        with open(traces[0]) as fh:
-            rows = sorted((int(row["Start_Timestamp"]), row["Kernel_Name"], int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
-                          for row in csv.DictReader(fh))
-        stat_rows = []
-        if stats:
-            with open(stats[0]) as fh:
-                stat_rows = [{k: row[k] for k in ("Name", "Calls", "TotalDurationNs", "AverageNs") if k in row} for row in csv.DictReader(fh)
-                             if "rec_" in row.get("Name", "") or "dn_" in row.get("Name", "")]
-    mine = [(name, ns) for _, name, ns in rows if "rec_" in name or "dn_" in name]
+    rows, stat_rows = kernel_rows(["--phase", "kernels", "--width", str(W), "--height", str(H)], "split", timeout, with_stats=True)
+    rows = [(name, e - b) for name, b, e in rows]
+    stat_rows = [row for row in stat_rows if "rec_" in row.get("Name", "") or "dn_" in row.get("Name", "")]
+    mine = [(name, ns) for name, ns in rows if "rec_" in name or "dn_" in name]
     per_filter = 1 + 2 * PASSES                      # dn_var or rec_import, then (gauss, a-trous) per pass
     assert len(mine) == REPS * (1 + 2 * per_filter), len(mine)
     exports = mine[:REPS]

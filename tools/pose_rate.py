@@ -17,20 +17,18 @@ document on stdout (and into --out).  There is no pass mark.
     python tools/pose_rate.py [--scenes cornell_coat,cornell_dragon] [--out profiles/r22_pose.json]
 """
 import argparse
-import csv
-import glob
 import importlib
 import json
 import os
 import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _trace import kernel_rows      # noqa: E402
 
 KERNEL_CALLS = 5
 SKINS = [("rigid", 16), ("rigid", 256), ("four", 16), ("four", 256)]
@@ -139,15 +137,7 @@ def kernels_phase(prt, names):
 
 def kernel_times(prt, names, timeout):
     """per scene and skin: pose_kernel's duration (best and median of the calls after the first) and its streamed bytes per second"""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "pose", "--",
-               sys.executable, os.path.abspath(__file__), "--phase", "kernels", "--scenes", ",".join(names)]
-        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
-        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert traces, "rocprofv3 wrote no kernel trace"
-        with open(traces[0]) as fh:
-            rows = [(row["Kernel_Name"], int(row["Start_Timestamp"]), int(row["End_Timestamp"])) for row in csv.DictReader(fh)]
-    rows = sorted((r for r in rows if "pose_kernel" in r[0]), key=lambda r: r[1])
+    rows = [r for r in kernel_rows(["--phase", "kernels", "--scenes", ",".join(names)], "pose", timeout) if "pose_kernel" in r[0]]
     assert len(rows) == KERNEL_CALLS * len(SKINS) * len(names), len(rows)
     out = {}
     for s, name in enumerate(names):

@@ -15,8 +15,6 @@ stdout (and into --out).
     python tools/rebuild_rate.py [--scenes cornell_coat,cornell_dragon] [--out profiles/r15_rebuild.json]
 """
 import argparse
-import csv
-import glob
 import importlib
 import json
 import os
@@ -30,6 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _trace import kernel_rows      # noqa: E402
 
 from refit_rate import _median_ms, _scene, deform, write_mesh      # noqa: E402
 
@@ -162,15 +161,7 @@ def kernels_phase(prt, names):
 
 
 def kernel_times(names, timeout):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "rebuild", "--",
-               sys.executable, os.path.abspath(__file__), "--phase", "kernels", "--scenes", ",".join(names)]
-        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
-        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert traces, "rocprofv3 wrote no kernel trace"
-        with open(traces[0]) as fh:
-            rows = [(row["Kernel_Name"], int(row["Start_Timestamp"]), int(row["End_Timestamp"])) for row in csv.DictReader(fh)]
-    rows.sort(key=lambda r: r[1])
+    rows = kernel_rows(["--phase", "kernels", "--scenes", ",".join(names)], "rebuild", timeout)
     # one rebuild = a check launch and everything up to the next one
     starts = [i for i, r in enumerate(rows) if "refit_check" in r[0]]
     assert len(starts) == KERNEL_CALLS * len(names), (len(starts), len(rows))

@@ -23,8 +23,6 @@ Kernel times: from `rocprofv3 --kernel-trace --stats` in a run of its own (this 
     python tools/refit_rate.py [--scenes cornell_coat,cornell_dragon] [--out profiles/r12_refit.json]
 """
 import argparse
-import csv
-import glob
 import importlib
 import json
 import os
@@ -38,6 +36,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _trace import kernel_rows      # noqa: E402
 
 KERNEL_CALLS = 5
 f32 = np.float32
@@ -295,15 +294,7 @@ def normals_kernels_phase(prt, names):
 
 def normals_kernel_times(names, timeout):
     """per scene: the durations of the kernels of one generated update (best of the calls after the first), by kernel"""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "normals", "--",
-               sys.executable, os.path.abspath(__file__), "--phase", "normals-kernels", "--scenes", ",".join(names)]
-        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
-        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert traces, "rocprofv3 wrote no kernel trace"
-        with open(traces[0]) as fh:
-            rows = [(row["Kernel_Name"], int(row["Start_Timestamp"]), int(row["End_Timestamp"])) for row in csv.DictReader(fh)]
-    rows = sorted((r for r in rows if "refit_" in r[0] or "normals_" in r[0]), key=lambda r: r[1])
+    rows = [r for r in kernel_rows(["--phase", "normals-kernels", "--scenes", ",".join(names)], "normals", timeout) if "refit_" in r[0] or "normals_" in r[0]]
     starts = [i for i, r in enumerate(rows) if "refit_check" in r[0]]
     assert len(starts) == KERNEL_CALLS * len(names), (len(starts), len(rows))
     out = {}
@@ -340,15 +331,7 @@ def kernels_phase(prt, names):
 
 
 def kernel_times(names, timeout):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "refit", "--",
-               sys.executable, os.path.abspath(__file__), "--phase", "kernels", "--scenes", ",".join(names)]
-        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
-        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        assert traces, "rocprofv3 wrote no kernel trace"
-        with open(traces[0]) as fh:
-            rows = [(row["Kernel_Name"], int(row["Start_Timestamp"]), int(row["End_Timestamp"])) for row in csv.DictReader(fh)]
-    rows = sorted((r for r in rows if "refit_" in r[0]), key=lambda r: r[1])
+    rows = [r for r in kernel_rows(["--phase", "kernels", "--scenes", ",".join(names)], "refit", timeout) if "refit_" in r[0]]
     # one update = a check launch and everything up to the next one
     starts = [i for i, r in enumerate(rows) if "refit_check" in r[0]]
     assert len(starts) == KERNEL_CALLS * len(names), (len(starts), len(rows))

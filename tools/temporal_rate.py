@@ -11,14 +11,11 @@ own (this script with --phase kernels).  One JSON document on stdout (and into -
     python tools/temporal_rate.py [--width 1920 --height 1080] [--scenes cornell_diffuse,cornell_roughdiel] [--out profiles/r07_temporal.json]
 """
 import argparse
-import csv
-import glob
 import importlib
 import json
 import os
 import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -26,6 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _trace import kernel_rows      # noqa: E402
 
 KERNEL_CALLS = 6
 
@@ -62,20 +60,9 @@ def kernels_phase(prt, W, H, step):
 
 
 def kernel_times(W, H, step, timeout):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "tm", "--",
-               sys.executable, os.path.abspath(__file__), "--phase", "kernels", "--width", str(W), "--height", str(H), "--yaw-step", str(step)]
-        subprocess.run(cmd, check=True, timeout=timeout, stdout=subprocess.DEVNULL)
-        traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        assert traces, "rocprofv3 wrote no kernel trace"
-        with open(traces[0]) as fh:
-            rows = [(row["Kernel_Name"], int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) for row in csv.DictReader(fh)]
-        stat_rows = []
-        if stats:
-            with open(stats[0]) as fh:
-                stat_rows = [{k: row[k] for k in ("Name", "Calls", "TotalDurationNs", "AverageNs") if k in row} for row in csv.DictReader(fh)
-                             if "tm_" in row.get("Name", "") or "dn_" in row.get("Name", "") or "guide_kernel" in row.get("Name", "")]
+    rows, stat_rows = kernel_rows(["--phase", "kernels", "--width", str(W), "--height", str(H), "--yaw-step", str(step)], "tm", timeout, with_stats=True)
+    rows = [(name, e - b) for name, b, e in rows]
+    stat_rows = [row for row in stat_rows if "tm_" in row.get("Name", "") or "dn_" in row.get("Name", "") or "guide_kernel" in row.get("Name", "")]
     call = [(name, ns) for name, ns in rows if "tm_" in name or "dn_" in name]
     per_call = 1 + 1 + 2 * 5 + 1                      # dn_var, tm_reproject, (gauss, atrous) x 5, tm_feedback
     assert len(call) == KERNEL_CALLS * per_call, len(call)
