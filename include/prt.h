@@ -822,6 +822,73 @@ int prt_pose(prt_ctx* ctx, const float* matrices /* n_bones x 12, host */, uint3
 int prt_pose_device(prt_ctx* ctx, const void* d_matrices /* 16-byte aligned */, uint32_t mode, uint32_t max_leaf);
 int prt_read_posed(prt_ctx* ctx, float* vertices /* float4[3T] */, float* normals /* float4[3T], may be NULL */);
 
+/* Deforming geometry: the mesh MORPHED on the device from per-frame target weights -- morph targets / blend shapes, alone or in front of the
+ * skin (no counterpart in the reference).  The second per-frame input of an animated mesh besides its bone matrices is a handful of
+ * weights; the targets themselves are static, sparse per-corner deltas.  The caller gives the base mesh and the targets once and from then
+ * on n_targets floats per frame; the library blends the 3T vertices (and normals) with one streaming kernel into buffers of the context and
+ * hands them to the refit or the rebuild it already has -- or poses them by the skin in the same kernel (glTF's order: morph, then skin).
+ * Opt-in: without these calls every bit of every result is what it was.
+ * Corner c = 3i + k as for the skin.  A target lists the corners it moves, strictly ascending, with a position delta dp and -- optionally --
+ * a normal delta dn per listed corner.  The ENTRIES of a corner are the (t, dp, dn) of every target t that lists it, in ascending t.
+ * The morph, all f32, no contraction; sqrtf and / correctly rounded.  Per corner with base position (x, y, z) and base normal (nx, ny, nz):
+ *       p = (x, y, z);   n = (nx, ny, nz)
+ *       for each entry, in that order, with w = weights[t] != 0:     p.i = p.i + w * dp.i;   n.i = n.i + w * dn.i      i = x, y, z
+ *     (a weight of +0 or -0 skips the entry.  A target with d_normal == NULL has dn = +0.  Weights need not sum to 1 and may be negative.)
+ *   prt_morph:         vertex = {p, 0};   L = sqrtf((n.x*n.x + n.y*n.y) + n.z*n.z);   normal = L > 0 ? n / L (per component) : n;  lane 3 = 0.
+ *     A corner without an active entry keeps its base position bit for bit (a -0 stays -0: nothing is added) and gets its base normal
+ *     renormalised by the same rule.
+ *   prt_pose_morphed:  prt_pose's formulas exactly as they stand, with (x, y, z) = p and (nx, ny, nz) = n, un-normalised (the pose's own
+ *     normalisation is the only one).  The skin's rest arrays are not read, the set's base takes their place: the result is that of prt_pose
+ *     on a skin whose rest pose is p, n.  The morphed rest pose never goes to memory.
+ *   NaN and overflow go through the formulas as they stand, and weights are not checked: a non-finite weight of a target that some corner
+ *   lists gives a non-finite vertex, which the finite-vertex check of the entered path refuses, the scene untouched; of a target without
+ *   entries it is harmless.
+ * The morphed arrays go into buffers of the set (prt_morph) or into the skin's posed buffers (prt_pose_morphed: prt_read_posed returns them),
+ * and the call proceeds EXACTLY as if those buffers had been passed to prt_update_vertices_device (PRT_POSE_REFIT) or to
+ * prt_rebuild_bvh_device (PRT_POSE_REBUILD, max_leaf as there): the finite-vertex check, the motion snapshot rule, the guides going stale,
+ * the forgotten tile orders and what is kept are that path's.  With prt_set_smooth_normals on, or with a set without base normals,
+ * normals == NULL is passed on.  Deterministic: no dependence between lanes, no atomics; tile, row-block and rank contexts that each set the
+ * same targets and morph stay bit-identical in union to one whole-frame context.
+ * prt_set_morph_targets: checks, copies, builds the per-corner table on the host (a stable counting sort of the entries by corner) and
+ *   allocates everything a morph will ever need, the morphed buffers and a table of n_targets weights included.  Device memory per triangle:
+ *   48 bytes of base and 48 of morphed vertices, with base normals 48 + 48 more, and 12 bytes of offsets; per entry 16 bytes, with base
+ *   normals 32; per target 4.  Needs an uploaded scene with T > 0, else PRT_ERR_NOT_READY.  Refused with PRT_ERR_INVALID_ARGUMENT, each
+ *   leaving the set in force as it was: a null base_vertices or targets; n_targets outside 1 .. 65536; a target with n_entries > 0 and a null
+ *   corner or d_position; a corner >= 3T or not strictly above its predecessor; a base x, y, z or normal component that is not finite; a delta
+ *   component that is not finite (lane 3 is never looked at; d_normal is not read when the set has no base_normals).  PRT_ERR_UNSUPPORTED for
+ *   T > PRT_MAX_TRIANGLE_SLOTS and for more than 2^32 - 1 entries in total.  set == NULL turns the feature off and frees the buffers.
+ *   Setting it changes no bit of the scene by itself.  Its lifetime is the skin's: it survives prt_reset, prt_resize, tile and row-block
+ *   calls, camera changes, updates, rebuilds, poses and morphs; prt_upload_scene turns it off.  It is independent of prt_set_skin, in both
+ *   directions.
+ * prt_morph / prt_morph_device: `weights` is n_targets floats -- host memory (copied to the set's table on the context's stream), or device
+ *   memory of the context's device, 16-byte aligned.  mode and max_leaf as in prt_pose.  Ordered on the context's stream and complete on
+ *   return.  PRT_ERR_NOT_READY without a set; PRT_ERR_INVALID_ARGUMENT for null or misaligned weights or an unknown mode; otherwise the
+ *   refusals of the path it enters, each leaving the scene and a pending snapshot exactly as they were.
+ * prt_pose_morphed / prt_pose_morphed_device: additionally PRT_ERR_NOT_READY without a skin, PRT_ERR_INVALID_ARGUMENT for null or misaligned
+ *   matrices and when exactly one of the skin and the set has normals.
+ * prt_read_morphed: the morphed buffers of the last prt_morph, accepted or refused by its path: float4[3T] each.  PRT_ERR_NOT_READY before
+ *   the first one of the set in force; PRT_ERR_INVALID_ARGUMENT for null `vertices`, or for non-null `normals` with a set without base normals. */
+typedef struct prt_morph_target {
+    const uint32_t* corner;      /* n_entries corner indices (c = 3i + k), STRICTLY ascending, each < 3T */
+    const float*    d_position;  /* float4[n_entries], xyz used */
+    const float*    d_normal;    /* float4[n_entries], xyz used; NULL = this target moves no normal (+0 deltas); not read when the set has no base_normals */
+    uint32_t        n_entries;   /* 0 is allowed */
+    uint32_t        _pad;
+} prt_morph_target;
+typedef struct prt_morph_set {
+    const float* base_vertices;  /* float4[3T], layout of prt_scene_desc::vertices */
+    const float* base_normals;   /* float4[3T] or NULL: no normals are morphed */
+    const prt_morph_target* targets;
+    uint32_t n_targets;          /* 1 .. 65536 */
+    uint32_t _pad;
+} prt_morph_set;
+int prt_set_morph_targets(prt_ctx* ctx, const prt_morph_set* set /* NULL = off, frees the buffers */);
+int prt_morph(prt_ctx* ctx, const float* weights /* n_targets, host */, uint32_t mode, uint32_t max_leaf);
+int prt_morph_device(prt_ctx* ctx, const void* d_weights /* 16-byte aligned */, uint32_t mode, uint32_t max_leaf);
+int prt_pose_morphed(prt_ctx* ctx, const float* matrices, const float* weights, uint32_t mode, uint32_t max_leaf);
+int prt_pose_morphed_device(prt_ctx* ctx, const void* d_matrices, const void* d_weights, uint32_t mode, uint32_t max_leaf);
+int prt_read_morphed(prt_ctx* ctx, float* vertices /* float4[3T] */, float* normals /* float4[3T], may be NULL */);
+
 /* What this library was built from (no counterpart in the reference): a hash of the content of every source, header and compiler flag
  * of libprt.so, compiled in by the build (photorealistic-rendering-using-opencl_amd/build.py source_build_id(); a development variant of
  * tools/build_variant.sh reads "variant-<name>-<hash>").  bench.py prints it as `build_id` and refuses to time a library whose id is

@@ -328,6 +328,7 @@ class Renderer:
         self.mesh_count = int(desc.object_count[7])
         self.bvh_node_count = int(desc.bvh_node_count) if desc.triangle_count else 0
         self._skin = None                                  # (the library turns the skin off: T may have changed)
+        self._morph = None                                 # (... and the morph targets)
 
     def update_vertices(self, vertices, normals=None):
         """prt_update_vertices / prt_update_vertices_device: new vertices (and normals; None keeps the uploaded ones) for the uploaded scene,
@@ -479,6 +480,103 @@ class Renderer:
         v = np.zeros((corners, 4), dtype=np.float32)
         n = np.zeros((corners, 4), dtype=np.float32) if with_normals else None
         self._chk(self.lib.prt_read_posed(self.ctx, v.ctypes.data_as(C.c_void_p), None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_read_posed")
+        return v, n
+
+    def set_morph_targets(self, base_vertices, base_normals=None, targets=None):
+        """prt_set_morph_targets: the base mesh (float32 [3T, 4]; base_normals None = no normals are morphed) and the targets, a list of
+        (corner uint32 [n], d_position float32 [n, 4], d_normal float32 [n, 4] or None) with strictly ascending corners.  From then on
+        morph() moves the mesh from one weight per target, and pose_morphed() morphs in front of the skin (prt.h).  base_vertices None turns
+        it off"""
+        if base_vertices is None:
+            self._chk(self.lib.prt_set_morph_targets(self.ctx, None), "prt_set_morph_targets")
+            self._morph = None
+            return
+        corners = 3 * getattr(self, "triangle_count", 0)
+        v = np.ascontiguousarray(base_vertices, dtype=np.float32)
+        n = None if base_normals is None else np.ascontiguousarray(base_normals, dtype=np.float32)
+        if any(a is not None and a.size < 4 * corners for a in (v, n)):
+            raise ValueError("set_morph_targets: needs base arrays of at least %d elements" % (4 * corners))
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        keep = []
+        for t, target in enumerate(targets or ()):
+            corner, dp, dn = target
+            corner = None if corner is None else np.ascontiguousarray(corner, dtype=np.uint32).reshape(-1)
+            dp = None if dp is None else np.ascontiguousarray(dp, dtype=np.float32)
+            dn = None if dn is None else np.ascontiguousarray(dn, dtype=np.float32)
+            entries = 0 if corner is None else corner.size
+            if any(a is not None and a.size < 4 * entries for a in (dp, dn)):
+                raise ValueError("set_morph_targets: target %d needs delta arrays of at least %d elements" % (t, 4 * entries))
+            keep.append((corner, dp, dn, entries))
+        records = (_capi.MorphTarget * max(len(keep), 1))()
+        for t, (corner, dp, dn, entries) in enumerate(keep):
+            records[t] = _capi.MorphTarget(ptr(corner), ptr(dp), ptr(dn), entries, 0)
+        desc = _capi.MorphSet(ptr(v), ptr(n), records if targets is not None else None, len(keep), 0)
+        self._chk(self.lib.prt_set_morph_targets(self.ctx, C.byref(desc)), "prt_set_morph_targets")
+        self._morph = (len(keep), n is not None)
+
+    def _weights_ptr(self, weights, what):
+        """(pointer, is_device) of the frame's morph weights: a numpy array or None (host door), a tensor or a device address (device door)"""
+        count = self._morph[0] if getattr(self, "_morph", None) else 0
+        if isinstance(weights, np.ndarray) or weights is None:
+            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+            if w is not None and w.size < count:
+                raise ValueError("%s: needs a float32 array of at least %d weights" % (what, count))
+            return w, False
+        if hasattr(weights, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(weights.device).synchronize()
+        return self._device_ptr(weights, count, what), True
+
+    def _after_pose(self, mode):
+        if mode == _capi.POSE_REBUILD:
+            count = C.c_uint32(0)
+            self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
+            self.bvh_node_count = int(count.value)
+
+    def morph(self, weights, rebuild=False, max_leaf=0):
+        """prt_morph / prt_morph_device: the mesh morphed on the device from one float32 weight per target, then refitted (rebuild False) or
+        rebuilt (rebuild True, max_leaf as rebuild_bvh).  A numpy array takes the host door; a torch tensor on this context's device (work
+        queued on torch's current stream is waited for) or a device address the device door"""
+        mode = _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
+        w, device = self._weights_ptr(weights, "morph")
+        if device:
+            self._chk(self.lib.prt_morph_device(self.ctx, w, mode, int(max_leaf)), "prt_morph_device")
+        else:
+            self._chk(self.lib.prt_morph(self.ctx, None if w is None else w.ctypes.data_as(C.c_void_p), mode, int(max_leaf)), "prt_morph")
+        self._after_pose(mode)
+
+    def pose_morphed(self, matrices, weights, rebuild=False, max_leaf=0):
+        """prt_pose_morphed / prt_pose_morphed_device: the mesh morphed and then posed by the skin, in one kernel; matrices as pose(), weights
+        as morph().  Two numpy arrays (or None) take the host door, two tensors or device addresses the device door; read_posed() returns
+        the result"""
+        mode = _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
+        host = [isinstance(a, np.ndarray) or a is None for a in (matrices, weights)]
+        if host[0] != host[1]:
+            raise ValueError("pose_morphed: matrices and weights must both be host arrays or both be on the device")
+        w, device = self._weights_ptr(weights, "pose_morphed")
+        floats = 12 * (self._skin[0] if getattr(self, "_skin", None) else 0)
+        if device:
+            if hasattr(matrices, "data_ptr"):
+                import torch
+                torch.cuda.current_stream(matrices.device).synchronize()
+            self._chk(self.lib.prt_pose_morphed_device(self.ctx, self._device_ptr(matrices, floats, "pose_morphed"), w, mode, int(max_leaf)),
+                      "prt_pose_morphed_device")
+        else:
+            m = None if matrices is None else np.ascontiguousarray(matrices, dtype=np.float32)
+            if m is not None and m.size < floats:
+                raise ValueError("pose_morphed: needs a float32 array of at least %d matrix elements" % floats)
+            self._chk(self.lib.prt_pose_morphed(self.ctx, None if m is None else m.ctypes.data_as(C.c_void_p),
+                                                None if w is None else w.ctypes.data_as(C.c_void_p), mode, int(max_leaf)), "prt_pose_morphed")
+        self._after_pose(mode)
+
+    def read_morphed(self):
+        """prt_read_morphed: (vertices, normals) float32 [3T, 4] of the last morph(), accepted or refused; normals None for a set without
+        base normals"""
+        corners = 3 * getattr(self, "triangle_count", 0)
+        with_normals = bool(getattr(self, "_morph", None) and self._morph[1])
+        v = np.zeros((corners, 4), dtype=np.float32)
+        n = np.zeros((corners, 4), dtype=np.float32) if with_normals else None
+        self._chk(self.lib.prt_read_morphed(self.ctx, v.ctypes.data_as(C.c_void_p), None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_read_morphed")
         return v, n
 
     def read_bvh(self):

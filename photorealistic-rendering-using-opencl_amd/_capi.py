@@ -125,6 +125,17 @@ class Skin(C.Structure):
 
 POSE_REFIT, POSE_REBUILD = 0, 1
 
+
+# prt_set_morph_targets: prt_morph_target and prt_morph_set of include/prt.h
+class MorphTarget(C.Structure):
+    _fields_ = [("corner", C.c_void_p), ("d_position", C.c_void_p), ("d_normal", C.c_void_p), ("n_entries", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class MorphSet(C.Structure):
+    _fields_ = [("base_vertices", C.c_void_p), ("base_normals", C.c_void_p), ("targets", C.POINTER(MorphTarget)), ("n_targets", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 # (name, restype, argtypes) of every symbol include/prt.h declares
 PRT_API = [
     ("prt_create", C.c_int, [C.c_int, C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -150,6 +161,12 @@ PRT_API = [
     ("prt_pose", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("prt_pose_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("prt_read_posed", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_set_morph_targets", C.c_int, [C.c_void_p, C.POINTER(MorphSet)]),
+    ("prt_morph", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("prt_morph_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("prt_pose_morphed", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("prt_pose_morphed_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("prt_read_morphed", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_set_camera", C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     ("prt_upload_envmap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("prt_resize", C.c_int, [C.c_void_p, C.c_int, C.c_int]),

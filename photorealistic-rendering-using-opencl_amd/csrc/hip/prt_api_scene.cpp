@@ -1,5 +1,5 @@
 // prt_api_scene.cpp -- the scene calls of the C ABI (include/prt.h): upload, vertex updates with a refit, rebuilds, the tree's read-backs,
-// motion on / off, smooth normals, the skin and its poses.
+// motion on / off, smooth normals, the skin and its poses, the morph targets and their morphs.
 #include <cmath>
 #include <new>
 #include <utility>
@@ -7,6 +7,7 @@
 #include "prt_ctx.h"
 #include "pt_build.h"
 #include "pt_normals.h"
+#include "pt_morph.h"
 #include "pt_pack.h"
 #include "pt_pose.h"
 #include "pt_refit.h"
@@ -573,6 +574,150 @@ extern "C" int prt_read_posed(prt_ctx* c, float* vertices, float* normals) {
     const size_t bytes = 3 * (size_t)c->scene.n_tris * 4 * sizeof(float);
     HIPCHK(c, hipMemcpy(vertices, sk.out_v, bytes, hipMemcpyDeviceToHost));
     if (normals) HIPCHK(c, hipMemcpy(normals, sk.out_n, bytes, hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+// ---- the mesh morphed on the device from the frame's target weights, alone or in front of the skin (prt.h prt_set_morph_targets; pt_morph.hip) --
+extern "C" int prt_set_morph_targets(prt_ctx* c, const prt_morph_set* set) {
+    CTX_CHECK(c);
+    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_morph_targets: no scene with triangles uploaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!set) {                                            // off: nothing of the scene changes, the buffers go
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->scene.morph = MorphSet{};
+        return PRT_OK;
+    }
+    // every refusal before anything of the set in force is touched
+    const uint32_t T = c->scene.n_tris;
+    int code = PRT_OK;
+    if (const char* m = morph_set_error(set, T, &code)) return fail(c, code, std::string("prt_set_morph_targets: ") + m + " (the set in force stays)");
+    // everything a morph will ever need, into buffers of their own: a failure here leaves the set in force as it was
+    MorphTable tab;
+    try {
+        morph_build_table(set, T, tab);
+    } catch (const std::bad_alloc&) {
+        return fail(c, PRT_ERR_UNSUPPORTED,"prt_set_morph_targets: out of host memory for the per-corner table (the set in force stays)");
+    }
+    const size_t corners = 3 * (size_t)T;
+    const bool nrm = set->base_normals != nullptr;
+    MorphSet ms;
+    auto put = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    hipError_t e = ms.base_v.alloc(corners * 4);
+    if (e == hipSuccess) e = put(ms.base_v, set->base_vertices, corners * 16);
+    if (e == hipSuccess && nrm) e = ms.base_n.alloc(corners * 4);
+    if (e == hipSuccess && nrm) e = put(ms.base_n, set->base_normals, corners * 16);
+    if (e == hipSuccess) e = ms.offset.upload(tab.offset);
+    if (e == hipSuccess) e = ms.entry_p.alloc(tab.entry_p.size() * 4);
+    if (e == hipSuccess) e = put(ms.entry_p, tab.entry_p.data(), tab.entry_p.size() * 16);
+    if (e == hipSuccess && nrm) e = ms.entry_n.alloc(tab.entry_n.size() * 4);
+    if (e == hipSuccess && nrm) e = put(ms.entry_n, tab.entry_n.data(), tab.entry_n.size() * 16);
+    if (e == hipSuccess) e = ms.weights.alloc(set->n_targets);
+    if (e == hipSuccess) e = ms.out_v.alloc(corners * 4);
+    if (e == hipSuccess && nrm) e = ms.out_n.alloc(corners * 4);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        c->err = std::string("prt_set_morph_targets: ") + hipGetErrorString(e);
+        return PRT_ERR_HIP;
+    }
+    ms.n_targets = set->n_targets;
+    ms.on = true;
+    c->scene.morph = std::move(ms);
+    return PRT_OK;
+}
+
+// the refusals of the four doors that come before the path the morph enters
+static int morph_checks(prt_ctx* c, const void* weights, uint32_t mode, const char* who) {
+    const std::string w(who);
+    if (!c->have_scene || !c->scene.morph.on) return fail(c, PRT_ERR_NOT_READY, w + ": no morph targets set (prt_set_morph_targets)");
+    if (!weights) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null weights");
+    if (mode != PRT_POSE_REFIT && mode != PRT_POSE_REBUILD) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown mode (the scene is unchanged)");
+    return PRT_OK;
+}
+
+static MorphTables morph_tables(const prt_ctx* c) {
+    const MorphSet& ms = c->scene.morph;
+    MorphTables t;
+    t.base_v = ms.base_v; t.base_n = ms.base_n; t.offset = ms.offset; t.entry_p = ms.entry_p; t.entry_n = ms.entry_n; t.n_tris = c->scene.n_tris;
+    return t;
+}
+
+extern "C" int prt_morph_device(prt_ctx* c, const void* d_weights, uint32_t mode, uint32_t max_leaf) {
+    CTX_CHECK(c);
+    if (int rc = morph_checks(c, d_weights, mode, "prt_morph_device")) return rc;
+    if (!aligned16(d_weights)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_morph_device: the weights must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    MorphSet& ms = c->scene.morph;
+    // the morphed arrays into the set's own buffers; everything else is the entered path's, over these buffers as over a caller's
+    launch_morph(morph_tables(c), static_cast<const float*>(d_weights), ms.out_v, ms.out_n, c->stream);
+    HIPCHK(c, hipGetLastError());
+    ms.morphed = true;
+    const float* n = (c->scene.smooth.on || !ms.base_n) ? nullptr : ms.out_n.get();
+    const int rc = mode == PRT_POSE_REFIT ? prt_update_vertices_device(c, ms.out_v, n) : prt_rebuild_bvh_device(c, ms.out_v, n, max_leaf);
+    if (rc) (void)hipStreamSynchronize(c->stream);         // (a path that refuses before its own wait: the caller's weights may be reused on return)
+    return rc;
+}
+
+extern "C" int prt_morph(prt_ctx* c, const float* weights, uint32_t mode, uint32_t max_leaf) {
+    CTX_CHECK(c);
+    if (int rc = morph_checks(c, weights, mode, "prt_morph")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    MorphSet& ms = c->scene.morph;
+    HIPCHK(c, hipMemcpyAsync(ms.weights, weights, (size_t)ms.n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return prt_morph_device(c, ms.weights, mode, max_leaf);
+}
+
+// ... and of the fused doors: what is not ready first, then the arguments
+static int pose_morphed_checks(prt_ctx* c, const void* matrices, const void* weights, uint32_t mode, const char* who) {
+    const std::string w(who);
+    if (!c->have_scene || !c->scene.morph.on) return fail(c, PRT_ERR_NOT_READY, w + ": no morph targets set (prt_set_morph_targets)");
+    if (!c->scene.skin.on) return fail(c, PRT_ERR_NOT_READY, w + ": no skin set (prt_set_skin)");
+    if (int rc = morph_checks(c, weights, mode, who)) return rc;
+    if (int rc = pose_checks(c, matrices, mode, who)) return rc;
+    if (!c->scene.skin.rest_n != !c->scene.morph.base_n) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": exactly one of the skin and the morph set has normals");
+    return PRT_OK;
+}
+
+extern "C" int prt_pose_morphed_device(prt_ctx* c, const void* d_matrices, const void* d_weights, uint32_t mode, uint32_t max_leaf) {
+    CTX_CHECK(c);
+    if (int rc = pose_morphed_checks(c, d_matrices, d_weights, mode, "prt_pose_morphed_device")) return rc;
+    Skin& sk = c->scene.skin;
+    if (!aligned16(d_matrices) || !aligned16(d_weights))
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_pose_morphed_device: the matrices and the weights must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    // into the skin's posed buffers, as a pose: prt_read_posed returns them
+    PoseTables t;
+    t.rest_v = nullptr; t.rest_n = nullptr; t.bone_index = sk.index; t.bone_weight = sk.weight; t.n_tris = c->scene.n_tris;
+    launch_pose_morphed(morph_tables(c), t, static_cast<const float*>(d_matrices), static_cast<const float*>(d_weights), sk.out_v, sk.out_n, c->stream);
+    HIPCHK(c, hipGetLastError());
+    sk.posed = true;
+    const float* n = (c->scene.smooth.on || !sk.rest_n) ? nullptr : sk.out_n.get();
+    const int rc = mode == PRT_POSE_REFIT ? prt_update_vertices_device(c, sk.out_v, n) : prt_rebuild_bvh_device(c, sk.out_v, n, max_leaf);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+extern "C" int prt_pose_morphed(prt_ctx* c, const float* matrices, const float* weights, uint32_t mode, uint32_t max_leaf) {
+    CTX_CHECK(c);
+    if (int rc = pose_morphed_checks(c, matrices, weights, mode, "prt_pose_morphed")) return rc;
+    Skin& sk = c->scene.skin;
+    MorphSet& ms = c->scene.morph;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(sk.mats, matrices, 12 * (size_t)sk.n_bones * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ms.weights, weights, (size_t)ms.n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return prt_pose_morphed_device(c, sk.mats, ms.weights, mode, max_leaf);
+}
+
+extern "C" int prt_read_morphed(prt_ctx* c, float* vertices, float* normals) {
+    CTX_CHECK(c);
+    const MorphSet& ms = c->scene.morph;
+    if (!c->have_scene || !ms.on || !ms.morphed) return fail(c, PRT_ERR_NOT_READY, "prt_read_morphed: no morph yet (prt_set_morph_targets, prt_morph)");
+    if (!vertices) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_morphed: null vertices");
+    if (normals && !ms.base_n) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_morphed: the set has no base normals: normals must be NULL");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    const size_t bytes = 3 * (size_t)c->scene.n_tris * 4 * sizeof(float);
+    HIPCHK(c, hipMemcpy(vertices, ms.out_v, bytes, hipMemcpyDeviceToHost));
+    if (normals) HIPCHK(c, hipMemcpy(normals, ms.out_n, bytes, hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 

@@ -68,6 +68,17 @@ struct Skin {
     bool posed = false;                            // a pose, accepted or refused, has written out_v (and out_n)
 };
 
+// prt_set_morph_targets (pt_morph.hip): the base mesh (float4[3T]; base_n empty for a set without normals), the per-corner table (offset
+// [3T + 1], one float4 per entry and, with normals, a second one), the frame's weights (one float per target: the host doors' staging) and
+// what prt_morph writes -- the morphed vertices and normals (float4[3T])
+struct MorphSet {
+    DevBuf<float> base_v, base_n, entry_p, entry_n, weights, out_v, out_n;
+    DevBuf<uint32_t> offset;
+    uint32_t n_targets = 0;
+    bool on = false;
+    bool morphed = false;                          // a prt_morph, accepted or refused, has written out_v (and out_n)
+};
+
 // everything of the uploaded scene: prt_upload_scene starts from a fresh one
 struct Scene {
     TreeSet tree;                                  // slot_vtx, level_pairs and root arrive with the first update, query or rebuild (refit_tables)
@@ -99,6 +110,7 @@ struct Scene {
     Snapshots snap;                                // also dropped by prt_set_motion(off)
     Smooth smooth;                                 // also dropped by prt_set_smooth_normals(NULL)
     Skin skin;                                     // also dropped by prt_set_skin(NULL)
+    MorphSet morph;                                // also dropped by prt_set_morph_targets(NULL)
 };
 
 // everything of the frame part, with its size: alloc_frame starts from a fresh one.  All but the state planes, fb and the tile buffers are

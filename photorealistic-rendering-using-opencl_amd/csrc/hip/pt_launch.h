@@ -141,6 +141,22 @@ struct PoseTables {
 // the posed vertices into out_v and, with rest normals, the posed normals into out_n (device, float4[3 n_tris] each, 16-byte aligned) from
 // `matrices` (device, 16-byte aligned, 12 floats per bone): one launch
 void launch_pose(const PoseTables& t, const float* matrices, float* out_v, float* out_n, hipStream_t stream);
+// pt_morph.hip.  prt_set_morph_targets: the base mesh and the per-corner table of the targets' entries on the device (all device memory,
+// 16-byte aligned)
+struct MorphTables {
+    const float* base_v;            // float4[3 n_tris]
+    const float* base_n;            // float4[3 n_tris], or null: no normals are morphed
+    const uint32_t* offset;         // 3 n_tris + 1: corner c owns entries offset[c] .. offset[c + 1], in ascending target order
+    const float* entry_p;           // float4 per entry: {dp.x, dp.y, dp.z, the target's number as bits}
+    const float* entry_n;           // float4 per entry: dn (not read without base_n)
+    uint32_t n_tris;
+};
+// the morphed vertices into out_v and, with base normals, the morphed and renormalised normals into out_n (device, float4[3 n_tris] each,
+// 16-byte aligned) from `weights` (device, one float per target): one launch
+void launch_morph(const MorphTables& t, const float* weights, float* out_v, float* out_n, hipStream_t stream);
+// the same morph, un-normalised and in registers, as the rest pose of the skin's pose (skin.rest_v and rest_n are not read): one launch
+void launch_pose_morphed(const MorphTables& t, const PoseTables& skin, const float* matrices, const float* weights, float* out_v, float* out_n,
+                         hipStream_t stream);
 // pt_build.hip.  prt_rebuild_bvh: the scratch of one build over T triangles, carved out of one device allocation of the context
 struct BuildNode;
 struct BuildExtent;

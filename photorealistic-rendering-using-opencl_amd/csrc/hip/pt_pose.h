@@ -24,11 +24,11 @@ constexpr uint32_t PT_POSE_MAX_BONES = 65536u;
 // Corner c: A = +0;  for k = 0 .. 3 with w_k != 0 (a zero of either sign skips the influence and its matrix is not read):
 // A_ij = A_ij + w_k * M[b_k]_ij;  p' = ((A_i0 * x + A_i1 * y) + A_i2 * z) + A_i3;  n' = (A_i0 * nx + A_i1 * ny) + A_i2 * nz, L = |n'|,
 // normal = L > 0 ? n' / L : n'.  Lane 3 of both outputs = 0.  rest_n null: no normals (out_n is not written)
-PT_POSE_HD void pose_corner(const float* rest_v, const float* rest_n, const uint16_t* bone_index, const float* bone_weight, const float* matrices,
+// As a function of the corner's loaded values (p: the rest position, lane 3 unused; rest_normal(): the rest normal, asked for after the vertex
+// has been stored and only with has_n), so that pt_morph.h poses a rest pose that exists in registers only
+template <typename RestNormal>
+PT_POSE_HD void pose_values(const RefitQuad& p, bool has_n, RestNormal rest_normal, const RefitQuad& wq, const PoseIndex& idx, const float* matrices,
                             size_t c, float* out_v, float* out_n) {
-    const RefitQuad p = reinterpret_cast<const RefitQuad*>(rest_v)[c];
-    const RefitQuad wq = reinterpret_cast<const RefitQuad*>(bone_weight)[c];
-    const PoseIndex idx = reinterpret_cast<const PoseIndex*>(bone_index)[c];
     const float w[4] = {wq.x, wq.y, wq.z, wq.w};
     RefitQuad r0{0.0f, 0.0f, 0.0f, 0.0f}, r1 = r0, r2 = r0;
     for (int k = 0; k < 4; ++k) {
@@ -42,8 +42,8 @@ PT_POSE_HD void pose_corner(const float* rest_v, const float* rest_n, const uint
     }
     reinterpret_cast<RefitQuad*>(out_v)[c] = RefitQuad{((r0.x * p.x + r0.y * p.y) + r0.z * p.z) + r0.w, ((r1.x * p.x + r1.y * p.y) + r1.z * p.z) + r1.w,
                                                        ((r2.x * p.x + r2.y * p.y) + r2.z * p.z) + r2.w, 0.0f};
-    if (rest_n) {
-        const RefitQuad n = reinterpret_cast<const RefitQuad*>(rest_n)[c];
+    if (has_n) {
+        const RefitQuad n = rest_normal();
         const float nx = (r0.x * n.x + r0.y * n.y) + r0.z * n.z;
         const float ny = (r1.x * n.x + r1.y * n.y) + r1.z * n.z;
         const float nz = (r2.x * n.x + r2.y * n.y) + r2.z * n.z;
@@ -51,6 +51,14 @@ PT_POSE_HD void pose_corner(const float* rest_v, const float* rest_n, const uint
         const bool unit = L > 0.0f;
         reinterpret_cast<RefitQuad*>(out_n)[c] = RefitQuad{unit ? nx / L : nx, unit ? ny / L : ny, unit ? nz / L : nz, 0.0f};
     }
+}
+
+PT_POSE_HD void pose_corner(const float* rest_v, const float* rest_n, const uint16_t* bone_index, const float* bone_weight, const float* matrices,
+                            size_t c, float* out_v, float* out_n) {
+    const RefitQuad p = reinterpret_cast<const RefitQuad*>(rest_v)[c];
+    const RefitQuad wq = reinterpret_cast<const RefitQuad*>(bone_weight)[c];
+    const PoseIndex idx = reinterpret_cast<const PoseIndex*>(bone_index)[c];
+    pose_values(p, rest_n != nullptr, [=]() { return reinterpret_cast<const RefitQuad*>(rest_n)[c]; }, wq, idx, matrices, c, out_v, out_n);
 }
 
 // ---- host only ----------------------------------------------------------------------------------------------------------------------------------
