@@ -889,6 +889,66 @@ int prt_pose_morphed(prt_ctx* ctx, const float* matrices, const float* weights, 
 int prt_pose_morphed_device(prt_ctx* ctx, const void* d_matrices, const void* d_weights, uint32_t mode, uint32_t max_leaf);
 int prt_read_morphed(prt_ctx* ctx, float* vertices /* float4[3T] */, float* normals /* float4[3T], may be NULL */);
 
+/* Deforming geometry: the cost of the current tree, measured on the device, and a rule that rebuilds a refitted tree once it has degraded (no
+ * counterpart in the reference).  A refit keeps the topology, so a mesh that moves far from the pose its tree was built for renders through
+ * boxes that overlap more and more; the surface-area-heuristic cost says by how much, and a rebuild resets it.
+ * The cost, f64, all operations as written, no contraction.  "Pair" k is inner node k of the library's own table: the inner nodes the root
+ * reaches, each holding the boxes and the kinds of its two children (what prt_read_bvh returns, without the nodes nothing references).
+ *   Box area, for a box stored as f32 min_x max_x min_y max_y min_z max_z:  e_i = (double)max_i - (double)min_i;  d_i = e_i > 0.0 ? e_i : 0.0
+ *     (max(e_i, 0) in its comparison form);  A = 2.0 * ((d_x*d_y + d_y*d_z) + d_z*d_x).
+ *   Term of pair k:  t_k = w_0 + w_1;  for an inner child w = 1.0 * A(its box), for a leaf child of primitive_count n > 0
+ *     w = (double)n * A(its box), for an empty leaf w = +0.0 whatever its box.
+ *   Sum S: the n terms t_0 .. t_(n-1) are padded with +0.0 to the next power of two and reduced by the complete binary tree over the pair
+ *     index: level by level, s[i] = s[2i] + s[2i+1], until one value is left.  The shape is part of the contract: it makes every bit of S
+ *     independent of block size, grid size and scheduling (there are no atomics and no hand-off between workgroups in the kernels).
+ *   Inner root:  cost = (A(root) + S) / A(root), root = the root's box as prt_read_bvh_bounds defines node 0 (the union rule over pair 0).
+ *   Leaf root of n triangles:  cost = w / A(root) with w as for a leaf child -- n for a box with area, NaN for one without.
+ *   A(root) == 0 goes through as IEEE gives it: NaN or an infinity.
+ * Up to the order of the sum this is the SAH cost of prt_read_bvh's tree: the sum over the inner nodes the root reaches of their area, plus the
+ * sum over the leaves of area x primitive_count, over the root's area.  The result is a pure function of the pair table and the root's box:
+ * tile, row-block and rank contexts that hold the same tree get the same bits.
+ * prt_bvh_cost: the cost of the current tree -- uploaded, refitted or rebuilt -- into *cost.  One launch per 256-fold level of the sum (three
+ *   for a tree of 400 k pairs), ordered on the context's stream and complete on return; 8 bytes come back.  It reads the scene's tables only:
+ *   like the ray queries it changes nothing of the scene, the frame, the guides, the histories or a pending motion snapshot (its partial sums,
+ *   8 bytes per 256 pairs, are allocated on first use).  It works on trees that prt_update_vertices refuses for their depth.
+ *   PRT_ERR_NOT_READY without a scene or with T == 0, PRT_ERR_INVALID_ARGUMENT for a null pointer.
+ * prt_set_rebuild_policy: opt-in; off (the default) every bit of every result is what it is without these calls, and the refit path launches
+ *   nothing new.  Setting it measures the BASELINE: the cost of the tree as it is at that moment; the baseline is measured again at the end of
+ *   every accepted rebuild while the policy is in force -- prt_rebuild_bvh[_device], PRT_POSE_REBUILD, or the policy's own.  From then on every
+ *   call that goes through prt_update_vertices_device's path -- prt_update_vertices, and PRT_POSE_REFIT of prt_pose*, prt_morph* and
+ *   prt_pose_morphed* -- first does exactly what it does without a policy, then costs the refitted tree, and when
+ *       cost > (double)limit * baseline            (false for a NaN on either side: no rebuild)
+ *   proceeds exactly as if the caller had then called prt_rebuild_bvh_device with the same vertex and normal arguments and the policy's
+ *   max_leaf (the host variant: with its staged buffers; a pose or a morph: with its posed buffers; normals == NULL is passed on as NULL).
+ *   Every bit of the scene, the generated normals, the motion snapshot and the lifetimes are those of that sequence of two calls.  If the
+ *   rebuild is refused or fails, the call returns the rebuild's status and message, and the scene is the valid REFITTED one: the vertices
+ *   have arrived, the old topology stays (e.g. normals == NULL under a caller's tree that does not reference every triangle: every update
+ *   that passes the limit returns PRT_ERR_INVALID_ARGUMENT and leaves a scene that renders).
+ *   limit: a factor >= 1 (1.3: rebuild once the refitted tree costs 30 % more than the last built one); max_leaf as prt_rebuild_bvh, 0 = its
+ *   default.  policy == NULL turns it off.  Needs an uploaded scene with T > 0, else PRT_ERR_NOT_READY.  Refused with
+ *   PRT_ERR_INVALID_ARGUMENT, each leaving the policy in force as it was: a limit that is not finite or below 1, max_leaf > 64.
+ *   PRT_ERR_UNSUPPORTED where no rebuild could ever be accepted (T - 1 > PRT_MAX_NODE_PAIRS).  Setting it changes no bit of the scene.  It
+ *   survives what the skin survives -- prt_reset, prt_resize, tile and row-block calls, camera changes, updates and rebuilds;
+ *   prt_upload_scene turns it off.
+ * prt_get_rebuild_report: what the last refit-path call under the policy did -- cost: the cost after its refit (before any such call: the
+ *   baseline measured by prt_set_rebuild_policy); rebuilt: 1 if that call rebuilt; rebuilds: the rebuilds the policy has made since it was
+ *   set; baseline: the baseline in force now (after that call, or after an explicit rebuild since).  PRT_ERR_NOT_READY without a policy,
+ *   PRT_ERR_INVALID_ARGUMENT for a null pointer.
+ * The loop per displayed frame with a policy: update (or pose, or morph), prt_reset, render, prt_render_guides, prt_denoise_temporal -- the
+ * caller never reads the tree. */
+typedef struct prt_rebuild_policy {
+    float limit;           /* rebuild when cost > limit * baseline; finite, >= 1 */
+    uint32_t max_leaf;     /* of the rebuild: 1 .. 64, 0 = the library's default */
+} prt_rebuild_policy;
+typedef struct prt_rebuild_report {
+    double cost, baseline;
+    uint32_t rebuilt;
+    uint32_t rebuilds;
+} prt_rebuild_report;
+int prt_bvh_cost(prt_ctx* ctx, double* cost);
+int prt_set_rebuild_policy(prt_ctx* ctx, const prt_rebuild_policy* policy /* NULL = off */);
+int prt_get_rebuild_report(prt_ctx* ctx, prt_rebuild_report* out);
+
 /* What this library was built from (no counterpart in the reference): a hash of the content of every source, header and compiler flag
  * of libprt.so, compiled in by the build (photorealistic-rendering-using-opencl_amd/build.py source_build_id(); a development variant of
  * tools/build_variant.sh reads "variant-<name>-<hash>").  bench.py prints it as `build_id` and refuses to time a library whose id is

@@ -329,6 +329,7 @@ class Renderer:
         self.bvh_node_count = int(desc.bvh_node_count) if desc.triangle_count else 0
         self._skin = None                                  # (the library turns the skin off: T may have changed)
         self._morph = None                                 # (... and the morph targets)
+        self._policy = False                               # (... and the rebuild policy)
 
     def update_vertices(self, vertices, normals=None):
         """prt_update_vertices / prt_update_vertices_device: new vertices (and normals; None keeps the uploaded ones) for the uploaded scene,
@@ -342,6 +343,7 @@ class Renderer:
                 raise ValueError("update_vertices: needs float32 arrays of at least %d elements" % floats)
             self._chk(self.lib.prt_update_vertices(self.ctx, None if v is None else v.ctypes.data_as(C.c_void_p),
                                                    None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_update_vertices")
+            self._after_pose(_capi.POSE_REFIT)
             return
         if hasattr(vertices, "data_ptr"):
             import torch
@@ -349,6 +351,7 @@ class Renderer:
         pv = self._device_ptr(vertices, floats, "update_vertices")
         pn = None if normals is None else self._device_ptr(normals, floats, "update_vertices")
         self._chk(self.lib.prt_update_vertices_device(self.ctx, pv, pn), "prt_update_vertices_device")
+        self._after_pose(_capi.POSE_REFIT)
 
     def update_primitives(self, meshes, device=False, count=None):
         """prt_update_primitives / prt_update_primitives_device: the prt_mesh records (256 bytes each, all object_count[7] of them, in the
@@ -468,10 +471,7 @@ class Renderer:
                 import torch
                 torch.cuda.current_stream(matrices.device).synchronize()
             self._chk(self.lib.prt_pose_device(self.ctx, self._device_ptr(matrices, floats, "pose"), mode, int(max_leaf)), "prt_pose_device")
-        if mode == _capi.POSE_REBUILD:
-            count = C.c_uint32(0)
-            self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
-            self.bvh_node_count = int(count.value)
+        self._after_pose(mode)
 
     def read_posed(self):
         """prt_read_posed: (vertices, normals) float32 [3T, 4] of the last pose, accepted or refused; normals None for a skin without rest normals"""
@@ -528,7 +528,8 @@ class Renderer:
         return self._device_ptr(weights, count, what), True
 
     def _after_pose(self, mode):
-        if mode == _capi.POSE_REBUILD:
+        """the node count of a tree that may be a new one: after a rebuild, and after a refit under a rebuild policy"""
+        if mode == _capi.POSE_REBUILD or getattr(self, "_policy", False):
             count = C.c_uint32(0)
             self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
             self.bvh_node_count = int(count.value)
@@ -589,6 +590,31 @@ class Renderer:
         if nodes.size:
             self._chk(self.lib.prt_read_bvh(self.ctx, nodes.ctypes.data_as(C.c_void_p), C.byref(count), prims.ctypes.data_as(C.c_void_p)), "prt_read_bvh")
         return nodes, prims
+
+    def bvh_cost(self):
+        """prt_bvh_cost: the SAH cost of the current tree -- uploaded, refitted or rebuilt -- summed on the device in the fixed order of prt.h
+        (float; the module's bvh_cost(read_bvh()[0]) up to the order of the sum).  Reads the scene only"""
+        cost = C.c_double(0.0)
+        self._chk(self.lib.prt_bvh_cost(self.ctx, C.byref(cost)), "prt_bvh_cost")
+        return float(cost.value)
+
+    def set_rebuild_policy(self, limit, max_leaf=0):
+        """prt_set_rebuild_policy: from now on update_vertices, and pose / morph / pose_morphed with rebuild False, cost the refitted tree and
+        rebuild it (max_leaf as rebuild_bvh) once the cost passes limit x the cost of the last built tree (prt.h).  limit None turns it off"""
+        if limit is None:
+            self._chk(self.lib.prt_set_rebuild_policy(self.ctx, None), "prt_set_rebuild_policy")
+            self._policy = False
+            return
+        policy = _capi.RebuildPolicy(float(limit), int(max_leaf))
+        self._chk(self.lib.prt_set_rebuild_policy(self.ctx, C.byref(policy)), "prt_set_rebuild_policy")
+        self._policy = True
+
+    def rebuild_report(self):
+        """prt_get_rebuild_report: what the last refit-path call under the policy did, as a dict: cost (after its refit), baseline (in force
+        now), rebuilt (bool), rebuilds (by the policy, since it was set)"""
+        rep = _capi.RebuildReport()
+        self._chk(self.lib.prt_get_rebuild_report(self.ctx, C.byref(rep)), "prt_get_rebuild_report")
+        return {"cost": float(rep.cost), "baseline": float(rep.baseline), "rebuilt": bool(rep.rebuilt), "rebuilds": int(rep.rebuilds)}
 
     def _query(self, name, rays, out, words):
         """prt_cast_rays / prt_occluded and their device variants: rays a float32 [n, 8] numpy array (host door) or a tensor on this context's

@@ -136,6 +136,15 @@ class MorphSet(C.Structure):
                 ("_pad", C.c_uint32)]
 
 
+# prt_set_rebuild_policy / prt_get_rebuild_report: prt_rebuild_policy and prt_rebuild_report of include/prt.h
+class RebuildPolicy(C.Structure):
+    _fields_ = [("limit", C.c_float), ("max_leaf", C.c_uint32)]
+
+
+class RebuildReport(C.Structure):
+    _fields_ = [("cost", C.c_double), ("baseline", C.c_double), ("rebuilt", C.c_uint32), ("rebuilds", C.c_uint32)]
+
+
 # (name, restype, argtypes) of every symbol include/prt.h declares
 PRT_API = [
     ("prt_create", C.c_int, [C.c_int, C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -154,6 +163,9 @@ PRT_API = [
     ("prt_rebuild_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_rebuild_bvh_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("prt_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_bvh_cost", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("prt_set_rebuild_policy", C.c_int, [C.c_void_p, C.POINTER(RebuildPolicy)]),
+    ("prt_get_rebuild_report", C.c_int, [C.c_void_p, C.POINTER(RebuildReport)]),
     ("prt_weld_corners", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("prt_set_smooth_normals", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]),
     ("prt_read_normals", C.c_int, [C.c_void_p, C.c_void_p]),

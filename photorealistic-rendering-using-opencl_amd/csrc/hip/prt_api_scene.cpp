@@ -119,6 +119,79 @@ static const float* generate_normals(prt_ctx* c, const float* v) {
     return sm.nrm;
 }
 
+// ---- the cost of the current tree, and the rule that rebuilds a refitted tree (prt.h prt_bvh_cost / prt_set_rebuild_policy; pt_cost.hip) ------
+// the checks are the caller's: a scene with triangles, the device selected.  The launches on the context's stream, the 8 bytes back, complete
+// on return.  Only the scratch is written
+static int measure_cost(prt_ctx* c, double* cost) {
+    Scene& sn = c->scene;
+    HIPCHK(c, sn.cost_work.reserve(cost_work_doubles(c->sc.n_pairs)));
+    const double* at = sn.cost_work;
+    if (c->sc.root_is_leaf)      // (the root's box: the device's after an update, before one as uploaded)
+        launch_bvh_cost_leaf_root(sn.refitted ? sn.tree.root.get() : nullptr, sn.root_bounds, c->sc.root_leaf_count, sn.cost_work, c->stream);
+    else
+        at = launch_bvh_cost(sn.tree.pairs, c->sc.n_pairs, sn.cost_work, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cost, at, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+extern "C" int prt_bvh_cost(prt_ctx* c, double* cost) {
+    CTX_CHECK(c);
+    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_bvh_cost: no scene with triangles uploaded");
+    if (!cost) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_bvh_cost: null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    double v = 0.0;
+    if (int rc = measure_cost(c, &v)) return rc;
+    *cost = v;
+    return PRT_OK;
+}
+
+extern "C" int prt_set_rebuild_policy(prt_ctx* c, const prt_rebuild_policy* policy) {
+    CTX_CHECK(c);
+    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_rebuild_policy: no scene with triangles uploaded");
+    if (!policy) {                                         // off: nothing of the scene changes
+        c->scene.policy = RebuildPolicy{};
+        return PRT_OK;
+    }
+    // every refusal before anything of the policy in force is touched
+    if (!std::isfinite(policy->limit) || policy->limit < 1.0f)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_rebuild_policy: limit is not finite or below 1 (the policy in force stays)");
+    if (policy->max_leaf > 64u) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_rebuild_policy: max_leaf above 64 (the policy in force stays)");
+    if (c->scene.n_tris - 1u > PRT_MAX_NODE_PAIRS)
+        return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_rebuild_policy: more than PRT_MAX_NODE_PAIRS + 1 triangles: no rebuild would be accepted (the policy in force stays)");
+    HIPCHK(c, hipSetDevice(c->device));
+    RebuildPolicy p;
+    if (int rc = measure_cost(c, &p.baseline)) return rc;
+    p.on = true; p.limit = policy->limit; p.max_leaf = policy->max_leaf;
+    p.rep.cost = p.baseline;
+    c->scene.policy = p;
+    return PRT_OK;
+}
+
+extern "C" int prt_get_rebuild_report(prt_ctx* c, prt_rebuild_report* out) {
+    CTX_CHECK(c);
+    if (!c->have_scene || !c->scene.policy.on) return fail(c, PRT_ERR_NOT_READY, "prt_get_rebuild_report: no rebuild policy set (prt_set_rebuild_policy)");
+    if (!out) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_get_rebuild_report: null pointer");
+    *out = c->scene.policy.rep;
+    out->baseline = c->scene.policy.baseline;              // (in force now: an explicit rebuild since the last refit-path call has moved it)
+    return PRT_OK;
+}
+
+// the policy's part of an accepted refit: the refitted tree is costed and, past the limit, rebuilt from the same buffers -- the sequence
+// update, prt_bvh_cost, prt_rebuild_bvh_device, call for call.  A rebuild that is refused or fails returns its status: the scene is the
+// refitted one
+static int policy_after_refit(prt_ctx* c, const void* d_vertices, const void* d_normals) {
+    RebuildPolicy& p = c->scene.policy;
+    double cost = 0.0;
+    if (int rc = measure_cost(c, &cost)) return rc;
+    p.rep.cost = cost; p.rep.rebuilt = 0;
+    if (!(cost > (double)p.limit * p.baseline)) return PRT_OK;       // (a NaN on either side: no rebuild)
+    if (int rc = prt_rebuild_bvh_device(c, d_vertices, d_normals, p.max_leaf)) return rc;       // (measures the new baseline)
+    p.rep.rebuilt = 1; p.rep.rebuilds += 1;
+    return PRT_OK;
+}
+
 extern "C" int prt_update_vertices_device(prt_ctx* c, const void* d_vertices, const void* d_normals) {
     CTX_CHECK(c);
     int rc = refit_prepare(c, d_vertices, "prt_update_vertices_device");
@@ -156,7 +229,7 @@ extern "C" int prt_update_vertices_device(prt_ctx* c, const void* d_vertices, co
     launch_refit(t, v, n, tree.pairs, tree.tri_geom, tree.tri_nrm, tree.root, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));       // the caller's buffers may be reused on return
-    return PRT_OK;
+    return sn.policy.on ? policy_after_refit(c, d_vertices, d_normals) : PRT_OK;
 }
 
 extern "C" int prt_update_vertices(prt_ctx* c, const float* vertices, const float* normals) {
@@ -370,7 +443,7 @@ extern "C" int prt_rebuild_bvh_device(prt_ctx* c, const void* d_vertices, const 
     sn.rebuilt = sn.refit_ready = sn.refitted = true;
     c->frame.guides_valid = false;
     forget_tile_orders(c);
-    return PRT_OK;
+    return sn.policy.on ? measure_cost(c, &sn.policy.baseline) : PRT_OK;       // (prt_set_rebuild_policy: every accepted rebuild moves the baseline)
 }
 
 extern "C" int prt_rebuild_bvh(prt_ctx* c, const float* vertices, const float* normals, uint32_t max_leaf) {

@@ -79,6 +79,16 @@ struct MorphSet {
     bool morphed = false;                          // a prt_morph, accepted or refused, has written out_v (and out_n)
 };
 
+// prt_set_rebuild_policy (pt_cost.hip): the rule in force, the cost of the tree when the rule was set or a rebuild was last accepted, and
+// what the last refit-path call under the rule did
+struct RebuildPolicy {
+    bool on = false;
+    float limit = 0.0f;
+    uint32_t max_leaf = 0;
+    double baseline = 0.0;
+    prt_rebuild_report rep{};
+};
+
 // everything of the uploaded scene: prt_upload_scene starts from a fresh one
 struct Scene {
     TreeSet tree;                                  // slot_vtx, level_pairs and root arrive with the first update, query or rebuild (refit_tables)
@@ -111,6 +121,8 @@ struct Scene {
     Smooth smooth;                                 // also dropped by prt_set_smooth_normals(NULL)
     Skin skin;                                     // also dropped by prt_set_skin(NULL)
     MorphSet morph;                                // also dropped by prt_set_morph_targets(NULL)
+    DevBuf<double> cost_work;                      // prt_bvh_cost's partials (cost_work_doubles of the pairs), on first use; grown when a rebuild needs more
+    RebuildPolicy policy;                          // also dropped by prt_set_rebuild_policy(NULL)
 };
 
 // everything of the frame part, with its size: alloc_frame starts from a fresh one.  All but the state planes, fb and the tile buffers are

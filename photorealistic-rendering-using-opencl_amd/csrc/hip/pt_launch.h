@@ -113,6 +113,13 @@ void launch_refit_check(const float* vertices, size_t n_vertices, uint32_t* flag
 // into root6 (device, 6 floats)
 void launch_refit(const RefitTables& t, const float* vertices, const float* normals, NodePair* pairs, TriGeom* tri_geom, TriNrm* tri_nrm,
                   float* root6, hipStream_t stream);
+// pt_cost.hip.  prt_bvh_cost: the SAH cost of a tree with an inner root from its n_pairs >= 1 pairs (device), one launch per level of
+// PT_COST_BLOCK-fold reduction; work: cost_work_doubles(n_pairs) doubles of scratch (device).  Returns where in `work` the cost is once the
+// stream has run the launches
+size_t cost_work_doubles(uint32_t n_pairs);
+const double* launch_bvh_cost(const NodePair* pairs, uint32_t n_pairs, double* work, hipStream_t stream);
+// ... of a tree whose root is a leaf of `count` triangles into work[0]: root6 the root's box on the device, or null: host_root6 (host, 6 floats)
+void launch_bvh_cost_leaf_root(const float* root6, const float* host_root6, uint32_t count, double* work, hipStream_t stream);
 // pt_prims.hip.  prt_update_primitives: `count` prt_mesh records (device, 16-byte aligned; n_spheres spheres, then n_sdfs SDF primitives, then
 // quads) into the three tables, and 1 into *flag (device; the caller zeroes it first) if a record's t differs from types[i] or a field that
 // is read is not finite
