@@ -361,6 +361,48 @@ PT_DEV Ray create_cam_ray_at(int cx, int cy, float dx, float dy, int width, int 
     ray.t = 0.0f;
     return ray;
 }
+// What the thin lens of create_cam_ray and the cosine_hemisphere of lambert_sample have in common: two draws, the sine and cosine of
+// 2 pi times the first, the square root of the second (2 * PT_PI and PT_TWO_PI are one binary32 constant and the product commutes).  A wave
+// whose lanes run both issues this block twice; lane_front_shared_disk sends both groups through one copy.
+struct DiskSample { float sn, cs, r, xi2; };
+PT_DEV DiskSample disk_sample(Rng& rng) {
+    DiskSample d;
+    const float xi1 = next1D(rng);
+    d.xi2 = next1D(rng);
+    sincos_pair(xi1 * PT_TWO_PI, d.sn, d.cs);
+    d.r = hw_sqrt(d.xi2);
+    return d;
+}
+// create_cam_ray behind its disk sample (`lens`: cam.apertureRadius > 0.00001f, and then `ds` is the sample): the same operations on the
+// same operands, everything that depends on the pixel alone included, so that a caller carries only (cx, cy) across the sample
+PT_DEV Ray cam_ray_from_disk(int cx, int cy, int width, int height, const DevCamera& cam, const bool lens, const DiskSample& ds, Rng& rng) {
+    const f3 hAxis = ld3(cam.hAxis), vAxis = ld3(cam.vAxis), position = ld3(cam.position);
+    const f3 middle = ld3(cam.middle), horizontal = ld3(cam.horizontal), vertical = ld3(cam.vertical);
+    int pixelx = cx;
+    int pixely = height - cy - 1;
+    float sx = (float)pixelx / (width - 1.0f);
+    float sy = (float)pixely / (height - 1.0f);
+    f3 onPlane = middle + (horizontal * ((2 * sx) - 1)) + (vertical * ((2 * sy) - 1));
+    f3 onImagePlane = position + ((onPlane - position) * cam.focalDistance);
+    f3 aperturePoint;
+    if (lens) {
+        float distance = cam.apertureRadius * ds.r;
+        float apertureX = ds.cs * distance;
+        float apertureY = ds.sn * distance;
+        aperturePoint = position + (hAxis * apertureX) + (vAxis * apertureY);
+    } else {
+        aperturePoint = position;
+    }
+    Ray ray;
+    ray.backside = false;
+    ray.origin = aperturePoint;
+    ray.dir = normalize(onImagePlane - aperturePoint);
+    ray.time = next1D(rng);
+    ray.normal = splat(0.0f);
+    ray.pos = splat(0.0f);
+    ray.t = 0.0f;
+    return ray;
+}
 
 // ---- BVH, kernels/geometry/bvh.cl + triangle.cl ------------------------------------------------
 struct RayPre { float ix, iy, iz, sx, sy, sz; bool nx, ny, nz; };
@@ -1577,9 +1619,115 @@ PT_DEV void lane_finish_segment(const DevScene& sc, Lane& L, f3 emission, const 
     L.stage = ST_READY;
 }
 
+// The builds whose only sampled BSDF is Lambert's and that have no medium: the compiled set LIGHT|DIFF, its adaptive and filter builds
+// included (the flags of the run-time dispatch never come with a compiled set, pt_variant.h).  lane_back reuses there what the lane already
+// holds.  (The medium builds of the set keep the parent's code throughout: config 4 runs what it ran.)
+template <unsigned MATS, bool MEDIUM>
+PT_HD constexpr bool lambert_only() { return !MEDIUM && (MATS & ~(PT_MATS_ADAPT | PT_MATS_FILTER)) == (PRT_MAT_LIGHT | PRT_MAT_DIFF); }
+// ... and of those, the builds whose lane_front is lane_front_shared_disk: no pixel filter (create_cam_ray_at).  A medium's distance sample
+// would draw between the segment's start and the BSDF's sample
+template <unsigned MATS, bool MEDIUM>
+PT_HD constexpr bool shared_disk() { return lambert_only<MATS, MEDIUM>() && !(MATS & PT_MATS_FILTER); }
+
+// A, for the shared_disk builds: lane_front below, statement for statement, cut where create_cam_ray and lambert_sample would draw.  In
+// nearly every iteration a wave holds lanes that restart a path AND lanes that shade a diffuse vertex, and the two drew their disk sample
+// (disk_sample: two draws, a sine / cosine pair, a square root) in two branches, one after the other.  Here a lane first goes up to its
+// draw -- the restart, or the hit's material, the miss and light exits, the frame and wi -- then every lane that needs a sample takes it
+// in ONE block with one way in and one way out, then each finishes what it began.  A lane draws what it drew and computes what it computed
+// before; what is live across the block is the shading lane's state, as across lambert_sample before (a restarting lane brings gx, gy).
+template <unsigned MATS>
+PT_DEV void lane_front_shared_disk(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, Lane& L, int gx, int gy) {
+    bool restart = false;
+    if (!L.begun) {                                                      // main.cl:108-136
+        const unsigned frame = fa.first_frame + L.f;
+        const int random0 = const_i32(fa.seed_pairs, 2u * L.f), random1 = const_i32(fa.seed_pairs, 2u * L.f + 1u);
+        L.rng.s0 = (unsigned)gx * frame % 1000u + ((unsigned)random0 * 100u);      // main.cl:108-109
+        L.rng.s1 = (unsigned)gy * frame % 1000u + ((unsigned)random1 * 100u);
+        { const float tt = L.t; L.t = L.time; L.time = tt; }                        // tempToRay after rayToTemp, main.cl:27-28
+        if (L.reset || L.samples == 0) {                                            // main.cl:122-136, up to createCamRay's draws
+            ++L.samples;
+            L.total = 0; L.diff = 0; L.spec = 0; L.trans = 0; L.scatters = 0;
+            L.wasSpecular = true;
+            L.reset = false;
+            L.mask = splat(1.0f);
+            L.h_valid = false;
+            restart = true;
+        }
+        L.begun = true;
+    }
+    const bool shade = L.h_valid;                                        // (a restarting lane has no hit)
+    bool sample = false, mis = false;
+    Frame frame;
+    f3 wi, color;
+    if (shade) {                                                         // the segment's vertex, up to lambert_sample's draws
+        const bool didHit = L.h.didHit;
+        L.mesh_id = L.h.mesh_id;
+        L.t = L.h.t;
+        L.h_valid = false;
+        L.kind = K_NONE; L.terminate = false; L.w2_ran = false; L.sh = false;
+        L.vis = splat(0.0f);
+        const Mat mat = load_mat<dist_mask<MATS>()>(sc.mats, (L.mesh_id + 1) ? (unsigned)(L.mesh_id + 1) : sc.n_meshes + 1u);
+        if (!didHit) {                                                   // pathtracing.cl:66-75
+            f3 emission = splat(0.0f);
+            float alpha = 1.0f;
+            L.reset = true;
+            if (sc.alpha_testing) alpha = 0.0f;
+            else emission = L.mask * env_lookup(sc, L.dir);
+            lane_finish_segment<MATS, false>(sc, L, emission, alpha, false, true, false);
+        } else if (mat.t & PRT_MAT_LIGHT) {                              // pathtracing.cl:77-84
+            f3 emission = splat(0.0f);
+            if (L.wasSpecular) emission = emission + mat.color * L.mask;
+            L.reset = true;
+            lane_finish_segment<MATS, false>(sc, L, emission, 1.0f, false, true, false);
+        } else {                                                         // makeLocalScatterEvent, base.cl:11-14
+            frame = make_frame(L.h.normal);
+            wi = to_local(frame, -L.dir);
+            color = mat.color;
+            mis = (mat.lobes & ~(PRT_LOBE_SPECULAR | PRT_LOBE_FORWARD) & 0xffu) != 0u;
+            sample = (mat.t & PRT_MAT_DIFF) && !(wi.z <= 0.0f);          // bsdf_sample2 of this set: lambert_sample, or nothing
+            if (!sample) {
+                L.wi = wi; L.weight = splat(1.0f); L.pdf = 1.0f; L.sampledLobe = 0u; L.n_shade = L.h.normal;
+                if (mis) {                                               // handleSurface, base.cl:168-172
+                    L.kind = K_SURFACE_MIS; L.terminate = true; L.stage = ST_BACK;
+                } else {
+                    L.reset = true;
+                    lane_finish_segment<MATS, false>(sc, L, splat(0.0f), 1.0f, false, true, false);
+                }
+            }
+        }
+    }
+    const bool lens = cam.apertureRadius > 0.00001f;
+    const bool need_disk = sample || (restart && lens);
+    DiskSample ds;
+    if (need_disk) ds = disk_sample(L.rng);
+    if (restart) {                                                       // the rest of createCamRay
+        const Ray cr = cam_ray_from_disk(gx, gy, fa.width, fa.full_height, cam, lens, ds, L.rng);
+        L.origin = cr.origin; L.dir = cr.dir; L.t = cr.t; L.time = cr.time;
+    }
+    if (sample) {                                                        // the rest of lambert_sample and of the segment's front
+        const f3 wo = F3(ds.cs * ds.r, ds.sn * ds.r, hw_sqrt(prt_fmax(1.0f - ds.xi2, 0.0f)));
+        L.wi = wi; L.weight = color; L.pdf = prt_fabs(wo.z) * PT_INV_PI; L.sampledLobe = PRT_LOBE_DIFFUSE_R; L.n_shade = L.h.normal;
+        L.origin = lane_hit_pos(L);
+        L.dir = to_global(frame, wo);
+        if (mis) {
+            L.kind = K_SURFACE_MIS;
+            L.w2_ran = true; L.stage = ST_WALKC; L.fresh = true; L.w2 = true;
+        } else {
+            lane_finish_segment<MATS, false>(sc, L, splat(0.0f), 1.0f, true, false, false);
+        }
+    }
+    if (!shade) {                                                        // W1: intersect_scene of the path ray, pathtracing.cl:27
+        L.stage = ST_WALKC; L.fresh = true; L.w2 = false;
+    }
+}
+
 // A
 template <unsigned MATS, bool MEDIUM>
 PT_DEV void lane_front(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, Lane& L, int gx, int gy) {
+    if constexpr (shared_disk<MATS, MEDIUM>()) {
+        lane_front_shared_disk<MATS>(sc, cam, fa, L, gx, gy);
+        return;
+    }
     if (!L.begun) {                                                      // main.cl:108-136
         const unsigned frame = fa.first_frame + L.f;
         const int random0 = const_i32(fa.seed_pairs, 2u * L.f), random1 = const_i32(fa.seed_pairs, 2u * L.f + 1u);
@@ -1734,7 +1882,12 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
     if (MATS & PT_MATS_ENVIS) L.sh_vertex = false;
     if (L.kind == K_SURFACE_MIS) {
         constexpr bool ENVIS = (MATS & PT_MATS_ENVIS) != 0;
-        const Mat mat = load_mat<dist_mask<MATS>()>(sc.mats, (L.mesh_id + 1) ? (unsigned)(L.mesh_id + 1) : sc.n_meshes + 1u);
+        // lambert_only builds (no ENVIS, no PICK) do not load the vertex's material a second time: lambert_eval reads nothing of it but the
+        // colour, and that is L.weight where the sample succeeded (lambert_sample: e.weight = mat.color; L.w2_ran says so at a K_SURFACE_MIS
+        // vertex); where it failed -- wi.z <= 0, or a material that is not Lambert's -- the value is zero before the colour is read.  bsdf_pdf
+        // is 0 in these sets
+        constexpr bool REUSE = lambert_only<MATS, MEDIUM>();
+        const Mat mat = REUSE ? Mat() : load_mat<dist_mask<MATS>()>(sc.mats, (L.mesh_id + 1) ? (unsigned)(L.mesh_id + 1) : sc.n_meshes + 1u);
         // PT_MATS_ENVIS: does the map light this vertex at all?  In the default mode it does so through the BSDF-sampled ray alone, looked up in the
         // path's next segment -- which a path that this vertex's counters reset (lane_finish_segment's caps, after its increments by
         // L.sampledLobe) never runs.  Such a vertex gets neither the map sample nor the escaped ray's term, and its light sample is no coin's side
@@ -1794,7 +1947,9 @@ PT_DEV void lane_back(const DevScene& sc, Lane& L) {
                 e.frame = make_frame(L.n_shade);
                 e.wi = L.wi; e.weight = L.weight; e.pdf = L.pdf; e.sampledLobe = L.sampledLobe;
                 e.wo = to_local(e.frame, rec.d);
-                const f3 fr = bsdf_eval2<MATS>(sc, e, mat);
+                f3 fr;
+                if (REUSE) fr = (L.w2_ran && !(e.wo.z <= 0.0f)) ? L.weight * PT_INV_PI * e.wo.z : splat(0.0f);       // lambert_eval
+                else fr = bsdf_eval2<MATS>(sc, e, mat);
                 if (!(dot(fr, fr) == 0.0f)) {
                     L.sh = true; L.sh_d = rec.d; L.sh_tmax = rec.dist;
                     const Mat lm = load_mat(sc.mats, lmesh + 1u);
