@@ -1022,6 +1022,43 @@ const char* prt_last_error(prt_ctx* ctx);
 /* message for a failed prt_create (ctx == NULL) */
 const char* prt_last_global_error(void);
 
+/* Temporal response: a second, short history beside each of the context's two histories and a clamp of the long one against it, for light
+ * that changes on a surface that stands still (the "fast history" of ReLAX; variance clipping after Salvi 2016).  Such a tap passes every test
+ * of the reprojection, so without the clamp a low alpha_color drags the old light for history_cap frames.  Opt-in: while the setting is off
+ * (the default) every bit of every result of the temporal calls is what it is without it.  All f32, no contraction, no atomics.
+ *   Fast history: one more colour f per pixel, double-buffered like the history (32 bytes per pixel per history, allocated by the first
+ *     temporal call made with the setting on).  A pixel that takes the history branch (sum w >= 0.01) blends it from the same valid taps and
+ *     weights:  f_h = (sum w f_prev) / sum w,  n_f = min(n_h + 1, fast_cap) with n_h the reprojected length before the + 1,
+ *     f_i = f_h + (c - f_h) (1 / n_f).  A pixel without history, or with a non-finite c, takes f_i = c.  That is prt_denoise_temporal's accumulation with
+ *     alpha_color = 0 and history_cap = fast_cap; it is never fed back from the filter (PRT_TEMPORAL_FEEDBACK_ATROUS touches the slow colour only).
+ *   Clamp: a pass of its own behind the reprojection and in front of a-trous pass 0.  Window of pixel p: the taps q = p + (dx, dy) with
+ *     |dx|, |dy| <= radius that lie in the frame and whose f_i(q) is finite in all three channels; m their number, taken dy outer and dx
+ *     inner, both ascending.  Per channel: mu = (sum f) / m;  s = sum (f - mu)^2 (a second sweep, not E[f^2] - mu^2);  sigma = sqrtf(s / m);
+ *     lo = mu - k sigma, hi = mu + k sigma.  When p took the history branch, its c_i is finite and m >= 1:
+ *     c_i' = fminf(fmaxf(c_i, lo), hi) per channel, clamped = (c_i' != c_i in any channel), n' = clamped ? min(n, fast_cap) : n.
+ *     The filter's input becomes {c_i', v} and the history stores {c_i', n'}; v, m1 and m2 stay as the reprojection made them (the moments of
+ *     a pixel whose light just changed say "high variance", which is what the spatial filter should hear).  Every other pixel passes through
+ *     bit for bit.
+ *   prt_read_response / prt_read_records_response: per pixel 4 floats {f_i.rgb, flag} in framebuffer order, of the frame history / the record
+ *     history; flag 0 = no history, 1 = history kept, 2 = clamped.  They write nothing.  PRT_ERR_NOT_READY while the setting is off or the
+ *     history is empty; otherwise refused as prt_read_history / prt_read_records_history.  Those two keep returning 0 in float 7.
+ *   prt_set_temporal_response: r NULL = off, which frees the fast planes.  A call that changes the setting empties both histories (the fast
+ *     plane has nothing to reproject); a call with the values already in force does nothing.  Everything that empties a history empties its
+ *     fast plane with it.  PRT_ERR_INVALID_ARGUMENT, leaving the setting in force, for fast_cap == 0, a radius outside 1 .. 3 or a k that is
+ *     not > 0 or not finite; PRT_ERR_UNSUPPORTED with a debug view. */
+#define PRT_RESPONSE_DEFAULT_FAST_CAP 4u
+#define PRT_RESPONSE_DEFAULT_RADIUS 2u
+#define PRT_RESPONSE_DEFAULT_K 2.0f
+typedef struct prt_temporal_response {
+    uint32_t fast_cap;   /* >= 1: length of the fast history in frames */
+    uint32_t radius;     /* 1 .. 3: the window is (2 radius + 1)^2 pixels */
+    float k;             /* > 0, finite: half-width of the clamp in sigmas */
+    uint32_t _pad;
+} prt_temporal_response;
+int prt_set_temporal_response(prt_ctx* ctx, const prt_temporal_response* r);
+int prt_read_response(prt_ctx* ctx, float* out4);
+int prt_read_records_response(prt_ctx* ctx, int width, int height, float* out4);
+
 #ifdef __cplusplus
 }
 #endif

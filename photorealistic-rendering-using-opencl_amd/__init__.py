@@ -15,14 +15,14 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import NORMALS_WEIGHTINGS, LOADER_CREASE_COS, PIXEL_FILTERS,PIXEL_FILTER_DEFAULT_RADIUS, DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
+from ._capi import NORMALS_WEIGHTINGS, LOADER_CREASE_COS, PIXEL_FILTERS,PIXEL_FILTER_DEFAULT_RADIUS, DENOISE_DEFAULTS, DenoiseParams, TEMPORAL_DEFAULTS, TemporalParams, RESPONSE_DEFAULTS, TemporalResponse, Adaptive, AdaptiveReport, Camera, Config, SceneDesc, Stats, load_library, PATH_STATE_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SCENES_DIR = os.path.join(REPO, "scenes")
 MODELS_DIR = os.path.join(SCENES_DIR, "models")
 
-__all__ = ["NORMALS_WEIGHTINGS", "LOADER_CREASE_COS", "weld_corners", "PIXEL_FILTERS","PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "env_cdf", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
+__all__ = ["NORMALS_WEIGHTINGS", "LOADER_CREASE_COS", "weld_corners", "PIXEL_FILTERS","PIXEL_FILTER_DEFAULT_RADIUS", "pixel_filter_offsets", "env_cdf", "adaptive_converged", "adaptive_luminance", "Adaptive", "AdaptiveReport", "DenoiseParams", "DENOISE_DEFAULTS", "TemporalParams", "TEMPORAL_DEFAULTS", "TemporalResponse", "RESPONSE_DEFAULTS", "ensure_dragon_standin", "HostScene", "Renderer", "default_camera", "orbit_camera", "seed_pairs", "scene_arrays", "bvh_cost", "make_sky", "load_hdr", "write_hdr", "PrtError",
            "Camera", "Config", "SceneDesc", "Stats", "PATH_STATE_DTYPE", "SCENES_DIR", "MODELS_DIR", "build", "model_meshes", "build_id", "source_build_id", "check_build_id", "StaleLibrary"]
 
 
@@ -766,6 +766,7 @@ class Renderer:
                          feedback=TEMPORAL_DEFAULTS["feedback"], tonemap=False):
         """prt_denoise_temporal: the history reprojected into this camera and blended with the framebuffer, then denoise()'s filter (prt.h).
         Takes denoise()'s keywords plus the temporal ones; feedback: "atrous" (pass 0's output becomes the history) | "integrated".
+        With set_temporal_response() on, the blended colour is clamped to the fast history's neighbourhood in front of the filter.
         Returns what denoise() returns"""
         p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
         t = TemporalParams(float(alpha_color), float(alpha_moments), float(tau_z), float(cos_n), int(history_cap), self._FEEDBACK[feedback])
@@ -783,6 +784,24 @@ class Renderer:
 
     def reset_history(self):
         self._chk(self.lib.prt_reset_history(self.ctx), "prt_reset_history")
+
+    def set_temporal_response(self, fast_cap=_capi.RESPONSE_DEFAULTS["fast_cap"], radius=_capi.RESPONSE_DEFAULTS["radius"],
+                              k=_capi.RESPONSE_DEFAULTS["k"]):
+        """prt_set_temporal_response: a fast history of fast_cap frames beside both histories of this context, and the clamp of the blended
+        colour to mean +- k sigma of its (2 radius + 1)^2 neighbourhood (prt.h).  set_temporal_response(None) turns it off.  A change of
+        the setting empties both histories"""
+        if fast_cap is None:
+            self._chk(self.lib.prt_set_temporal_response(self.ctx, None), "prt_set_temporal_response")
+            return
+        r = TemporalResponse(int(fast_cap), int(radius), float(k), 0)
+        self._chk(self.lib.prt_set_temporal_response(self.ctx, C.byref(r)), "prt_set_temporal_response")
+
+    def read_response(self):
+        """the temporal response of the frame history: float32 [rows, width, 4] = {f.rgb, flag} per pixel, framebuffer order; flag 0 no
+        history, 1 history kept, 2 clamped"""
+        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
+        self._chk(self.lib.prt_read_response(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_response")
+        return out
 
     @staticmethod
     def _device_ptr(t, floats, what):
@@ -830,6 +849,7 @@ class Renderer:
                                  motion=None):
         """prt_denoise_records_temporal: denoise_records() with denoise_temporal()'s step in front.  `cam`: the camera the records were rendered
         with.  The record history is this context's second one (reset_records_history(); a call with another size empties it too).
+        set_temporal_response() applies to it as to denoise_temporal()'s.
         motion: None, or the frame's motion plane (a [height, width, 4] float32 tensor on this device or a device address: the gathered
         export_motion() of every part) -- prt_denoise_records_temporal_motion"""
         p = DenoiseParams(int(passes), self._VAR_SOURCES[var_source], float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a))
@@ -849,6 +869,13 @@ class Renderer:
         width, height = int(width), int(height)
         out = np.zeros((max(height, 0), max(width, 0), 8), dtype=np.float32)      # a size below 1 is the library's to refuse
         self._chk(self.lib.prt_read_records_history(self.ctx, width, height, out.ctypes.data_as(C.c_void_p)), "prt_read_records_history")
+        return out
+
+    def read_records_response(self, width, height):
+        """read_response()'s twin for the record history: float32 [height, width, 4] = {f.rgb, flag} per pixel"""
+        width, height = int(width), int(height)
+        out = np.zeros((max(height, 0), max(width, 0), 4), dtype=np.float32)      # a size below 1 is the library's to refuse
+        self._chk(self.lib.prt_read_records_response(self.ctx, width, height, out.ctypes.data_as(C.c_void_p)), "prt_read_records_response")
         return out
 
     def set_pixel_filter(self, kind="tent", radius=None):

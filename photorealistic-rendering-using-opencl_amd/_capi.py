@@ -91,6 +91,14 @@ class TemporalParams(C.Structure):
 PRT_TEMPORAL_FEEDBACK_INTEGRATED, PRT_TEMPORAL_FEEDBACK_ATROUS = 0, 1
 TEMPORAL_DEFAULTS = dict(alpha_color=0.2, alpha_moments=0.2, tau_z=0.05, cos_n=0.9, history_cap=32, feedback="atrous")
 
+
+# prt_set_temporal_response: prt_temporal_response and its suggested values (PRT_RESPONSE_DEFAULT_* of include/prt.h)
+class TemporalResponse(C.Structure):
+    _fields_ = [("fast_cap", C.c_uint32), ("radius", C.c_uint32), ("k", C.c_float), ("_pad", C.c_uint32)]
+
+
+RESPONSE_DEFAULTS = dict(fast_cap=4, radius=2, k=2.0)
+
 # prt_set_pixel_filter kinds by name, and the default radius of each (include/prt.h)
 PIXEL_FILTERS = {"none": 0, "box": 1, "tent": 2, "gaussian": 3, "blackman-harris": 4}
 PIXEL_FILTER_DEFAULT_RADIUS = {"none": 0.0, "box": 0.5, "tent": 1.0, "gaussian": 1.5, "blackman-harris": 2.0}
@@ -199,6 +207,8 @@ PRT_API = [
     ("prt_denoise_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p]),
     ("prt_read_history", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_reset_history", C.c_int, [C.c_void_p]),
+    ("prt_set_temporal_response", C.c_int, [C.c_void_p, C.POINTER(TemporalResponse)]),
+    ("prt_read_response", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_export_denoise_inputs", C.c_int, [C.c_void_p, C.c_void_p]),
     ("prt_denoise_records", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_denoise_records_temporal", C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(Camera), C.c_int, C.c_int,
@@ -207,6 +217,7 @@ PRT_API = [
                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("prt_reset_records_history", C.c_int, [C.c_void_p]),
     ("prt_read_records_history", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("prt_read_records_response", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("prt_set_pixel_filter", C.c_int, [C.c_void_p, C.c_uint32, C.c_float]),
     ("prt_pixel_filter_offsets", C.c_int, [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("prt_env_cdf", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,7 @@
 // prt_api_denoise.cpp -- the denoiser's calls of the C ABI (include/prt.h): the a-trous filter and its temporal variant on the context's frame
 // and on records, and both histories.
+#include <cmath>
+
 #include "prt_ctx.h"
 
 static prt_denoise_params default_denoise_params() {
@@ -73,12 +75,16 @@ static int records_output(prt_ctx* c, const float4* out, int W, int H, void* dev
 
 // a temporal call on an npix-pixel history: what it reads (the half of the last call) and writes (the other half).  The history counts as
 // empty until history_commit: a failure in between leaves it empty
-static TemporalHistory history_begin(History& h, size_t npix) {
+static TemporalHistory history_begin(const prt_ctx* c, History& h, size_t npix) {
     float4* half_prev = h.planes + 2 * npix * (size_t)h.cur;           // {c, n} plane, then {m1, m2, v, 0}
     float4* half_next = h.planes + 2 * npix * (size_t)(h.cur ^ 1);
     TemporalHistory t;
     t.cn_prev = half_prev; t.m_prev = half_prev + npix; t.guides_prev = h.guides; t.cam_prev = h.cam; t.valid = h.valid;
     t.cn = half_next; t.m = half_next + npix;
+    if (c->response_on) {                                              // (history_buffers has allocated the fast plane)
+        t.fast_prev = h.fast + npix * (size_t)h.cur; t.fast = h.fast + npix * (size_t)(h.cur ^ 1);
+        t.fast_cap = c->response.fast_cap; t.radius = c->response.radius; t.k = c->response.k;
+    }
     h.valid = false;
     return t;
 }
@@ -91,14 +97,26 @@ static int history_commit(prt_ctx* c, History& h, const float4* guides, size_t n
     h.valid = true;
     return PRT_OK;
 }
-// the last call's half of an npix-pixel history, interleaved per pixel: {c, n}, {m1, m2, v, 0}
+// the last call's half of an npix-pixel history, interleaved per pixel: {c, n}, {m1, m2, v, 0}.  (With a temporal response the spare lane of
+// the moments plane holds the pixel's flag on the device: the read returns the 0 it always has)
 static int read_history_planes(prt_ctx* c, const History& h, size_t npix, float* out8) {
     std::vector<float4> p(2 * npix);
     HIPCHK(c, hipMemcpy(p.data(), h.planes + 2 * npix * (size_t)h.cur, 2 * npix * sizeof(float4), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < npix; ++k) {
         const float4 a = p[k], b = p[npix + k];
         float* o = out8 + 8 * k;
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = 0.0f;
+    }
+    return PRT_OK;
+}
+// ... and its response: {f.rgb, flag} per pixel -- the fast plane's colour and the flag from the spare lane of the moments plane
+static int read_response_planes(prt_ctx* c, const History& h, size_t npix, float* out4) {
+    std::vector<float4> f(npix), m(npix);
+    HIPCHK(c, hipMemcpy(f.data(), h.fast + npix * (size_t)h.cur, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(m.data(), h.planes + 2 * npix * (size_t)h.cur + npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < npix; ++k) {
+        float* o = out4 + 4 * k;
+        o[0] = f[k].x; o[1] = f[k].y; o[2] = f[k].z; o[3] = m[k].w;
     }
     return PRT_OK;
 }
@@ -109,11 +127,13 @@ static int filter_buffers(prt_ctx* c) {
     HIPCHK(c, c->frame.dn_g.first_use(c->npix));
     return PRT_OK;
 }
-// the two buffers of an npix-pixel history, on first use; anew: whatever it holds goes first (the record history at a new size)
+// the two buffers of an npix-pixel history, on first use, and with a temporal response its fast plane (two halves); anew: whatever it holds
+// goes first (the record history at a new size)
 static int history_buffers(prt_ctx* c, History& h, size_t npix, bool anew) {
     if (anew) h = History{};
     HIPCHK(c, h.planes.first_use(4 * npix));
     HIPCHK(c, h.guides.first_use(2 * npix));
+    if (c->response_on) HIPCHK(c, h.fast.first_use(2 * npix));
     return PRT_OK;
 }
 
@@ -142,7 +162,7 @@ extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatia
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = filter_buffers(c)) || (rc = history_buffers(c, c->frame.hist, c->npix, false))) return rc;
-    const TemporalHistory h = history_begin(c->frame.hist, c->npix);
+    const TemporalHistory h = history_begin(c, c->frame.hist, c->npix);
     float4* out = c->frame.dn + 2 * c->npix;
     // the context's motion plane when motion is on and the plane is the valid guides' own (prt.h)
     const float4* motion = (c->motion && c->frame.motion_valid) ? c->frame.motion : nullptr;
@@ -166,6 +186,40 @@ extern "C" int prt_reset_history(prt_ctx* c) {
     CTX_CHECK(c);
     c->frame.hist.valid = false;
     return PRT_OK;
+}
+
+// ---- temporal response (prt.h prt_set_temporal_response; pt_temporal.hip tm_clamp_kernel) ------------------------------------------------------
+extern "C" int prt_set_temporal_response(prt_ctx* c, const prt_temporal_response* r) {
+    CTX_CHECK(c);
+    if (r) {
+        if (r->fast_cap < 1 || r->radius < 1 || r->radius > 3 || !(r->k > 0.0f) || !std::isfinite(r->k))
+            return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_temporal_response: fast_cap must be >= 1, radius 1 .. 3 and k > 0 and finite");
+        if (c->cfg.view_option != PRT_VIEW_RESULTS)
+            return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_temporal_response: a debug view is not a picture to filter");
+        if (c->response_on && c->response.fast_cap == r->fast_cap && c->response.radius == r->radius && c->response.k == r->k) return PRT_OK;
+    } else if (!c->response_on) {
+        return PRT_OK;
+    }
+    // a change: the fast planes hold nothing the new setting could reproject, so both histories start over
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->frame.hist.valid = false;
+    c->ctx.rec_hist.valid = false;
+    c->response_on = r != nullptr;
+    c->response = r ? *r : prt_temporal_response{};
+    c->response._pad = 0;
+    if (!r) { c->frame.hist.fast.reset(); c->ctx.rec_hist.fast.reset(); }
+    return PRT_OK;
+}
+
+extern "C" int prt_read_response(prt_ctx* c, float* out4) {
+    CTX_CHECK(c);
+    if (!out4 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_response: bad arguments");
+    if (!c->response_on) return fail(c, PRT_ERR_NOT_READY, "prt_read_response: no temporal response is set (prt_set_temporal_response)");
+    if (!c->frame.hist.valid || !c->frame.hist.fast) return fail(c, PRT_ERR_NOT_READY, "prt_read_response: the history is empty (prt_denoise_temporal)");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    return read_response_planes(c, c->frame.hist, c->npix, out4);
 }
 
 // ---- denoiser inputs as records (prt.h prt_export_denoise_inputs, prt_denoise_records; pt_records.hip) ---------------------------------------
@@ -233,7 +287,7 @@ static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params
     c->ctx.rec_hist_w = W; c->ctx.rec_hist_h = H;
     DevCamera dc;
     make_dev_camera(*cam, dc);
-    const TemporalHistory h = history_begin(rh, npix);
+    const TemporalHistory h = history_begin(c, rh, npix);
     launch_denoise_temporal_var(fb, guides, W, H, p, *t, dc, h, buf0, buf1, g, out, c->stream, static_cast<const float4*>(device_motion));
     HIPCHK(c, hipGetLastError());
     if (int rc = history_commit(c, rh, guides, npix, dc)) return rc;
@@ -284,4 +338,17 @@ extern "C" int prt_read_records_history(prt_ctx* c, int width, int height, float
     int rc = prt_synchronize(c);
     if (rc) return rc;
     return read_history_planes(c, c->ctx.rec_hist, (size_t)width * (size_t)height, out8);
+}
+
+extern "C" int prt_read_records_response(prt_ctx* c, int width, int height, float* out4) {
+    CTX_CHECK(c);
+    if (!out4 || width < 1 || height < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_response: bad arguments");
+    if (!c->response_on) return fail(c, PRT_ERR_NOT_READY, "prt_read_records_response: no temporal response is set (prt_set_temporal_response)");
+    if (!c->ctx.rec_hist.valid || !c->ctx.rec_hist.planes || !c->ctx.rec_hist.fast)
+        return fail(c, PRT_ERR_NOT_READY, "prt_read_records_response: the record history is empty (prt_denoise_records_temporal)");
+    if (width != c->ctx.rec_hist_w || height != c->ctx.rec_hist_h)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_response: the record history has another size");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    return read_response_planes(c, c->ctx.rec_hist, (size_t)width * (size_t)height, out4);
 }

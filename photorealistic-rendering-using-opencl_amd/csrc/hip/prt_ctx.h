@@ -19,9 +19,11 @@ using namespace prt;
 
 // what a temporal call carries to the next one.  planes holds two halves of {c, n} and {m1, m2, v, 0} planes (half cur is the last call's,
 // the other one is written by the next call: a flip of cur swaps them), guides the guides of the last call; cam its camera.  A history
-// without one of its buffers is empty: only history_commit, which needs both, sets valid
+// without one of its buffers is empty: only history_commit, which needs both, sets valid.  fast (prt_set_temporal_response): two halves of one
+// {f.rgb, took the history branch} plane, flipped by the same cur; allocated by the first temporal call made with the setting on, it lives and
+// dies with the history and is dropped when the setting goes off
 struct History {
-    DevBuf<float4> planes, guides;
+    DevBuf<float4> planes, guides, fast;
     int cur = 0;
     bool valid = false;
     DevCamera cam{};
@@ -189,6 +191,8 @@ struct prt_ctx {
     DevScene sc{};                                 // what the kernels take: the scene's scalars, and the pointers bind() fills
     DevState S{};
     bool motion = false;                           // prt_set_motion
+    bool response_on = false;                      // prt_set_temporal_response: the setting in force, of both histories
+    prt_temporal_response response{};
     bool have_scene = false, have_cam = false, have_size = false;
     bool state_undefined = false;   // a render call failed half-way (prt_render_spp's abort path): pixels may be ahead of the launch windows
                                     // (run-ahead leads in the state) -- the state is unusable until prt_reset / prt_write_state

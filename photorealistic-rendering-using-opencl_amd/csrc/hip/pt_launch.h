@@ -83,6 +83,12 @@ struct TemporalHistory {
     bool valid;
     float4* cn;                     // written by this call
     float4* m;
+    // prt_set_temporal_response: the fast history {f.rgb, took the history branch} of the previous call (read) and of this one (written),
+    // and the setting.  fast null = off: today's reprojection alone, and none of the others is read
+    const float4* fast_prev = nullptr;
+    float4* fast = nullptr;
+    uint32_t fast_cap = 0, radius = 0;
+    float k = 0.0f;
 };
 void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
                              const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,

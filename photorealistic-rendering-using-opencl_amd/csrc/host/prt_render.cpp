@@ -7,7 +7,8 @@
 // "-denoise" writes the picture through prt_denoise (guides of "-guide-spp K" samples, default 4; with -adaptive the variance comes from
 // the stats plane); "-guides-out base" writes base_albedo.pfm, base_normal.pfm and base_depth.pfm.  "-orbit-frames F -orbit-yaw RAD"
 // renders F frames along a yaw orbit (InteractiveCamera::changeYaw by RAD between frames), each -spp fresh paths after a prt_reset, guides and
-// prt_denoise_temporal -- the loop of a moving camera -- and writes the last one.  "-filter none|box|tent|gaussian|blackman-harris
+// prt_denoise_temporal -- the loop of a moving camera -- and writes the last one; "-response FASTCAP,RADIUS,K" runs that loop with
+// prt_set_temporal_response on.  "-filter none|box|tent|gaussian|blackman-harris
 // [-filter-radius R]" renders through prt_set_pixel_filter (antialiasing; every mode above honours it).
 #include <cstdio>
 #include <cstdlib>
@@ -102,6 +103,8 @@ int main(int argc, char** argv) {
     std::string guides_out;                                        // -guides-out base: base_{albedo,normal,depth}.pfm
     unsigned orbit_frames = 0;                                     // -orbit-frames F: F frames through prt_denoise_temporal ...
     float orbit_yaw = 0.0f;                                        // -orbit-yaw RAD: ... RAD of yaw apart
+    bool response = false;                                         // -response FASTCAP,RADIUS,K: prt_set_temporal_response for the orbit's frames
+    prt_temporal_response resp = {PRT_RESPONSE_DEFAULT_FAST_CAP, PRT_RESPONSE_DEFAULT_RADIUS, PRT_RESPONSE_DEFAULT_K, 0};
     std::string filter = "none";                                   // -filter NAME: the pixel filter (prt_set_pixel_filter)
     float filter_radius = PRT_FILTER_DEFAULT_RADIUS;               // -filter-radius R
     bool pick = false;                                             // -pick X,Y: print the hit of that pixel (prt_cast_pixels) and render nothing
@@ -131,6 +134,10 @@ int main(int argc, char** argv) {
         else if (a == "-guides-out") guides_out = next();
         else if (a == "-orbit-frames") orbit_frames = (unsigned)std::atoi(next());
         else if (a == "-orbit-yaw") orbit_yaw = (float)std::atof(next());
+        else if (a == "-response") {
+            if (std::sscanf(next(), "%u,%u,%f", &resp.fast_cap, &resp.radius, &resp.k) != 3) { std::fprintf(stderr, "-response: needs FASTCAP,RADIUS,K\n"); return 2; }
+            response = true;
+        }
         else if (a == "-filter") filter = next();
         else if (a == "-filter-radius") filter_radius = (float)std::atof(next());
         else if (a == "-pick") {
@@ -217,6 +224,7 @@ int main(int argc, char** argv) {
             const size_t npix = (size_t)window_width * window_height;
             orbit_rgba.resize(npix * 4);
             orbit_ldr.resize(npix * 4);
+            if (response) CHECK(prt_set_temporal_response(ctx, &resp));
             for (unsigned f = 0; f < orbit_frames; ++f) {
                 if (f) {
                     ic.changeYaw(orbit_yaw);

@@ -73,7 +73,8 @@ def denoise_on_rank0(renderer, height, width, world, dist, cam=None, temporal=Fa
     camera).  motion=True (needs temporal=True and Renderer.set_motion on every rank): every rank also exports its motion plane
     (Renderer.export_motion) and sends both as one (rows, width, 20) tile -- still one collective --, which rank 0 splits into the two
     contiguous buffers of prt_denoise_records_temporal_motion.  params: the keywords of Renderer.denoise / denoise_temporal.  Returns the (height, width, 4) float32 tensor on rank 0's device,
-    None on the other ranks.  The bits are those of prt_denoise on one whole-frame context."""
+    None on the other ranks.  The bits are those of prt_denoise on one whole-frame context.  A temporal response
+    (Renderer.set_temporal_response) needs no argument here: the setting is rank 0's context's, whose record history the call uses."""
     import torch
     if temporal and cam is None:
         raise ValueError("denoise_on_rank0: temporal=True needs the frame's camera")
