@@ -316,10 +316,72 @@ class Renderer:
         if rc:
             raise PrtError("prt_create failed (%d): %s" % (rc, self.lib.prt_last_global_error().decode()))
         self.width = self.height = self.rows = 0
+        # what upload_scene and the set_* calls keep of the scene: the sizes the arrays of later calls are checked against
+        self.triangle_count = self.mesh_count = self.bvh_node_count = 0
+        self._skin = self._morph = None                    # (n_bones, has normals), (n_targets, has normals)
+        self._policy = False
 
     def _chk(self, rc, what):
         if rc:
             raise PrtError("%s failed (%d): %s" % (what, rc, self.lib.prt_last_error(self.ctx).decode()), rc)
+
+    def _arg(self, a, count, what, wait=True):
+        """(pointer or None, is_device) of one float32 array argument of at least `count` elements: None and a numpy array are the host
+        door's, a tensor on this context's device (wait: work queued on torch's current stream is waited for) and an integer address the
+        device door's"""
+        if a is None:
+            return None, False
+        if isinstance(a, np.ndarray):
+            h = np.ascontiguousarray(a, dtype=np.float32)
+            if h.size < count:
+                raise ValueError("%s: needs float32 arrays of at least %d elements" % (what, count))
+            return h.ctypes.data_as(C.c_void_p), False     # (the pointer keeps a converted copy alive)
+        if wait and hasattr(a, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(a.device).synchronize()
+        return self._device_ptr(a, count, what), True
+
+    def _through(self, name, arrays, *tail):
+        """prt_X(ctx, arrays..., tail...) through its host door `name` or its device door `name`_device: the first of `arrays`, (array, least
+        size) pairs, decides, and the others go with it (None is NULL through either).  A first array that is a tensor is the one whose
+        stream is waited for: the call's tensors are on one device"""
+        what, ptrs, device = name[4:], [], None
+        for a, count in arrays:
+            p, d = self._arg(a, count, what, device is None)
+            if device is None:
+                device = d
+            elif p is not None and d != device:
+                raise ValueError("%s: the arrays must all be host arrays or all be on the device" % what)
+            ptrs.append(p)
+        if device:
+            name += "_device"
+        self._chk(getattr(self.lib, name)(self.ctx, *ptrs, *tail), name)
+
+    @staticmethod
+    def _mode(rebuild):
+        """PRT_POSE_* of a `rebuild` argument: False, True, or the number itself"""
+        return _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
+
+    def _refresh_node_count(self, mode=None):
+        """the node count of a tree that may be a new one: after a rebuild (mode None: rebuild_bvh itself), and after a refit under a rebuild
+        policy"""
+        if mode is None or mode == _capi.POSE_REBUILD or self._policy:
+            count = C.c_uint32(0)
+            self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
+            self.bvh_node_count = int(count.value)
+
+    def _read(self, name, shape, dtype, *head):
+        """a read-back prt_X(ctx, head..., out) into a new array"""
+        out = np.zeros(shape, dtype=dtype)
+        self._chk(getattr(self.lib, name)(self.ctx, *head, out.ctypes.data_as(C.c_void_p)), name)
+        return out
+
+    def _read_deformed(self, name, with_normals):
+        """prt_read_posed / prt_read_morphed: (vertices, normals or None) float32 [3T, 4]"""
+        v = np.zeros((3 * self.triangle_count, 4), dtype=np.float32)
+        n = np.zeros_like(v) if with_normals else None
+        self._chk(getattr(self.lib, name)(self.ctx, v.ctypes.data_as(C.c_void_p), None if n is None else n.ctypes.data_as(C.c_void_p)), name)
+        return v, n
 
     def upload_scene(self, scene):
         desc = scene.desc if isinstance(scene, HostScene) else scene
@@ -335,30 +397,16 @@ class Renderer:
         """prt_update_vertices / prt_update_vertices_device: new vertices (and normals; None keeps the uploaded ones) for the uploaded scene,
         the tree refitted on the device (prt.h).  Both float32 [3T, 4] in the layout of SceneDesc.  numpy arrays take the host entry point;
         torch tensors on this context's device (work queued on torch's current stream is waited for) or device addresses the device one"""
-        floats = 12 * getattr(self, "triangle_count", 0)
-        if isinstance(vertices, np.ndarray) or vertices is None:
-            v = None if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32)
-            n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32)
-            if (v is not None and v.size < floats) or (n is not None and n.size < floats):
-                raise ValueError("update_vertices: needs float32 arrays of at least %d elements" % floats)
-            self._chk(self.lib.prt_update_vertices(self.ctx, None if v is None else v.ctypes.data_as(C.c_void_p),
-                                                   None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_update_vertices")
-            self._after_pose(_capi.POSE_REFIT)
-            return
-        if hasattr(vertices, "data_ptr"):
-            import torch
-            torch.cuda.current_stream(vertices.device).synchronize()
-        pv = self._device_ptr(vertices, floats, "update_vertices")
-        pn = None if normals is None else self._device_ptr(normals, floats, "update_vertices")
-        self._chk(self.lib.prt_update_vertices_device(self.ctx, pv, pn), "prt_update_vertices_device")
-        self._after_pose(_capi.POSE_REFIT)
+        floats = 12 * self.triangle_count
+        self._through("prt_update_vertices", [(vertices, floats), (normals, floats)])
+        self._refresh_node_count(_capi.POSE_REFIT)
 
     def update_primitives(self, meshes, device=False, count=None):
         """prt_update_primitives / prt_update_primitives_device: the prt_mesh records (256 bytes each, all object_count[7] of them, in the
         uploaded order) of the moved spheres, SDF primitives and quads into the uploaded scene (prt.h).  Host door: the Mesh array of a
         HostScene.desc (a ctypes array or pointer), or a numpy array / view of count x 256 bytes.  device=True, a torch tensor or an integer
         address: the device door (count x 256 bytes, 16-byte aligned; work queued on torch's current stream is waited for)"""
-        count = int(getattr(self, "mesh_count", 0)) if count is None else int(count)     # (count: the uploaded scene's, unless given)
+        count = self.mesh_count if count is None else int(count)     # (count: the uploaded scene's, unless given)
         nbytes = count * C.sizeof(_capi.Mesh)
         if hasattr(meshes, "data_ptr"):
             import torch
@@ -384,31 +432,14 @@ class Renderer:
 
     def read_bvh_bounds(self):
         """prt_read_bvh_bounds: float32 [bvh_node_count, 6] = min_x max_x min_y max_y min_z max_z per node of the uploaded tree, in its numbering"""
-        out = np.zeros((getattr(self, "bvh_node_count", 0), 6), dtype=np.float32)
-        self._chk(self.lib.prt_read_bvh_bounds(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_bvh_bounds")
-        return out
+        return self._read("prt_read_bvh_bounds", (self.bvh_node_count, 6), np.float32)
 
     def rebuild_bvh(self, vertices, normals=None, max_leaf=0):
         """prt_rebuild_bvh / prt_rebuild_bvh_device: new vertices (and normals; None carries the current ones over) and a new Morton-order tree
         over all T triangles, built on the device (prt.h).  Arguments as update_vertices; max_leaf 1 .. 64, 0 = the library's default"""
-        floats = 12 * getattr(self, "triangle_count", 0)
-        if isinstance(vertices, np.ndarray) or vertices is None:
-            v = None if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32)
-            n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32)
-            if (v is not None and v.size < floats) or (n is not None and n.size < floats):
-                raise ValueError("rebuild_bvh: needs float32 arrays of at least %d elements" % floats)
-            self._chk(self.lib.prt_rebuild_bvh(self.ctx, None if v is None else v.ctypes.data_as(C.c_void_p),
-                                               None if n is None else n.ctypes.data_as(C.c_void_p), int(max_leaf)), "prt_rebuild_bvh")
-        else:
-            if hasattr(vertices, "data_ptr"):
-                import torch
-                torch.cuda.current_stream(vertices.device).synchronize()
-            pv = self._device_ptr(vertices, floats, "rebuild_bvh")
-            pn = None if normals is None else self._device_ptr(normals, floats, "rebuild_bvh")
-            self._chk(self.lib.prt_rebuild_bvh_device(self.ctx, pv, pn, int(max_leaf)), "prt_rebuild_bvh_device")
-        count = C.c_uint32(0)
-        self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
-        self.bvh_node_count = int(count.value)
+        floats = 12 * self.triangle_count
+        self._through("prt_rebuild_bvh", [(vertices, floats), (normals, floats)], int(max_leaf))
+        self._refresh_node_count()
 
     def set_smooth_normals(self, groups, n_groups=None, weighting="unit", crease_cos=LOADER_CREASE_COS):
         """prt_set_smooth_normals: the smoothing topology of the uploaded mesh -- groups uint32 [3T], one id per corner (weld_corners gives the
@@ -418,8 +449,8 @@ class Renderer:
             self._chk(self.lib.prt_set_smooth_normals(self.ctx, None, 0, 0, C.c_float(0.0)), "prt_set_smooth_normals")
             return
         g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
-        if g.size < 3 * getattr(self, "triangle_count", 0):
-            raise ValueError("set_smooth_normals: needs %d group ids" % (3 * getattr(self, "triangle_count", 0)))
+        if g.size < 3 * self.triangle_count:
+            raise ValueError("set_smooth_normals: needs %d group ids" % (3 * self.triangle_count))
         if isinstance(weighting, str):
             if weighting not in NORMALS_WEIGHTINGS:
                 raise ValueError("unknown weighting %r (one of %s)" % (weighting, ", ".join(NORMALS_WEIGHTINGS)))
@@ -431,9 +462,7 @@ class Renderer:
 
     def read_normals(self):
         """prt_read_normals: float32 [3T, 4], the current normal records in corner order (lane 3 = 0; zeros for a triangle no leaf holds)"""
-        out = np.zeros((3 * getattr(self, "triangle_count", 0), 4), dtype=np.float32)
-        self._chk(self.lib.prt_read_normals(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_normals")
-        return out
+        return self._read("prt_read_normals", (3 * self.triangle_count, 4), np.float32)
 
     def set_skin(self, rest_vertices, rest_normals=None, bone_index=None, bone_weight=None, n_bones=0):
         """prt_set_skin: the rest pose (float32 [3T, 4]; rest_normals None = no normals are posed) and the influences of every corner
@@ -443,7 +472,7 @@ class Renderer:
             self._chk(self.lib.prt_set_skin(self.ctx, None), "prt_set_skin")
             self._skin = None
             return
-        corners = 3 * getattr(self, "triangle_count", 0)
+        corners = 3 * self.triangle_count
         v = np.ascontiguousarray(rest_vertices, dtype=np.float32)
         n = None if rest_normals is None else np.ascontiguousarray(rest_normals, dtype=np.float32)
         b = None if bone_index is None else np.ascontiguousarray(bone_index, dtype=np.uint16)
@@ -459,28 +488,13 @@ class Renderer:
         """prt_pose / prt_pose_device: the mesh posed on the device from n_bones 3x4 row-major matrices (float32 [n_bones, 12] or [n_bones, 3, 4]),
         then refitted (rebuild False) or rebuilt (rebuild True, max_leaf as rebuild_bvh).  A numpy array takes the host door; a torch tensor
         on this context's device (work queued on torch's current stream is waited for) or a device address the device door"""
-        mode = _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
-        floats = 12 * (self._skin[0] if getattr(self, "_skin", None) else 0)
-        if isinstance(matrices, np.ndarray) or matrices is None:
-            m = None if matrices is None else np.ascontiguousarray(matrices, dtype=np.float32)
-            if m is not None and m.size < floats:
-                raise ValueError("pose: needs a float32 array of at least %d elements" % floats)
-            self._chk(self.lib.prt_pose(self.ctx, None if m is None else m.ctypes.data_as(C.c_void_p), mode, int(max_leaf)), "prt_pose")
-        else:
-            if hasattr(matrices, "data_ptr"):
-                import torch
-                torch.cuda.current_stream(matrices.device).synchronize()
-            self._chk(self.lib.prt_pose_device(self.ctx, self._device_ptr(matrices, floats, "pose"), mode, int(max_leaf)), "prt_pose_device")
-        self._after_pose(mode)
+        mode = self._mode(rebuild)
+        self._through("prt_pose", [(matrices, 12 * self._skin[0] if self._skin else 0)], mode, int(max_leaf))
+        self._refresh_node_count(mode)
 
     def read_posed(self):
         """prt_read_posed: (vertices, normals) float32 [3T, 4] of the last pose, accepted or refused; normals None for a skin without rest normals"""
-        corners = 3 * getattr(self, "triangle_count", 0)
-        with_normals = bool(getattr(self, "_skin", None) and self._skin[1])
-        v = np.zeros((corners, 4), dtype=np.float32)
-        n = np.zeros((corners, 4), dtype=np.float32) if with_normals else None
-        self._chk(self.lib.prt_read_posed(self.ctx, v.ctypes.data_as(C.c_void_p), None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_read_posed")
-        return v, n
+        return self._read_deformed("prt_read_posed", bool(self._skin and self._skin[1]))
 
     def set_morph_targets(self, base_vertices, base_normals=None, targets=None):
         """prt_set_morph_targets: the base mesh (float32 [3T, 4]; base_normals None = no normals are morphed) and the targets, a list of
@@ -491,7 +505,7 @@ class Renderer:
             self._chk(self.lib.prt_set_morph_targets(self.ctx, None), "prt_set_morph_targets")
             self._morph = None
             return
-        corners = 3 * getattr(self, "triangle_count", 0)
+        corners = 3 * self.triangle_count
         v = np.ascontiguousarray(base_vertices, dtype=np.float32)
         n = None if base_normals is None else np.ascontiguousarray(base_normals, dtype=np.float32)
         if any(a is not None and a.size < 4 * corners for a in (v, n)):
@@ -514,71 +528,29 @@ class Renderer:
         self._chk(self.lib.prt_set_morph_targets(self.ctx, C.byref(desc)), "prt_set_morph_targets")
         self._morph = (len(keep), n is not None)
 
-    def _weights_ptr(self, weights, what):
-        """(pointer, is_device) of the frame's morph weights: a numpy array or None (host door), a tensor or a device address (device door)"""
-        count = self._morph[0] if getattr(self, "_morph", None) else 0
-        if isinstance(weights, np.ndarray) or weights is None:
-            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
-            if w is not None and w.size < count:
-                raise ValueError("%s: needs a float32 array of at least %d weights" % (what, count))
-            return w, False
-        if hasattr(weights, "data_ptr"):
-            import torch
-            torch.cuda.current_stream(weights.device).synchronize()
-        return self._device_ptr(weights, count, what), True
-
-    def _after_pose(self, mode):
-        """the node count of a tree that may be a new one: after a rebuild, and after a refit under a rebuild policy"""
-        if mode == _capi.POSE_REBUILD or getattr(self, "_policy", False):
-            count = C.c_uint32(0)
-            self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
-            self.bvh_node_count = int(count.value)
-
     def morph(self, weights, rebuild=False, max_leaf=0):
         """prt_morph / prt_morph_device: the mesh morphed on the device from one float32 weight per target, then refitted (rebuild False) or
         rebuilt (rebuild True, max_leaf as rebuild_bvh).  A numpy array takes the host door; a torch tensor on this context's device (work
         queued on torch's current stream is waited for) or a device address the device door"""
-        mode = _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
-        w, device = self._weights_ptr(weights, "morph")
-        if device:
-            self._chk(self.lib.prt_morph_device(self.ctx, w, mode, int(max_leaf)), "prt_morph_device")
-        else:
-            self._chk(self.lib.prt_morph(self.ctx, None if w is None else w.ctypes.data_as(C.c_void_p), mode, int(max_leaf)), "prt_morph")
-        self._after_pose(mode)
+        mode = self._mode(rebuild)
+        self._through("prt_morph", [(weights, self._morph[0] if self._morph else 0)], mode, int(max_leaf))
+        self._refresh_node_count(mode)
 
     def pose_morphed(self, matrices, weights, rebuild=False, max_leaf=0):
         """prt_pose_morphed / prt_pose_morphed_device: the mesh morphed and then posed by the skin, in one kernel; matrices as pose(), weights
         as morph().  Two numpy arrays (or None) take the host door, two tensors or device addresses the device door; read_posed() returns
         the result"""
-        mode = _capi.POSE_REBUILD if rebuild is True else _capi.POSE_REFIT if rebuild is False else int(rebuild)
-        host = [isinstance(a, np.ndarray) or a is None for a in (matrices, weights)]
-        if host[0] != host[1]:
+        if (isinstance(matrices, np.ndarray) or matrices is None) != (isinstance(weights, np.ndarray) or weights is None):
             raise ValueError("pose_morphed: matrices and weights must both be host arrays or both be on the device")
-        w, device = self._weights_ptr(weights, "pose_morphed")
-        floats = 12 * (self._skin[0] if getattr(self, "_skin", None) else 0)
-        if device:
-            if hasattr(matrices, "data_ptr"):
-                import torch
-                torch.cuda.current_stream(matrices.device).synchronize()
-            self._chk(self.lib.prt_pose_morphed_device(self.ctx, self._device_ptr(matrices, floats, "pose_morphed"), w, mode, int(max_leaf)),
-                      "prt_pose_morphed_device")
-        else:
-            m = None if matrices is None else np.ascontiguousarray(matrices, dtype=np.float32)
-            if m is not None and m.size < floats:
-                raise ValueError("pose_morphed: needs a float32 array of at least %d matrix elements" % floats)
-            self._chk(self.lib.prt_pose_morphed(self.ctx, None if m is None else m.ctypes.data_as(C.c_void_p),
-                                                None if w is None else w.ctypes.data_as(C.c_void_p), mode, int(max_leaf)), "prt_pose_morphed")
-        self._after_pose(mode)
+        mode = self._mode(rebuild)
+        self._through("prt_pose_morphed", [(matrices, 12 * self._skin[0] if self._skin else 0), (weights, self._morph[0] if self._morph else 0)],
+                      mode, int(max_leaf))
+        self._refresh_node_count(mode)
 
     def read_morphed(self):
         """prt_read_morphed: (vertices, normals) float32 [3T, 4] of the last morph(), accepted or refused; normals None for a set without
         base normals"""
-        corners = 3 * getattr(self, "triangle_count", 0)
-        with_normals = bool(getattr(self, "_morph", None) and self._morph[1])
-        v = np.zeros((corners, 4), dtype=np.float32)
-        n = np.zeros((corners, 4), dtype=np.float32) if with_normals else None
-        self._chk(self.lib.prt_read_morphed(self.ctx, v.ctypes.data_as(C.c_void_p), None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_read_morphed")
-        return v, n
+        return self._read_deformed("prt_read_morphed", bool(self._morph and self._morph[1]))
 
     def read_bvh(self):
         """prt_read_bvh: (nodes [node_count] of _capi.BVH_NODE_DTYPE, primitive_indices uint64 [T]): the current tree in the reference's layout,
@@ -586,7 +558,7 @@ class Renderer:
         count = C.c_uint32(0)
         self._chk(self.lib.prt_read_bvh(self.ctx, None, C.byref(count), None), "prt_read_bvh")
         nodes = np.zeros(int(count.value), dtype=np.dtype(_capi.BVH_NODE_DTYPE))
-        prims = np.zeros(getattr(self, "triangle_count", 0), dtype=np.uint64)
+        prims = np.zeros(self.triangle_count, dtype=np.uint64)
         if nodes.size:
             self._chk(self.lib.prt_read_bvh(self.ctx, nodes.ctypes.data_as(C.c_void_p), C.byref(count), prims.ctypes.data_as(C.c_void_p)), "prt_read_bvh")
         return nodes, prims
@@ -706,9 +678,7 @@ class Renderer:
 
     def read_adaptive_stats(self):
         """the adaptive plane: float32 [rows * width, 2] = {l, s2} per pixel, framebuffer order"""
-        out = np.zeros((self.rows * self.width, 2), dtype=np.float32)
-        self._chk(self.lib.prt_read_adaptive_stats(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_adaptive_stats")
-        return out
+        return self._read("prt_read_adaptive_stats", (self.rows * self.width, 2), np.float32)
 
     def adaptive_report(self):
         rep = AdaptiveReport()
@@ -721,9 +691,7 @@ class Renderer:
 
     def read_guides(self):
         """the guide plane: float32 [rows, width, 8] = {albedo.rgb, coverage, normal.xyz, depth} per pixel, framebuffer order"""
-        out = np.zeros((self.rows, self.width, 8), dtype=np.float32)
-        self._chk(self.lib.prt_read_guides(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_guides")
-        return out
+        return self._read("prt_read_guides", (self.rows, self.width, 8), np.float32)
 
     def set_motion(self, enable=True):
         """prt_set_motion: the guide renders also write the motion plane of the deforming mesh (update_vertices) and denoise_temporal
@@ -732,9 +700,7 @@ class Renderer:
 
     def read_motion(self):
         """the motion plane of the last render_guides: float32 [rows, width, 4] = {D.xyz, m} per pixel, framebuffer order (prt.h)"""
-        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
-        self._chk(self.lib.prt_read_motion(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_motion")
-        return out
+        return self._read("prt_read_motion", (self.rows, self.width, 4), np.float32)
 
     def export_motion(self, ptr_or_tensor):
         """prt_export_motion: the motion plane of this context's frame part into device memory: a [rows, width, 4] float32 tensor on this
@@ -778,9 +744,7 @@ class Renderer:
 
     def read_history(self):
         """the temporal history: float32 [rows, width, 8] = {c.rgb, n, m1, m2, v, 0} per pixel, framebuffer order"""
-        out = np.zeros((self.rows, self.width, 8), dtype=np.float32)
-        self._chk(self.lib.prt_read_history(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_history")
-        return out
+        return self._read("prt_read_history", (self.rows, self.width, 8), np.float32)
 
     def reset_history(self):
         self._chk(self.lib.prt_reset_history(self.ctx), "prt_reset_history")
@@ -799,9 +763,7 @@ class Renderer:
     def read_response(self):
         """the temporal response of the frame history: float32 [rows, width, 4] = {f.rgb, flag} per pixel, framebuffer order; flag 0 no
         history, 1 history kept, 2 clamped"""
-        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
-        self._chk(self.lib.prt_read_response(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_response")
-        return out
+        return self._read("prt_read_response", (self.rows, self.width, 4), np.float32)
 
     @staticmethod
     def _device_ptr(t, floats, what):
@@ -866,17 +828,13 @@ class Renderer:
     def read_records_history(self, width, height):
         """the record history of denoise_records_temporal()'s width x height frame: float32 [height, width, 8] = {c.rgb, n, m1, m2, v, 0} per
         pixel, framebuffer order (read_history()'s twin)"""
-        width, height = int(width), int(height)
-        out = np.zeros((max(height, 0), max(width, 0), 8), dtype=np.float32)      # a size below 1 is the library's to refuse
-        self._chk(self.lib.prt_read_records_history(self.ctx, width, height, out.ctypes.data_as(C.c_void_p)), "prt_read_records_history")
-        return out
+        width, height = int(width), int(height)                # (a size below 1 is the library's to refuse)
+        return self._read("prt_read_records_history", (max(height, 0), max(width, 0), 8), np.float32, width, height)
 
     def read_records_response(self, width, height):
         """read_response()'s twin for the record history: float32 [height, width, 4] = {f.rgb, flag} per pixel"""
         width, height = int(width), int(height)
-        out = np.zeros((max(height, 0), max(width, 0), 4), dtype=np.float32)      # a size below 1 is the library's to refuse
-        self._chk(self.lib.prt_read_records_response(self.ctx, width, height, out.ctypes.data_as(C.c_void_p)), "prt_read_records_response")
-        return out
+        return self._read("prt_read_records_response", (max(height, 0), max(width, 0), 4), np.float32, width, height)
 
     def set_pixel_filter(self, kind="tent", radius=None):
         """prt_set_pixel_filter: antialiasing by filter importance sampling (prt.h).  kind: a name of PIXEL_FILTERS ("none", "box", "tent",
@@ -897,23 +855,17 @@ class Renderer:
         self._chk(self.lib.prt_synchronize(self.ctx), "prt_synchronize")
 
     def read_framebuffer(self):
-        out = np.zeros((self.rows, self.width, 4), dtype=np.float32)
-        self._chk(self.lib.prt_read_framebuffer(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_framebuffer")
-        return out
+        return self._read("prt_read_framebuffer", (self.rows, self.width, 4), np.float32)
 
     def tonemap_rgba8(self):
         """the reference's display transform (shaders/tonemapper.glsl) of the framebuffer, rows bottom-up"""
-        out = np.zeros((self.rows, self.width, 4), dtype=np.uint8)
-        self._chk(self.lib.prt_tonemap_rgba8(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_tonemap_rgba8")
-        return out
+        return self._read("prt_tonemap_rgba8", (self.rows, self.width, 4), np.uint8)
 
     def copy_framebuffer_to_device(self, device_ptr):
         self._chk(self.lib.prt_copy_framebuffer_to_device(self.ctx, C.c_void_p(device_ptr)), "prt_copy_framebuffer_to_device")
 
     def read_state(self):
-        out = np.zeros(self.rows * self.width, dtype=np.dtype(PATH_STATE_DTYPE))
-        self._chk(self.lib.prt_read_state(self.ctx, out.ctypes.data_as(C.c_void_p)), "prt_read_state")
-        return out
+        return self._read("prt_read_state", self.rows * self.width, np.dtype(PATH_STATE_DTYPE))
 
     def write_state(self, state):
         state = np.ascontiguousarray(state)

@@ -21,7 +21,7 @@ COMMON = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
 HOST_SOURCES = ["host/scene.cpp", "host/camera.cpp", "host/model_loader.cpp", "host/bvh.cpp", "host/hdr_loader.cpp", "host/host_capi.cpp"]
 # the render kernel is instantiated per compile-time material set in a file of its own (pt_inst_*.hip): they compile in parallel
 # (CORE_HIP_SOURCES: everything but the instance files -- what tools/build_variant.sh compiles, with the instances in one unit)
-CORE_HIP_SOURCES = ["hip/prt_api.cpp", "hip/prt_api_scene.cpp", "hip/prt_api_render.cpp", "hip/prt_api_denoise.cpp", "hip/prt_api_query.cpp", "hip/pt_pack.cpp", "hip/pt_kernels.hip",
+CORE_HIP_SOURCES = ["hip/prt_api.cpp", "hip/prt_api_scene.cpp", "hip/prt_api_deform.cpp", "hip/prt_api_render.cpp", "hip/prt_api_denoise.cpp", "hip/prt_api_query.cpp", "hip/pt_pack.cpp", "hip/pt_kernels.hip",
                     "hip/pt_denoise.hip", "hip/pt_temporal.hip", "hip/pt_records.hip", "hip/pt_filter.hip", "hip/pt_refit.hip", "hip/pt_normals.hip", "hip/pt_pose.hip", "hip/pt_morph.hip", "hip/pt_build.hip", "hip/pt_cost.hip", "hip/pt_prims.hip", "hip/pt_cast.hip", "hip/prt_build_id.cpp"]
 HIP_SOURCES = CORE_HIP_SOURCES + \
     ["hip/pt_inst_%s.hip" % k for k in ("light_diff", "coat", "rough_cond", "rough_diel", "generic", "sdf", "view", "view_sdf", "pick", "envis")] + \

@@ -2,7 +2,8 @@
 // Replaces the OpenCL host sequence of the reference's src/main.cpp (see prt.h for the
 // call-by-call mapping).  No CPU fallback: every entry point needs a HIP device.
 // This file: the context, the frame, camera, environment map, pixel filter, options, read-backs and selftests.  The scene calls are in
-// prt_api_scene.cpp, the render drivers in prt_api_render.cpp, the denoiser's in prt_api_denoise.cpp; prt_ctx.h is what they share.
+// prt_api_scene.cpp, what deforms the mesh for them (smooth normals, skin, morph targets) in prt_api_deform.cpp, the render drivers in
+// prt_api_render.cpp, the denoiser's in prt_api_denoise.cpp, the ray queries in prt_api_query.cpp; prt_ctx.h is what they share.
 #include <cstdlib>
 
 #include "prt_ctx.h"

@@ -1,15 +1,12 @@
-// prt_api_scene.cpp -- the scene calls of the C ABI (include/prt.h): upload, vertex updates with a refit, rebuilds, the tree's read-backs,
-// motion on / off, smooth normals, the skin and its poses, the morph targets and their morphs.
+// prt_api_scene.cpp -- the scene calls of the C ABI (include/prt.h): upload, the two entry paths of new vertices (update with a refit,
+// rebuild) with the normals they generate, the primitives, the tree's cost and rebuild policy, motion on / off and the tree's read-backs.
+// What produces vertices or normals for the two paths -- the smoothing topology, the skin, the morph targets -- is in prt_api_deform.cpp.
 #include <cmath>
-#include <new>
 #include <utility>
 
 #include "prt_ctx.h"
 #include "pt_build.h"
-#include "pt_normals.h"
-#include "pt_morph.h"
 #include "pt_pack.h"
-#include "pt_pose.h"
 #include "pt_refit.h"
 
 extern "C" int prt_upload_scene(prt_ctx* c, const prt_scene_desc* s) {
@@ -319,6 +316,23 @@ extern "C" int prt_update_primitives(prt_ctx* c, const prt_mesh* meshes, uint32_
     return prt_update_primitives_device(c, c->scene.stage_meshes, count);
 }
 
+// ---- the tree's read-backs (the caller has waited for the context's work: prt_synchronize) ---------------------------------------------------
+// the first n records of a device buffer
+template <typename T>
+static hipError_t download(const DevBuf<T>& src, size_t n, std::vector<T>& out) {
+    out.resize(n);
+    return n ? hipMemcpy(out.data(), src, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+}
+
+// the slot table of the current tree: the uploaded tree's is on the host, a rebuilt tree's on the device only -- that one comes into
+// `scratch`.  Null: the copy failed (prt_last_error says how)
+static const std::vector<uint32_t>* current_slot_vtx(prt_ctx* c, std::vector<uint32_t>& scratch) {
+    if (!c->scene.rebuilt) return &c->scene.slot_vtx;
+    const hipError_t e = download(c->scene.tree.slot_vtx, c->scene.n_slots, scratch);
+    if (e != hipSuccess) c->err = std::string("the slot table of the rebuilt tree: ") + hipGetErrorString(e);
+    return e == hipSuccess ? &scratch : nullptr;
+}
+
 extern "C" int prt_read_bvh_bounds(prt_ctx* c, float* bounds6) {
     CTX_CHECK(c);
     if (!c->have_scene) return fail(c, PRT_ERR_NOT_READY, "prt_read_bvh_bounds: no scene uploaded");
@@ -326,8 +340,8 @@ extern "C" int prt_read_bvh_bounds(prt_ctx* c, float* bounds6) {
     if (!c->scene.n_nodes) return PRT_OK;
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    std::vector<NodePair> pairs(c->sc.n_pairs);
-    if (!pairs.empty()) HIPCHK(c, hipMemcpy(pairs.data(), c->scene.tree.pairs, pairs.size() * sizeof(NodePair), hipMemcpyDeviceToHost));
+    std::vector<NodePair> pairs;
+    HIPCHK(c, download(c->scene.tree.pairs, c->sc.n_pairs, pairs));
     for (uint32_t i = 0; i < c->scene.n_nodes; ++i) {
         float* o = bounds6 + 6 * (size_t)i;
         const uint32_t at = c->scene.rebuilt ? i - 1u : c->scene.node_box[i];          // (a rebuilt tree: the children of pair k are nodes 2k + 1 and 2k + 2; i = 0 wraps to "none")
@@ -475,13 +489,14 @@ extern "C" int prt_read_bvh(prt_ctx* c, prt_bvh_node* nodes, uint32_t* node_coun
     int rc = prt_synchronize(c);
     if (rc) return rc;
     if (primitive_indices) {
-        std::vector<uint32_t> sv(c->scene.n_slots);
-        HIPCHK(c, hipMemcpy(sv.data(), c->scene.tree.slot_vtx, sv.size() * 4, hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < sv.size(); ++s) primitive_indices[s] = sv[s] / 3u;
+        std::vector<uint32_t> scratch;
+        const std::vector<uint32_t>* sv = current_slot_vtx(c, scratch);
+        if (!sv) return PRT_ERR_HIP;
+        for (size_t s = 0; s < sv->size(); ++s) primitive_indices[s] = (*sv)[s] / 3u;
     }
     if (!nodes) return PRT_OK;
-    std::vector<NodePair> pairs(c->sc.n_pairs);
-    if (!pairs.empty()) HIPCHK(c, hipMemcpy(pairs.data(), c->scene.tree.pairs, pairs.size() * sizeof(NodePair), hipMemcpyDeviceToHost));
+    std::vector<NodePair> pairs;
+    HIPCHK(c, download(c->scene.tree.pairs, c->sc.n_pairs, pairs));
     std::memset(nodes, 0, sizeof(prt_bvh_node) * (size_t)c->scene.n_nodes);
     HIPCHK(c, hipMemcpy(nodes[0].bounds, c->scene.tree.root, 6 * sizeof(float), hipMemcpyDeviceToHost));
     if (c->sc.root_is_leaf) {
@@ -513,287 +528,6 @@ extern "C" int prt_set_motion(prt_ctx* c, int enable) {
     return PRT_OK;
 }
 
-// ---- smooth shading normals regenerated from new vertices (prt.h prt_set_smooth_normals; pt_normals.hip) ---------------------------------------
-extern "C" int prt_set_smooth_normals(prt_ctx* c, const uint32_t* corner_group, uint32_t n_groups, uint32_t weighting, float crease_cos) {
-    CTX_CHECK(c);
-    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_smooth_normals: no scene with triangles uploaded");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!corner_group) {                                   // off: nothing of the scene changes, the buffers go
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->scene.smooth = Smooth{};
-        return PRT_OK;
-    }
-    // every refusal before anything of the topology in force is touched
-    if (n_groups == 0) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: n_groups is 0 (the topology in force stays)");
-    if (weighting != PRT_NORMALS_UNIT && weighting != PRT_NORMALS_AREA)
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: unknown weighting (the topology in force stays)");
-    if (!std::isfinite(crease_cos)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: crease_cos is not finite (the topology in force stays)");
-    const uint32_t T = c->scene.n_tris;
-    if (T > PRT_MAX_TRIANGLE_SLOTS)
-        return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_smooth_normals: more than PRT_MAX_TRIANGLE_SLOTS triangles (corners are addressed by 32-bit indices)");
-    std::vector<uint32_t> group_first, member_face;
-    bool ids_ok = false;
-    try { ids_ok = normals_group_table(corner_group, T, n_groups, group_first, member_face); }
-    catch (const std::bad_alloc&) { return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_smooth_normals: no host memory for a table of n_groups + 1 entries (the topology in force stays)"); }
-    if (!ids_ok) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_smooth_normals: a group id >= n_groups (the topology in force stays)");
-    // everything a generation will ever need, into buffers of their own: a failure here leaves the topology in force as it was
-    const size_t corners = 3 * (size_t)T;
-    Smooth sm;
-    hipError_t e = sm.group.alloc(corners);
-    if (e == hipSuccess) e = hipMemcpy(sm.group, corner_group, corners * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = sm.first.upload(group_first);
-    if (e == hipSuccess) e = sm.member.upload(member_face);
-    if (e == hipSuccess) e = sm.face_f.alloc(T);
-    if (e == hipSuccess && weighting == PRT_NORMALS_AREA) e = sm.face_r.alloc(T);
-    if (e == hipSuccess) e = sm.nrm.alloc(corners * 4);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        c->err = std::string("prt_set_smooth_normals: ") + hipGetErrorString(e);
-        return PRT_ERR_HIP;
-    }
-    sm.weighting = weighting; sm.crease = crease_cos;
-    sm.on = true;
-    c->scene.smooth = std::move(sm);
-    return PRT_OK;
-}
-
-// ---- the mesh posed on the device from the frame's bone matrices (prt.h prt_set_skin / prt_pose; pt_pose.hip) ----------------------------------
-extern "C" int prt_set_skin(prt_ctx* c, const prt_skin* skin) {
-    CTX_CHECK(c);
-    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_skin: no scene with triangles uploaded");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!skin) {                                           // off: nothing of the scene changes, the buffers go
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->scene.skin = Skin{};
-        return PRT_OK;
-    }
-    // every refusal before anything of the skin in force is touched
-    const uint32_t T = c->scene.n_tris;
-    if (T > PRT_MAX_TRIANGLE_SLOTS)
-        return fail(c, PRT_ERR_UNSUPPORTED, "prt_set_skin: more than PRT_MAX_TRIANGLE_SLOTS triangles (corners are addressed by 32-bit indices)");
-    if (const char* m = pose_skin_error(skin->rest_vertices, skin->rest_normals, skin->bone_index, skin->bone_weight, skin->n_bones, T))
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, std::string("prt_set_skin: ") + m + " (the skin in force stays)");
-    // everything a pose will ever need, into buffers of their own: a failure here leaves the skin in force as it was
-    const size_t corners = 3 * (size_t)T;
-    Skin sk;
-    auto put = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
-    hipError_t e = sk.rest_v.alloc(corners * 4);
-    if (e == hipSuccess) e = put(sk.rest_v, skin->rest_vertices, corners * 16);
-    if (e == hipSuccess && skin->rest_normals) e = sk.rest_n.alloc(corners * 4);
-    if (e == hipSuccess && skin->rest_normals) e = put(sk.rest_n, skin->rest_normals, corners * 16);
-    if (e == hipSuccess) e = sk.index.alloc(corners * 4);
-    if (e == hipSuccess) e = put(sk.index, skin->bone_index, corners * 8);
-    if (e == hipSuccess) e = sk.weight.alloc(corners * 4);
-    if (e == hipSuccess) e = put(sk.weight, skin->bone_weight, corners * 16);
-    if (e == hipSuccess) e = sk.mats.alloc(12 * (size_t)skin->n_bones);
-    if (e == hipSuccess) e = sk.out_v.alloc(corners * 4);
-    if (e == hipSuccess && skin->rest_normals) e = sk.out_n.alloc(corners * 4);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        c->err = std::string("prt_set_skin: ") + hipGetErrorString(e);
-        return PRT_ERR_HIP;
-    }
-    sk.n_bones = skin->n_bones;
-    sk.on = true;
-    c->scene.skin = std::move(sk);
-    return PRT_OK;
-}
-
-// the refusals of both doors that come before the path the pose enters
-static int pose_checks(prt_ctx* c, const void* matrices, uint32_t mode, const char* who) {
-    const std::string w(who);
-    if (!c->have_scene || !c->scene.skin.on) return fail(c, PRT_ERR_NOT_READY, w + ": no skin set (prt_set_skin)");
-    if (!matrices) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null matrices");
-    if (mode != PRT_POSE_REFIT && mode != PRT_POSE_REBUILD) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown mode (the scene is unchanged)");
-    return PRT_OK;
-}
-
-extern "C" int prt_pose_device(prt_ctx* c, const void* d_matrices, uint32_t mode, uint32_t max_leaf) {
-    CTX_CHECK(c);
-    if (int rc = pose_checks(c, d_matrices, mode, "prt_pose_device")) return rc;
-    if (!aligned16(d_matrices)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_pose_device: the matrices must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    Skin& sk = c->scene.skin;
-    // the posed arrays into the skin's own buffers: only scratch of the context is written.  Everything else -- the finite-vertex check, the
-    // snapshot, the guides, the tile orders, the generated normals -- is the entered path's, over these buffers as over a caller's
-    PoseTables t;
-    t.rest_v = sk.rest_v; t.rest_n = sk.rest_n; t.bone_index = sk.index; t.bone_weight = sk.weight; t.n_tris = c->scene.n_tris;
-    launch_pose(t, static_cast<const float*>(d_matrices), sk.out_v, sk.out_n, c->stream);
-    HIPCHK(c, hipGetLastError());
-    sk.posed = true;
-    const float* n = (c->scene.smooth.on || !sk.rest_n) ? nullptr : sk.out_n.get();
-    const int rc = mode == PRT_POSE_REFIT ? prt_update_vertices_device(c, sk.out_v, n) : prt_rebuild_bvh_device(c, sk.out_v, n, max_leaf);
-    if (rc) (void)hipStreamSynchronize(c->stream);         // (a path that refuses before its own wait: the caller's matrices may be reused on return)
-    return rc;
-}
-
-extern "C" int prt_pose(prt_ctx* c, const float* matrices, uint32_t mode, uint32_t max_leaf) {
-    CTX_CHECK(c);
-    if (int rc = pose_checks(c, matrices, mode, "prt_pose")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    Skin& sk = c->scene.skin;
-    HIPCHK(c, hipMemcpyAsync(sk.mats, matrices, 12 * (size_t)sk.n_bones * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    return prt_pose_device(c, sk.mats, mode, max_leaf);
-}
-
-extern "C" int prt_read_posed(prt_ctx* c, float* vertices, float* normals) {
-    CTX_CHECK(c);
-    const Skin& sk = c->scene.skin;
-    if (!c->have_scene || !sk.on || !sk.posed) return fail(c, PRT_ERR_NOT_READY, "prt_read_posed: no pose yet (prt_set_skin, prt_pose)");
-    if (!vertices) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_posed: null vertices");
-    if (normals && !sk.rest_n) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_posed: the skin has no rest normals: normals must be NULL");
-    int rc = prt_synchronize(c);
-    if (rc) return rc;
-    const size_t bytes = 3 * (size_t)c->scene.n_tris * 4 * sizeof(float);
-    HIPCHK(c, hipMemcpy(vertices, sk.out_v, bytes, hipMemcpyDeviceToHost));
-    if (normals) HIPCHK(c, hipMemcpy(normals, sk.out_n, bytes, hipMemcpyDeviceToHost));
-    return PRT_OK;
-}
-
-// ---- the mesh morphed on the device from the frame's target weights, alone or in front of the skin (prt.h prt_set_morph_targets; pt_morph.hip) --
-extern "C" int prt_set_morph_targets(prt_ctx* c, const prt_morph_set* set) {
-    CTX_CHECK(c);
-    if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_morph_targets: no scene with triangles uploaded");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!set) {                                            // off: nothing of the scene changes, the buffers go
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->scene.morph = MorphSet{};
-        return PRT_OK;
-    }
-    // every refusal before anything of the set in force is touched
-    const uint32_t T = c->scene.n_tris;
-    int code = PRT_OK;
-    if (const char* m = morph_set_error(set, T, &code)) return fail(c, code, std::string("prt_set_morph_targets: ") + m + " (the set in force stays)");
-    // everything a morph will ever need, into buffers of their own: a failure here leaves the set in force as it was
-    MorphTable tab;
-    try {
-        morph_build_table(set, T, tab);
-    } catch (const std::bad_alloc&) {
-        return fail(c, PRT_ERR_UNSUPPORTED,"prt_set_morph_targets: out of host memory for the per-corner table (the set in force stays)");
-    }
-    const size_t corners = 3 * (size_t)T;
-    const bool nrm = set->base_normals != nullptr;
-    MorphSet ms;
-    auto put = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    hipError_t e = ms.base_v.alloc(corners * 4);
-    if (e == hipSuccess) e = put(ms.base_v, set->base_vertices, corners * 16);
-    if (e == hipSuccess && nrm) e = ms.base_n.alloc(corners * 4);
-    if (e == hipSuccess && nrm) e = put(ms.base_n, set->base_normals, corners * 16);
-    if (e == hipSuccess) e = ms.offset.upload(tab.offset);
-    if (e == hipSuccess) e = ms.entry_p.alloc(tab.entry_p.size() * 4);
-    if (e == hipSuccess) e = put(ms.entry_p, tab.entry_p.data(), tab.entry_p.size() * 16);
-    if (e == hipSuccess && nrm) e = ms.entry_n.alloc(tab.entry_n.size() * 4);
-    if (e == hipSuccess && nrm) e = put(ms.entry_n, tab.entry_n.data(), tab.entry_n.size() * 16);
-    if (e == hipSuccess) e = ms.weights.alloc(set->n_targets);
-    if (e == hipSuccess) e = ms.out_v.alloc(corners * 4);
-    if (e == hipSuccess && nrm) e = ms.out_n.alloc(corners * 4);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        c->err = std::string("prt_set_morph_targets: ") + hipGetErrorString(e);
-        return PRT_ERR_HIP;
-    }
-    ms.n_targets = set->n_targets;
-    ms.on = true;
-    c->scene.morph = std::move(ms);
-    return PRT_OK;
-}
-
-// the refusals of the four doors that come before the path the morph enters
-static int morph_checks(prt_ctx* c, const void* weights, uint32_t mode, const char* who) {
-    const std::string w(who);
-    if (!c->have_scene || !c->scene.morph.on) return fail(c, PRT_ERR_NOT_READY, w + ": no morph targets set (prt_set_morph_targets)");
-    if (!weights) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": null weights");
-    if (mode != PRT_POSE_REFIT && mode != PRT_POSE_REBUILD) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": unknown mode (the scene is unchanged)");
-    return PRT_OK;
-}
-
-static MorphTables morph_tables(const prt_ctx* c) {
-    const MorphSet& ms = c->scene.morph;
-    MorphTables t;
-    t.base_v = ms.base_v; t.base_n = ms.base_n; t.offset = ms.offset; t.entry_p = ms.entry_p; t.entry_n = ms.entry_n; t.n_tris = c->scene.n_tris;
-    return t;
-}
-
-extern "C" int prt_morph_device(prt_ctx* c, const void* d_weights, uint32_t mode, uint32_t max_leaf) {
-    CTX_CHECK(c);
-    if (int rc = morph_checks(c, d_weights, mode, "prt_morph_device")) return rc;
-    if (!aligned16(d_weights)) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_morph_device: the weights must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    MorphSet& ms = c->scene.morph;
-    // the morphed arrays into the set's own buffers; everything else is the entered path's, over these buffers as over a caller's
-    launch_morph(morph_tables(c), static_cast<const float*>(d_weights), ms.out_v, ms.out_n, c->stream);
-    HIPCHK(c, hipGetLastError());
-    ms.morphed = true;
-    const float* n = (c->scene.smooth.on || !ms.base_n) ? nullptr : ms.out_n.get();
-    const int rc = mode == PRT_POSE_REFIT ? prt_update_vertices_device(c, ms.out_v, n) : prt_rebuild_bvh_device(c, ms.out_v, n, max_leaf);
-    if (rc) (void)hipStreamSynchronize(c->stream);         // (a path that refuses before its own wait: the caller's weights may be reused on return)
-    return rc;
-}
-
-extern "C" int prt_morph(prt_ctx* c, const float* weights, uint32_t mode, uint32_t max_leaf) {
-    CTX_CHECK(c);
-    if (int rc = morph_checks(c, weights, mode, "prt_morph")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    MorphSet& ms = c->scene.morph;
-    HIPCHK(c, hipMemcpyAsync(ms.weights, weights, (size_t)ms.n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    return prt_morph_device(c, ms.weights, mode, max_leaf);
-}
-
-// ... and of the fused doors: what is not ready first, then the arguments
-static int pose_morphed_checks(prt_ctx* c, const void* matrices, const void* weights, uint32_t mode, const char* who) {
-    const std::string w(who);
-    if (!c->have_scene || !c->scene.morph.on) return fail(c, PRT_ERR_NOT_READY, w + ": no morph targets set (prt_set_morph_targets)");
-    if (!c->scene.skin.on) return fail(c, PRT_ERR_NOT_READY, w + ": no skin set (prt_set_skin)");
-    if (int rc = morph_checks(c, weights, mode, who)) return rc;
-    if (int rc = pose_checks(c, matrices, mode, who)) return rc;
-    if (!c->scene.skin.rest_n != !c->scene.morph.base_n) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": exactly one of the skin and the morph set has normals");
-    return PRT_OK;
-}
-
-extern "C" int prt_pose_morphed_device(prt_ctx* c, const void* d_matrices, const void* d_weights, uint32_t mode, uint32_t max_leaf) {
-    CTX_CHECK(c);
-    if (int rc = pose_morphed_checks(c, d_matrices, d_weights, mode, "prt_pose_morphed_device")) return rc;
-    Skin& sk = c->scene.skin;
-    if (!aligned16(d_matrices) || !aligned16(d_weights))
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_pose_morphed_device: the matrices and the weights must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    // into the skin's posed buffers, as a pose: prt_read_posed returns them
-    PoseTables t;
-    t.rest_v = nullptr; t.rest_n = nullptr; t.bone_index = sk.index; t.bone_weight = sk.weight; t.n_tris = c->scene.n_tris;
-    launch_pose_morphed(morph_tables(c), t, static_cast<const float*>(d_matrices), static_cast<const float*>(d_weights), sk.out_v, sk.out_n, c->stream);
-    HIPCHK(c, hipGetLastError());
-    sk.posed = true;
-    const float* n = (c->scene.smooth.on || !sk.rest_n) ? nullptr : sk.out_n.get();
-    const int rc = mode == PRT_POSE_REFIT ? prt_update_vertices_device(c, sk.out_v, n) : prt_rebuild_bvh_device(c, sk.out_v, n, max_leaf);
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    return rc;
-}
-
-extern "C" int prt_pose_morphed(prt_ctx* c, const float* matrices, const float* weights, uint32_t mode, uint32_t max_leaf) {
-    CTX_CHECK(c);
-    if (int rc = pose_morphed_checks(c, matrices, weights, mode, "prt_pose_morphed")) return rc;
-    Skin& sk = c->scene.skin;
-    MorphSet& ms = c->scene.morph;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(sk.mats, matrices, 12 * (size_t)sk.n_bones * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ms.weights, weights, (size_t)ms.n_targets * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    return prt_pose_morphed_device(c, sk.mats, ms.weights, mode, max_leaf);
-}
-
-extern "C" int prt_read_morphed(prt_ctx* c, float* vertices, float* normals) {
-    CTX_CHECK(c);
-    const MorphSet& ms = c->scene.morph;
-    if (!c->have_scene || !ms.on || !ms.morphed) return fail(c, PRT_ERR_NOT_READY, "prt_read_morphed: no morph yet (prt_set_morph_targets, prt_morph)");
-    if (!vertices) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_morphed: null vertices");
-    if (normals && !ms.base_n) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_morphed: the set has no base normals: normals must be NULL");
-    int rc = prt_synchronize(c);
-    if (rc) return rc;
-    const size_t bytes = 3 * (size_t)c->scene.n_tris * 4 * sizeof(float);
-    HIPCHK(c, hipMemcpy(vertices, ms.out_v, bytes, hipMemcpyDeviceToHost));
-    if (normals) HIPCHK(c, hipMemcpy(normals, ms.out_n, bytes, hipMemcpyDeviceToHost));
-    return PRT_OK;
-}
-
 extern "C" int prt_read_normals(prt_ctx* c, float* normals) {
     CTX_CHECK(c);
     if (!c->have_scene) return fail(c, PRT_ERR_NOT_READY, "prt_read_normals: no scene uploaded");
@@ -804,15 +538,12 @@ extern "C" int prt_read_normals(prt_ctx* c, float* normals) {
     if (!c->scene.n_slots) return PRT_OK;
     int rc = prt_synchronize(c);
     if (rc) return rc;
-    // the slot table: the uploaded tree's on the host, a rebuilt tree's on the device only
-    std::vector<uint32_t> sv;
-    if (c->scene.rebuilt) {
-        sv.resize(c->scene.n_slots);
-        HIPCHK(c, hipMemcpy(sv.data(), c->scene.tree.slot_vtx, sv.size() * 4, hipMemcpyDeviceToHost));
-    }
-    const std::vector<uint32_t>& slot_vtx = c->scene.rebuilt ? sv : c->scene.slot_vtx;
-    std::vector<TriNrm> tn(c->scene.n_slots);
-    HIPCHK(c, hipMemcpy(tn.data(), c->scene.tree.tri_nrm, tn.size() * sizeof(TriNrm), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> scratch;
+    const std::vector<uint32_t>* sv = current_slot_vtx(c, scratch);
+    if (!sv) return PRT_ERR_HIP;
+    const std::vector<uint32_t>& slot_vtx = *sv;
+    std::vector<TriNrm> tn;
+    HIPCHK(c, download(c->scene.tree.tri_nrm, c->scene.n_slots, tn));
     for (size_t s = 0; s < slot_vtx.size() && s < tn.size(); ++s) {
         const size_t fv = slot_vtx[s];
         if (fv + 3 > 3 * T) continue;

@@ -36,10 +36,11 @@ public:
     }
     hipError_t first_use(size_t n) { return p_ ? hipSuccess : alloc(n); }          // allocated once, with the owner's size
     hipError_t reserve(size_t n) { return cap_ >= n ? hipSuccess : alloc(n); }     // grown on demand, contents not kept
-    hipError_t upload(const std::vector<T>& src) {
-        const hipError_t e = alloc(src.size());
-        return e != hipSuccess || src.empty() ? e : hipMemcpy(p_, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    hipError_t upload(const T* src, size_t n) {                                    // exactly n records, filled from the host
+        const hipError_t e = alloc(n);
+        return e != hipSuccess || !n ? e : hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice);
     }
+    hipError_t upload(const std::vector<T>& src) { return upload(src.data(), src.size()); }
 
 private:
     T* p_ = nullptr;

@@ -4,7 +4,8 @@
 Every context renders; with --calls all (the default) it also goes through what allocates lazily and by lifetime: a vertex update and a
 rebuild (host doors: the staging buffers, the refit tables, the spare tree set and the build's scratch), smoothing and motion on and off
 (the topology, both snapshots), a primitive update, a host ray cast, a temporal denoise and a records denoise, and two more uploads of other
-triangle counts (the primitives alone, then the mesh again) with a rebuild behind them.  Prints the free-memory delta every 100 contexts and
+triangle counts (the primitives alone, then the mesh again) with a rebuild behind them, and a skin and a morph set with one pose of a morph
+(host door: both sets' buffers and staging) before both are turned off.  Prints the free-memory delta every 100 contexts and
 one JSON line at the end.  A tool, not a test: free memory on a shared card is another tenant's business as much as ours.
 
     python tools/leak_check.py [--contexts 300] [--calls all|render]
@@ -29,6 +30,11 @@ bare = prt.SceneDesc.from_buffer_copy(bytes(scene.desc))           # the primiti
 bare.triangle_count, bare.bvh_node_count = 0, 0
 rays = np.zeros((64, 8), dtype=np.float32); rays[:, 1] = 1.0; rays[:, 2] = 3.0; rays[:, 3] = 20.0; rays[:, 6] = -1.0
 records = torch.zeros((H, W, 16), dtype=torch.float32, device="cuda")
+bone_index = (np.arange(4 * len(v0)).reshape(-1, 4) % 4).astype(np.uint16)          # four bones, every corner under all of them
+bone_weight = np.full((len(v0), 4), 0.25, dtype=np.float32)
+matrices = np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0.01, 0, 0, 1, 0], dtype=np.float32), (4, 1))
+target = (np.arange(len(v0), dtype=np.uint32), v1 - v0, None)                       # one dense target
+weights = np.array([0.5], dtype=np.float32)
 
 
 def everything(r):
@@ -49,6 +55,11 @@ def everything(r):
     r.upload_scene(bare)
     r.upload_scene(scene)
     r.rebuild_bvh(v1, None)
+    r.set_skin(v0, n0, bone_index, bone_weight, 4)
+    r.set_morph_targets(v0, n0, [target])
+    r.pose_morphed(matrices, weights)
+    r.set_skin(None)
+    r.set_morph_targets(None)
 
 
 torch.cuda.synchronize()
