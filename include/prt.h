@@ -867,7 +867,29 @@ int prt_read_posed(prt_ctx* ctx, float* vertices /* float4[3T] */, float* normal
  * prt_pose_morphed / prt_pose_morphed_device: additionally PRT_ERR_NOT_READY without a skin, PRT_ERR_INVALID_ARGUMENT for null or misaligned
  *   matrices and when exactly one of the skin and the set has normals.
  * prt_read_morphed: the morphed buffers of the last prt_morph, accepted or refused by its path: float4[3T] each.  PRT_ERR_NOT_READY before
- *   the first one of the set in force; PRT_ERR_INVALID_ARGUMENT for null `vertices`, or for non-null `normals` with a set without base normals. */
+ *   the first one of the set in force; PRT_ERR_INVALID_ARGUMENT for null `vertices`, or for non-null `normals` with a set without base normals.
+ * prt_set_morph_targets_layout: the same set under one of two table layouts; the morphed bits are the same under both, for every set and
+ *   every weight vector, NaN and infinity included.  prt_set_morph_targets(ctx, set) is prt_set_morph_targets_layout(ctx, set,
+ *   PRT_MORPH_LAYOUT_CORNERS).  A context has one set in force: either call replaces it, either call with set == NULL turns it off.  The
+ *   refusals are prt_set_morph_targets', and an unknown layout is PRT_ERR_INVALID_ARGUMENT (tested after the scene, before set == NULL; the set
+ *   in force stays).  The five morph doors and prt_read_morphed run over whichever table the set in force has.
+ *   PRT_MORPH_LAYOUT_CORNERS: the per-corner table above.  A lane walks its corner's entries; a record holds its target's number, so it is
+ *     loaded before its weight is known: the cost of a morph is that of all E entries whatever the weights are.
+ *   PRT_MORPH_LAYOUT_PLANES: block b is corners 64 b .. 64 b + 63 (B = ceil(3T / 64) blocks, the last one may be ragged); a PLANE exists for
+ *     every pair (target t, block b) where t lists at least one corner of b, the planes ordered by (b, t).  A plane is a 16-byte head
+ *     {target, 0, the 64-bit mask of the listed lanes} and three rows of 64 floats (dp.x, dp.y, dp.z of lane l = c - 64 b; +0 on unlisted
+ *     lanes), with base normals three more for dn.  A wave owns a block and reads each row as 256 contiguous bytes; a plane whose target's
+ *     weight is zero costs the wave its head and its weight, two scalar loads, and no vector traffic: the cost of a morph is that of the
+ *     planes of the targets with a non-zero weight.  A lane the mask does not list is left alone (nothing is added: a -0 stays -0, a NaN
+ *     weight reaches listed lanes only), exactly as a corner without that entry is under CORNERS.
+ * prt_get_morph_report: layout, n_targets, E = entries (the sum of n_entries), P = planes (0 under CORNERS) and table_bytes, the device bytes
+ *   of the delta tables alone, with nrm = 1 with base normals, else 0:   CORNERS  4 (3T + 1) + 16 E (1 + nrm);
+ *   PLANES  4 (B + 1) + 16 P + 768 P (1 + nrm).  (Either layout: 48 bytes per triangle of base and 48 of morphed vertices, with base normals
+ *   48 + 48 more, and 4 per target, as above.)  The fill E / (64 P) is what to choose by: planes suit targets that are dense within the
+ *   blocks they touch (a plane at fill f streams 12 / f + 0.25 / f bytes per entry against 16; but only those of active targets), corners
+ *   suit scattered ones.  PRT_ERR_NOT_READY without a set in force, PRT_ERR_INVALID_ARGUMENT for a null `out`; it changes nothing. */
+#define PRT_MORPH_LAYOUT_CORNERS 0u   /* prt_set_morph_targets' table: a CSR over corners */
+#define PRT_MORPH_LAYOUT_PLANES  1u   /* per (target, block of 64 corners) one plane */
 typedef struct prt_morph_target {
     const uint32_t* corner;      /* n_entries corner indices (c = 3i + k), STRICTLY ascending, each < 3T */
     const float*    d_position;  /* float4[n_entries], xyz used */
@@ -888,6 +910,15 @@ int prt_morph_device(prt_ctx* ctx, const void* d_weights /* 16-byte aligned */, 
 int prt_pose_morphed(prt_ctx* ctx, const float* matrices, const float* weights, uint32_t mode, uint32_t max_leaf);
 int prt_pose_morphed_device(prt_ctx* ctx, const void* d_matrices, const void* d_weights, uint32_t mode, uint32_t max_leaf);
 int prt_read_morphed(prt_ctx* ctx, float* vertices /* float4[3T] */, float* normals /* float4[3T], may be NULL */);
+int prt_set_morph_targets_layout(prt_ctx* ctx, const prt_morph_set* set /* NULL = off */, uint32_t layout /* PRT_MORPH_LAYOUT_* */);
+typedef struct prt_morph_report {
+    uint32_t layout;       /* of the set in force */
+    uint32_t n_targets;
+    uint64_t entries;      /* sum of n_entries over the targets */
+    uint64_t planes;       /* 0 for CORNERS */
+    uint64_t table_bytes;  /* device bytes of the delta tables alone (formulas above) */
+} prt_morph_report;
+int prt_get_morph_report(prt_ctx* ctx, prt_morph_report* out);
 
 /* Deforming geometry: the cost of the current tree, measured on the device, and a rule that rebuilds a refitted tree once it has degraded (no
  * counterpart in the reference).  A refit keeps the topology, so a mesh that moves far from the pose its tree was built for renders through

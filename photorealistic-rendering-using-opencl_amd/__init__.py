@@ -496,11 +496,16 @@ class Renderer:
         """prt_read_posed: (vertices, normals) float32 [3T, 4] of the last pose, accepted or refused; normals None for a skin without rest normals"""
         return self._read_deformed("prt_read_posed", bool(self._skin and self._skin[1]))
 
-    def set_morph_targets(self, base_vertices, base_normals=None, targets=None):
+    def set_morph_targets(self, base_vertices, base_normals=None, targets=None, layout="corners"):
         """prt_set_morph_targets: the base mesh (float32 [3T, 4]; base_normals None = no normals are morphed) and the targets, a list of
         (corner uint32 [n], d_position float32 [n, 4], d_normal float32 [n, 4] or None) with strictly ascending corners.  From then on
         morph() moves the mesh from one weight per target, and pose_morphed() morphs in front of the skin (prt.h).  base_vertices None turns
-        it off"""
+        it off.  layout "corners" (prt_set_morph_targets' per-corner table) or "planes" (prt_set_morph_targets_layout: one plane per target
+        and block of 64 corners, a morph costs the planes of the targets with a non-zero weight); morph_report() tells which suits a set"""
+        if isinstance(layout, str):
+            if layout not in _capi.MORPH_LAYOUTS:
+                raise ValueError("unknown layout %r (one of %s)" % (layout, ", ".join(_capi.MORPH_LAYOUTS)))
+            layout = _capi.MORPH_LAYOUTS[layout]
         if base_vertices is None:
             self._chk(self.lib.prt_set_morph_targets(self.ctx, None), "prt_set_morph_targets")
             self._morph = None
@@ -525,8 +530,21 @@ class Renderer:
         for t, (corner, dp, dn, entries) in enumerate(keep):
             records[t] = _capi.MorphTarget(ptr(corner), ptr(dp), ptr(dn), entries, 0)
         desc = _capi.MorphSet(ptr(v), ptr(n), records if targets is not None else None, len(keep), 0)
-        self._chk(self.lib.prt_set_morph_targets(self.ctx, C.byref(desc)), "prt_set_morph_targets")
+        if layout == _capi.MORPH_LAYOUT_CORNERS:
+            self._chk(self.lib.prt_set_morph_targets(self.ctx, C.byref(desc)), "prt_set_morph_targets")
+        else:
+            self._chk(self.lib.prt_set_morph_targets_layout(self.ctx, C.byref(desc), int(layout)), "prt_set_morph_targets_layout")
         self._morph = (len(keep), n is not None)
+
+    def morph_report(self):
+        """prt_get_morph_report of the set in force: dict of layout ("corners" / "planes"), n_targets, entries, planes, table_bytes (the device
+        bytes of the delta tables alone) and fill = entries / (64 planes) (None under "corners"): planes suit a set whose fill is high"""
+        rep = _capi.MorphReport()
+        self._chk(self.lib.prt_get_morph_report(self.ctx, C.byref(rep)), "prt_get_morph_report")
+        names = {v: k for k, v in _capi.MORPH_LAYOUTS.items()}
+        return {"layout": names.get(int(rep.layout), int(rep.layout)), "n_targets": int(rep.n_targets), "entries": int(rep.entries),
+                "planes": int(rep.planes), "table_bytes": int(rep.table_bytes),
+                "fill": rep.entries / (64.0 * rep.planes) if rep.planes else None}
 
     def morph(self, weights, rebuild=False, max_leaf=0):
         """prt_morph / prt_morph_device: the mesh morphed on the device from one float32 weight per target, then refitted (rebuild False) or

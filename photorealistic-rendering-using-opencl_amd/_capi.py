@@ -144,6 +144,15 @@ class MorphSet(C.Structure):
                 ("_pad", C.c_uint32)]
 
 
+# prt_set_morph_targets_layout / prt_get_morph_report: PRT_MORPH_LAYOUT_* and prt_morph_report
+MORPH_LAYOUT_CORNERS, MORPH_LAYOUT_PLANES = 0, 1
+MORPH_LAYOUTS = {"corners": MORPH_LAYOUT_CORNERS, "planes": MORPH_LAYOUT_PLANES}
+
+
+class MorphReport(C.Structure):
+    _fields_ = [("layout", C.c_uint32), ("n_targets", C.c_uint32), ("entries", C.c_uint64), ("planes", C.c_uint64), ("table_bytes", C.c_uint64)]
+
+
 # prt_set_rebuild_policy / prt_get_rebuild_report: prt_rebuild_policy and prt_rebuild_report of include/prt.h
 class RebuildPolicy(C.Structure):
     _fields_ = [("limit", C.c_float), ("max_leaf", C.c_uint32)]
@@ -187,6 +196,8 @@ PRT_API = [
     ("prt_pose_morphed", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("prt_pose_morphed_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("prt_read_morphed", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("prt_set_morph_targets_layout", C.c_int, [C.c_void_p, C.POINTER(MorphSet), C.c_uint32]),
+    ("prt_get_morph_report", C.c_int, [C.c_void_p, C.POINTER(MorphReport)]),
     ("prt_set_camera", C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     ("prt_upload_envmap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("prt_resize", C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -76,6 +76,8 @@ static MorphTables morph_tables(const prt_ctx* c) {
     const MorphSet& ms = c->scene.morph;
     MorphTables t;
     t.base_v = ms.base_v; t.base_n = ms.base_n; t.offset = ms.offset; t.entry_p = ms.entry_p; t.entry_n = ms.entry_n; t.n_tris = c->scene.n_tris;
+    t.planes = ms.layout == PRT_MORPH_LAYOUT_PLANES;
+    t.block_first = ms.block_first; t.plane_head = ms.plane_head.get(); t.plane_p = ms.plane_p; t.plane_n = ms.plane_n;
     return t;
 }
 
@@ -175,20 +177,25 @@ extern "C" int prt_read_posed(prt_ctx* c, float* vertices, float* normals) {
 }
 
 // ---- the mesh morphed on the device from the frame's target weights, alone or in front of the skin (prt.h prt_set_morph_targets; pt_morph.hip) --
-extern "C" int prt_set_morph_targets(prt_ctx* c, const prt_morph_set* set) {
+extern "C" int prt_set_morph_targets_layout(prt_ctx* c, const prt_morph_set* set, uint32_t layout) {
     CTX_CHECK(c);
     if (!c->have_scene || c->scene.n_tris == 0) return fail(c, PRT_ERR_NOT_READY, "prt_set_morph_targets: no scene with triangles uploaded");
+    if (layout != PRT_MORPH_LAYOUT_CORNERS && layout != PRT_MORPH_LAYOUT_PLANES)
+        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_set_morph_targets_layout: unknown layout (the set in force stays)");
     HIPCHK(c, hipSetDevice(c->device));
     if (!set) return turn_off(c, c->scene.morph);
     // every refusal before anything of the set in force is touched
     const uint32_t T = c->scene.n_tris;
     int code = PRT_OK;
     if (const char* m = morph_set_error(set, T, &code)) return fail(c, code, std::string("prt_set_morph_targets: ") + m + " (the set in force stays)");
+    const bool planes = layout == PRT_MORPH_LAYOUT_PLANES;
     MorphTable tab;
+    MorphPlanes pl;
     try {
-        morph_build_table(set, T, tab);
+        if (planes) morph_build_planes(set, T, pl); else morph_build_table(set, T, tab);
     } catch (const std::bad_alloc&) {
-        return fail(c, PRT_ERR_UNSUPPORTED,"prt_set_morph_targets: out of host memory for the per-corner table (the set in force stays)");
+        return fail(c, PRT_ERR_UNSUPPORTED, planes ? "prt_set_morph_targets: out of host memory for the plane table (the set in force stays)"
+                                                   : "prt_set_morph_targets: out of host memory for the per-corner table (the set in force stays)");
     }
     const size_t lanes = 4 * 3 * (size_t)T;                // of a float4 per corner
     const bool nrm = set->base_normals != nullptr;
@@ -196,16 +203,35 @@ extern "C" int prt_set_morph_targets(prt_ctx* c, const prt_morph_set* set) {
     Fresh f;
     f.upload(ms.base_v, set->base_vertices, lanes)
      .upload(ms.base_n, set->base_normals, lanes, nrm)
-     .upload(ms.offset, tab.offset.data(), tab.offset.size())
-     .upload(ms.entry_p, reinterpret_cast<const float*>(tab.entry_p.data()), 4 * tab.entry_p.size())
-     .upload(ms.entry_n, reinterpret_cast<const float*>(tab.entry_n.data()), 4 * tab.entry_n.size(), nrm)
+     .upload(ms.offset, tab.offset.data(), tab.offset.size(), !planes)
+     .upload(ms.entry_p, reinterpret_cast<const float*>(tab.entry_p.data()), 4 * tab.entry_p.size(), !planes)
+     .upload(ms.entry_n, reinterpret_cast<const float*>(tab.entry_n.data()), 4 * tab.entry_n.size(), nrm && !planes)
+     .upload(ms.block_first, pl.block_first.data(), pl.block_first.size(), planes)
+     .upload(ms.plane_head, reinterpret_cast<const uint4*>(pl.head.data()), pl.head.size(), planes)
+     .upload(ms.plane_p, pl.plane_p.data(), pl.plane_p.size(), planes)
+     .upload(ms.plane_n, pl.plane_n.data(), pl.plane_n.size(), nrm && planes)
      .alloc(ms.weights, set->n_targets)
      .alloc(ms.out_v, lanes)
      .alloc(ms.out_n, lanes, nrm);
     if (int rc = f.done(c, "prt_set_morph_targets")) return rc;
+    ms.layout = layout;
+    ms.entries = planes ? pl.entries : (uint64_t)tab.entry_p.size();
+    ms.planes = pl.head.size();
     ms.n_targets = set->n_targets;
     ms.on = true;
     c->scene.morph = std::move(ms);
+    return PRT_OK;
+}
+
+extern "C" int prt_set_morph_targets(prt_ctx* c, const prt_morph_set* set) { return prt_set_morph_targets_layout(c, set, PRT_MORPH_LAYOUT_CORNERS); }
+
+extern "C" int prt_get_morph_report(prt_ctx* c, prt_morph_report* out) {
+    CTX_CHECK(c);
+    const MorphSet& ms = c->scene.morph;
+    if (!c->have_scene || !ms.on) return fail(c, PRT_ERR_NOT_READY, "prt_get_morph_report: no morph targets set (prt_set_morph_targets)");
+    if (!out) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_get_morph_report: null out");
+    out->layout = ms.layout; out->n_targets = ms.n_targets; out->entries = ms.entries; out->planes = ms.planes;
+    out->table_bytes = morph_table_bytes(ms.layout, c->scene.n_tris, ms.entries, ms.planes, ms.base_n != nullptr);
     return PRT_OK;
 }
 

@@ -72,10 +72,17 @@ struct Skin {
 
 // prt_set_morph_targets (pt_morph.hip): the base mesh (float4[3T]; base_n empty for a set without normals), the per-corner table (offset
 // [3T + 1], one float4 per entry and, with normals, a second one), the frame's weights (one float per target: the host doors' staging) and
-// what prt_morph writes -- the morphed vertices and normals (float4[3T])
+// what prt_morph writes -- the morphed vertices and normals (float4[3T]).  Under PRT_MORPH_LAYOUT_PLANES the plane table takes the place of
+// the per-corner one (pt_morph.h: block_first [ceil(3T / 64) + 1], a 16-byte head and 3 x 64 floats per plane and, with normals, 3 x 64
+// more); entries and planes are the counts prt_get_morph_report returns
 struct MorphSet {
     DevBuf<float> base_v, base_n, entry_p, entry_n, weights, out_v, out_n;
     DevBuf<uint32_t> offset;
+    uint32_t layout = PRT_MORPH_LAYOUT_CORNERS;
+    DevBuf<uint32_t> block_first;
+    DevBuf<uint4> plane_head;
+    DevBuf<float> plane_p, plane_n;
+    uint64_t entries = 0, planes = 0;
     uint32_t n_targets = 0;
     bool on = false;
     bool morphed = false;                          // a prt_morph, accepted or refused, has written out_v (and out_n)

@@ -163,6 +163,13 @@ struct MorphTables {
     const float* entry_p;           // float4 per entry: {dp.x, dp.y, dp.z, the target's number as bits}
     const float* entry_n;           // float4 per entry: dn (not read without base_n)
     uint32_t n_tris;
+    // prt_set_morph_targets_layout with PRT_MORPH_LAYOUT_PLANES: `planes` is set, offset and the entries are null, and the table is per (block
+    // of 64 corners, target) one plane (pt_morph.h): block b owns planes block_first[b] .. block_first[b + 1], in ascending target order
+    bool planes = false;
+    const uint32_t* block_first = nullptr;    // ceil(3 n_tris / 64) + 1
+    const void* plane_head = nullptr;         // 16 bytes per plane: {target, 0, mask_lo, mask_hi}
+    const float* plane_p = nullptr;           // float[3][64] per plane: the x, y and z rows of dp, +0 on unlisted lanes
+    const float* plane_n = nullptr;           // the same for dn (not read without base_n)
 };
 // the morphed vertices into out_v and, with base normals, the morphed and renormalised normals into out_n (device, float4[3 n_tris] each,
 // 16-byte aligned) from `weights` (device, one float per target): one launch

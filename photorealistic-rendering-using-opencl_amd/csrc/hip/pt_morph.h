@@ -2,7 +2,7 @@
 // per-corner deltas of the targets + the frame's weights -> morphed vertices and normals, written as the formulas of prt.h.  Plain pointers
 // and __host__ __device__ inline functions only, as pt_pose.h, so that a host harness (tests/emu/morph_emu.cpp) runs the same code serially.
 // f32 operations in the order of prt.h, no contraction (build.py: -ffp-contract=off); sqrtf and / are the correctly rounded ones on both sides.
-// The host-only part below the body: the checks of prt_set_morph_targets and the builder of the per-corner table.
+// The host-only part below the body: the checks of prt_set_morph_targets and the builders of the per-corner table and of the plane table.
 #pragma once
 #include <stdint.h>
 
@@ -69,6 +69,100 @@ PT_MORPH_HD void pose_morphed_corner(const float* base_v, const float* base_n, c
     RefitQuad n{0.0f, 0.0f, 0.0f, 0.0f};
     if (base_n) n = reinterpret_cast<const RefitQuad*>(base_n)[c];
     morph_raw(offset, entry_p, base_n ? entry_n : nullptr, weights, c, p, n);
+    const RefitQuad wq = reinterpret_cast<const RefitQuad*>(bone_weight)[c];
+    const PoseIndex idx = reinterpret_cast<const PoseIndex*>(bone_index)[c];
+    pose_values(p, base_n != nullptr, [=]() { return n; }, wq, idx, matrices, c, out_v, out_n);
+}
+
+// ---- the plane table (prt.h PRT_MORPH_LAYOUT_PLANES) ---------------------------------------------------------------------------------------------
+// Block b is corners 64 b .. 64 b + 63; a plane exists for every (block b, target t) where t lists a corner of b, ordered by (b, t):
+// block_first[b] .. block_first[b + 1] are the planes of block b, in ascending t.  A plane is a head and three rows of 64 floats (with
+// normals three more): plane_p[192 u + 64 k + l] is component k of dp of lane l of plane u, +0 on a lane the mask does not list.  On the
+// device b is wave-uniform (one wave per block), so block_first, the head and the weight are scalar loads, the zero-weight test is a scalar
+// branch in front of the plane's rows, and a row is one 256-byte line of 64 lanes
+struct alignas(16) MorphPlaneHead { uint32_t target, zero, mask_lo, mask_hi; };
+typedef uint32_t MorphHeadWords __attribute__((ext_vector_type(4)));       // a head as it is loaded: x the target, z and w the mask
+constexpr uint32_t PT_MORPH_PLANE_FLOATS = 192u;
+// The loop takes the planes of a block PT_MORPH_TRIP at a time: the heads of a trip are asked for together, then their weights, then every
+// row of those with a non-zero weight, and only then is the first row used -- three waits for memory per trip, not per plane
+constexpr uint32_t PT_MORPH_TRIP = 4u;
+// the rows of one plane have been loaded into registers at this point of the program, whatever uses them later (the device only: the host
+// has no such choice to make).  Left to itself the compiler moves a row's load under the lane's mask bit and waits for it there
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PT_MORPH_LOADED(d) asm volatile("" : "+v"((d)[0]), "+v"((d)[1]), "+v"((d)[2]), "+v"((d)[3]), "+v"((d)[4]), "+v"((d)[5]))
+#else
+#define PT_MORPH_LOADED(d) ((void)(d))
+#endif
+
+// Lane l of block b: the loop of morph_raw over the planes of the block.  For a listed lane the operands and the order of the additions are
+// morph_raw's; for an unlisted one nothing is added (w * +0 would turn a -0 into +0 and a NaN weight into a NaN on every lane of the plane)
+PT_MORPH_HD void morph_raw_planes(const uint32_t* block_first, const MorphPlaneHead* plane_head, const float* plane_p, const float* plane_n,
+                                  const float* weights, uint32_t b, uint32_t l, RefitQuad& p, RefitQuad& n) {
+    const uint32_t first = block_first[b], end = block_first[b + 1];
+    for (uint32_t u0 = first; u0 < end; u0 += PT_MORPH_TRIP) {
+        // (a plane past the block's last one: the last one again, under a weight of zero)
+        // (a head is one 16-byte load: its mask is there before the rows are, not asked for after them)
+        MorphHeadWords h[PT_MORPH_TRIP];
+        float w[PT_MORPH_TRIP];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_MORPH_TRIP; ++j) h[j] = reinterpret_cast<const MorphHeadWords*>(plane_head)[u0 + j < end ? u0 + j : end - 1u];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_MORPH_TRIP; ++j) w[j] = weights[h[j].x];
+        uint32_t active = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < PT_MORPH_TRIP; ++j) {
+            if (u0 + j >= end) w[j] = 0.0f;
+            active |= w[j] == 0.0f ? 0u : 1u;               // (either sign; a NaN is not zero)
+        }
+        if (!active) continue;
+        float d[PT_MORPH_TRIP][6];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_MORPH_TRIP; ++j) {
+            for (int k = 0; k < 6; ++k) d[j][k] = 0.0f;
+            if (w[j] == 0.0f) continue;
+            const size_t row = (size_t)(u0 + j) * PT_MORPH_PLANE_FLOATS + l;         // 64-bit: 768 P bytes pass 4 GiB
+            d[j][0] = plane_p[row]; d[j][1] = plane_p[row + 64]; d[j][2] = plane_p[row + 128];
+            if (plane_n) { d[j][3] = plane_n[row]; d[j][4] = plane_n[row + 64]; d[j][5] = plane_n[row + 128]; }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < PT_MORPH_TRIP; ++j) PT_MORPH_LOADED(d[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < PT_MORPH_TRIP; ++j) {
+            if (w[j] == 0.0f) continue;
+            const uint64_t mask = (uint64_t)h[j].w << 32 | h[j].z;
+            const bool on = (mask >> l) & 1u;
+            const float wj = w[j];
+            p.x = on ? p.x + wj * d[j][0] : p.x; p.y = on ? p.y + wj * d[j][1] : p.y; p.z = on ? p.z + wj * d[j][2] : p.z;
+            if (plane_n) { n.x = on ? n.x + wj * d[j][3] : n.x; n.y = on ? n.y + wj * d[j][4] : n.y; n.z = on ? n.z + wj * d[j][5] : n.z; }
+        }
+    }
+}
+
+// prt_morph and prt_pose_morphed over the plane table: morph_corner's and pose_morphed_corner's loads and tails around the loop above
+PT_MORPH_HD void morph_planes_corner(const float* base_v, const float* base_n, const uint32_t* block_first, const MorphPlaneHead* plane_head,
+                                     const float* plane_p, const float* plane_n, const float* weights, uint32_t b, uint32_t l, float* out_v,
+                                     float* out_n) {
+    const size_t c = (size_t)b * 64 + l;
+    RefitQuad p = reinterpret_cast<const RefitQuad*>(base_v)[c];
+    RefitQuad n{0.0f, 0.0f, 0.0f, 0.0f};
+    if (base_n) n = reinterpret_cast<const RefitQuad*>(base_n)[c];
+    morph_raw_planes(block_first, plane_head, plane_p, base_n ? plane_n : nullptr, weights, b, l, p, n);
+    reinterpret_cast<RefitQuad*>(out_v)[c] = RefitQuad{p.x, p.y, p.z, 0.0f};
+    if (base_n) {
+        const float L = __builtin_sqrtf((n.x * n.x + n.y * n.y) + n.z * n.z);
+        const bool unit = L > 0.0f;
+        reinterpret_cast<RefitQuad*>(out_n)[c] = RefitQuad{unit ? n.x / L : n.x, unit ? n.y / L : n.y, unit ? n.z / L : n.z, 0.0f};
+    }
+}
+
+PT_MORPH_HD void pose_morphed_planes_corner(const float* base_v, const float* base_n, const uint32_t* block_first, const MorphPlaneHead* plane_head,
+                                            const float* plane_p, const float* plane_n, const float* weights, const uint16_t* bone_index,
+                                            const float* bone_weight, const float* matrices, uint32_t b, uint32_t l, float* out_v, float* out_n) {
+    const size_t c = (size_t)b * 64 + l;
+    RefitQuad p = reinterpret_cast<const RefitQuad*>(base_v)[c];
+    RefitQuad n{0.0f, 0.0f, 0.0f, 0.0f};
+    if (base_n) n = reinterpret_cast<const RefitQuad*>(base_n)[c];
+    morph_raw_planes(block_first, plane_head, plane_p, base_n ? plane_n : nullptr, weights, b, l, p, n);
     const RefitQuad wq = reinterpret_cast<const RefitQuad*>(bone_weight)[c];
     const PoseIndex idx = reinterpret_cast<const PoseIndex*>(bone_index)[c];
     pose_values(p, base_n != nullptr, [=]() { return n; }, wq, idx, matrices, c, out_v, out_n);
@@ -153,6 +247,66 @@ inline void morph_build_table(const prt_morph_set* set, uint32_t n_tris, MorphTa
             if (set->base_normals && g.d_normal) out.entry_n[e] = RefitQuad{g.d_normal[4 * j], g.d_normal[4 * j + 1], g.d_normal[4 * j + 2], 0.0f};
         }
     }
+}
+
+// the plane table of an accepted set: the planes of a block in ascending t (the targets are walked in ascending t, a target's corners in
+// ascending order).  plane_n stays empty without base normals; a target with d_normal == NULL contributes +0 deltas.  entries: the sum of
+// n_entries
+struct MorphPlanes {
+    std::vector<uint32_t> block_first;        // ceil(3T / 64) + 1
+    std::vector<MorphPlaneHead> head;
+    std::vector<float> plane_p, plane_n;      // 192 per plane
+    uint64_t entries = 0;
+};
+
+inline uint64_t morph_entries(const prt_morph_set* set) {
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < set->n_targets; ++t) total += set->targets[t].n_entries;
+    return total;
+}
+
+inline void morph_build_planes(const prt_morph_set* set, uint32_t n_tris, MorphPlanes& out) {
+    const size_t n = 3 * (size_t)n_tris, blocks = (n + 63) / 64;
+    const uint32_t none = 0xFFFFFFFFu;
+    out.entries = morph_entries(set);
+    out.block_first.assign(blocks + 1, 0u);
+    for (uint32_t t = 0; t < set->n_targets; ++t) {
+        const prt_morph_target& g = set->targets[t];
+        uint32_t last = none;
+        for (uint32_t j = 0; j < g.n_entries; ++j) {
+            const uint32_t b = g.corner[j] >> 6;
+            if (b != last) { ++out.block_first[(size_t)b + 1]; last = b; }
+        }
+    }
+    for (size_t b = 0; b < blocks; ++b) out.block_first[b + 1] += out.block_first[b];
+    const size_t planes = out.block_first[blocks];
+    const bool nrm = set->base_normals != nullptr;
+    out.head.assign(planes, MorphPlaneHead{0u, 0u, 0u, 0u});
+    out.plane_p.assign(planes * PT_MORPH_PLANE_FLOATS, 0.0f);
+    out.plane_n.assign(nrm ? planes * PT_MORPH_PLANE_FLOATS : 0, 0.0f);
+    std::vector<uint32_t> cursor(out.block_first.begin(), out.block_first.end() - 1);
+    for (uint32_t t = 0; t < set->n_targets; ++t) {
+        const prt_morph_target& g = set->targets[t];
+        uint32_t last = none;
+        size_t u = 0;
+        for (size_t j = 0; j < g.n_entries; ++j) {
+            const uint32_t b = g.corner[j] >> 6, l = g.corner[j] & 63u;
+            if (b != last) { u = cursor[b]++; out.head[u].target = t; last = b; }
+            if (l < 32u) out.head[u].mask_lo |= 1u << l; else out.head[u].mask_hi |= 1u << (l - 32u);
+            float* row = out.plane_p.data() + u * PT_MORPH_PLANE_FLOATS + l;
+            row[0] = g.d_position[4 * j]; row[64] = g.d_position[4 * j + 1]; row[128] = g.d_position[4 * j + 2];
+            if (nrm && g.d_normal) {
+                row = out.plane_n.data() + u * PT_MORPH_PLANE_FLOATS + l;
+                row[0] = g.d_normal[4 * j]; row[64] = g.d_normal[4 * j + 1]; row[128] = g.d_normal[4 * j + 2];
+            }
+        }
+    }
+}
+
+// prt_get_morph_report's table_bytes (prt.h): the device bytes of the delta tables alone
+inline uint64_t morph_table_bytes(uint32_t layout, uint32_t n_tris, uint64_t entries, uint64_t planes, bool nrm) {
+    const uint64_t n = 3 * (uint64_t)n_tris, k = nrm ? 2u : 1u;
+    return layout == PRT_MORPH_LAYOUT_PLANES ? 4 * ((n + 63) / 64 + 1) + 16 * planes + 768 * planes * k : 4 * (n + 1) + 16 * entries * k;
 }
 
 }  // namespace prt

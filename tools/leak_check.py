@@ -5,7 +5,8 @@ Every context renders; with --calls all (the default) it also goes through what 
 rebuild (host doors: the staging buffers, the refit tables, the spare tree set and the build's scratch), smoothing and motion on and off
 (the topology, both snapshots), a primitive update, a host ray cast, a temporal denoise and a records denoise, and two more uploads of other
 triangle counts (the primitives alone, then the mesh again) with a rebuild behind them, and a skin and a morph set with one pose of a morph
-(host door: both sets' buffers and staging) before both are turned off.  Prints the free-memory delta every 100 contexts and
+(host door: both sets' buffers and staging) before the skin is turned off, and the same set as planes (prt_set_morph_targets_layout: the
+plane table in place of the per-corner one) with one morph before it is.  Prints the free-memory delta every 100 contexts and
 one JSON line at the end.  A tool, not a test: free memory on a shared card is another tenant's business as much as ours.
 
     python tools/leak_check.py [--contexts 300] [--calls all|render]
@@ -59,6 +60,8 @@ def everything(r):
     r.set_morph_targets(v0, n0, [target])
     r.pose_morphed(matrices, weights)
     r.set_skin(None)
+    r.set_morph_targets(v0, n0, [target], layout="planes")
+    r.morph(weights)
     r.set_morph_targets(None)
 
 

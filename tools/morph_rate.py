@@ -15,7 +15,19 @@ with --phase kernels), and their streamed bytes per second (per corner 16 + 16 +
 corner for its indices and weights; the weight and matrix tables are not counted).  One JSON document on stdout (and into --out).  There is
 no pass mark.
 
+--layout both: the two table layouts of prt_set_morph_targets_layout against each other instead, per scene and set on two contexts of one
+process that hold the same set, PRT_MORPH_LAYOUT_CORNERS (the parent's kernel) and PRT_MORPH_LAYOUT_PLANES:
+  corners / planes                           prt_morph_device, PRT_POSE_REFIT, the two arms alternated call by call; medians with the
+                                             interquartile range; set time, prt_get_morph_report (table_bytes, fill) and device bytes of both
+  active targets                             the last dense set of --sets with k = 0, 1, 8, ... of its weights non-zero (--active), both arms,
+                                             and a plane set of one target without entries: a morph that reads no plane
+Kernel time: the four kernels' durations in a profiler run of their own with the same alternation, medians with the interquartile range,
+and the bytes each streams per second: per corner 64 (16 + 16 in, 32 out) and the table -- CORNERS 8 per corner of offsets and 32 per
+entry, PLANES 4 per block and, per plane of an active target, 16 + 1536 (the head and six rows; 16 for a plane that is skipped).
+dense_condition: the plane kernel's median below the per-corner kernel's by more than the two interquartile ranges together.
+
     python tools/morph_rate.py [--scenes cornell_coat,cornell_dragon] [--out profiles/r23_morph.json]
+    python tools/morph_rate.py --layout both --scenes cornell_dragon --out profiles/r28_morph_planes.json
 """
 import argparse
 import importlib
@@ -145,8 +157,215 @@ def kernel_times(prt, names, sets, timeout):
     return out
 
 
+# ---- --layout both: PRT_MORPH_LAYOUT_CORNERS against PRT_MORPH_LAYOUT_PLANES ----------------------------------------------------------------
+
+LAYOUTS = ("corners", "planes")
+KERNEL_OF = {"corners": ("morph_kernel", "pose_morphed_kernel"), "planes": ("morph_planes_kernel", "pose_morphed_planes_kernel")}
+
+
+def _spread(values):
+    q1, med, q3 = np.percentile(np.asarray(values, dtype=np.float64), [25, 50, 75])
+    return {"median": round(float(med), 4), "iqr": round(float(q3 - q1), 4), "min": round(float(min(values)), 4), "n": len(values)}
+
+
+def _alternated(arms, rounds, warm=2):
+    """pose_rate._rounds with the spread: wall clock in ms per arm, the arms alternated call by call with a rotating order"""
+    names = list(arms)
+    t = {k: [] for k in names}
+    for k in range(rounds + warm):
+        s = k % len(names)
+        for arm in names[s:] + names[:s]:
+            t0 = time.perf_counter()
+            arms[arm]()
+            if k >= warm:
+                t[arm].append(1e3 * (time.perf_counter() - t0))
+    return {k: _spread(v) for k, v in t.items()}
+
+
+def active_weights(n_targets, k):
+    """k of the n_targets weights non-zero, spread over the set"""
+    w = np.zeros(n_targets, dtype=f32)
+    if k:
+        w[np.linspace(0, n_targets - 1, k).round().astype(np.int64)] = 0.5 / k
+    return w
+
+
+def _pair(prt, scene, v0, n0, targets):
+    """two contexts over the scene that hold the same set, one per layout: ({layout: Renderer}, {layout: set time in ms})"""
+    pair, set_ms = {}, {}
+    for layout in LAYOUTS:
+        r = prt.Renderer(scene.config(), device=0)
+        r.upload_scene(scene)
+        t0 = time.perf_counter()
+        r.set_morph_targets(v0, n0, targets, layout=layout)
+        set_ms[layout] = round(1e3 * (time.perf_counter() - t0), 2)
+        pair[layout] = r
+    return pair, set_ms
+
+
+def _active_set(sets, active):
+    """the set the active-targets arm runs over: the last dense one, and the k that fit it"""
+    dense = [s for s in sets if s[1] >= 1.0]
+    if not dense or not active:
+        return None, []
+    return dense[-1], [k for k in active if k <= dense[-1][0]]
+
+
+def _empty_target():
+    return [(np.zeros(0, dtype=np.uint32), np.zeros((0, 4), dtype=f32), None)]
+
+
+def measure_layouts(prt, name, rounds, sets, active):
+    import torch
+    scene = _scene(prt, name)
+    a = prt.scene_arrays(scene.desc)
+    v0, n0 = a["vertices"].copy(), a["normals"].copy()
+    T = int(scene.desc.triangle_count)
+    out = {"triangles": T, "rounds": rounds, "sets": {}}
+    act_set, ks = _active_set(sets, active)
+    for n_targets, fraction in sets:
+        targets, w, entries = target_set(3 * T, n_targets, fraction, 5)
+        pair, set_ms = _pair(prt, scene, v0, n0, targets)
+        dw = torch.from_numpy(w).cuda()
+        rec = {"entries": entries, "set_morph_targets_ms": set_ms, "report": {}, "device_bytes": {}}
+        morphed = {}
+        for layout, r in pair.items():
+            rep = r.morph_report()
+            rec["report"][layout] = rep
+            rec["device_bytes"][layout] = 192 * T + rep["table_bytes"] + 4 * n_targets
+            r.morph(dw)
+            morphed[layout] = r.read_morphed()
+        rec["same_bytes"] = all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(morphed["corners"], morphed["planes"]))
+        del morphed
+        rec["morph_device_ms"] = _alternated({layout: (lambda r=r: r.morph(dw)) for layout, r in pair.items()}, rounds)
+        if (n_targets, fraction) == act_set:
+            rec["active"] = {}
+            for k in ks:
+                dk = torch.from_numpy(active_weights(n_targets, k)).cuda()
+                rec["active"]["k_%d" % k] = _alternated({layout: (lambda r=r: r.morph(dk)) for layout, r in pair.items()}, rounds)
+            r = pair["planes"]
+            r.set_morph_targets(v0, n0, _empty_target(), layout="planes")
+            d1 = torch.zeros(4, dtype=torch.float32, device="cuda")
+            rec["active"]["one_empty_target"] = _alternated({"planes": lambda: r.morph(d1)}, rounds)
+        for r in pair.values():
+            r.close()
+        out["sets"][_name(n_targets, fraction)] = rec
+        print(json.dumps({name: {_name(n_targets, fraction): rec}}), file=sys.stderr, flush=True)
+    return out
+
+
+def layout_kernels_phase(prt, names, sets, active, rounds):
+    """the launches rocprofv3 times, per scene and set: `rounds` morphs alternated between the layouts, `rounds` fused poses likewise, and for
+    the active-targets set `rounds` alternated morphs per k and `rounds` morphs over the plane set of one empty target"""
+    import torch
+    act_set, ks = _active_set(sets, active)
+    for name in names:
+        scene = _scene(prt, name)
+        a = prt.scene_arrays(scene.desc)
+        v0, n0 = a["vertices"].copy(), a["normals"].copy()
+        T = int(scene.desc.triangle_count)
+        index, weight = influences(v0, "four", N_BONES, 3)
+        M = torch.from_numpy(bones(N_BONES, 9)).cuda()
+        for n_targets, fraction in sets:
+            targets, w, _ = target_set(3 * T, n_targets, fraction, 5)
+            pair, _ = _pair(prt, scene, v0, n0, targets)
+            dw = torch.from_numpy(w).cuda()
+            for r in pair.values():
+                r.set_skin(v0, n0, index, weight, N_BONES)
+            for _ in range(rounds):
+                for r in pair.values():
+                    r.morph(dw)
+            for _ in range(rounds):
+                for r in pair.values():
+                    r.pose_morphed(M, dw)
+            if (n_targets, fraction) == act_set:
+                for k in ks:
+                    dk = torch.from_numpy(active_weights(n_targets, k)).cuda()
+                    for _ in range(rounds):
+                        for r in pair.values():
+                            r.morph(dk)
+                r = pair["planes"]
+                r.set_morph_targets(v0, n0, _empty_target(), layout="planes")
+                d1 = torch.zeros(4, dtype=torch.float32, device="cuda")
+                for _ in range(rounds):
+                    r.morph(d1)
+            for r in pair.values():
+                r.close()
+
+
+def layout_kernel_times(prt, names, sets, active, rounds, timeout, doc):
+    """per scene and set: the four kernels' durations (median, interquartile range and best of the calls after the first) and their streamed
+    bytes per second; the active-targets curves; the dense condition"""
+    spec = ",".join("%d:%g" % s for s in sets)
+    rows = kernel_rows(["--phase", "kernels", "--layout", "both", "--scenes", ",".join(names), "--sets", spec, "--calls", str(rounds),
+                        "--active", ",".join(str(k) for k in active)], "morph_planes", timeout)
+    act_set, ks = _active_set(sets, active)
+    mine = {kernel: [(e - b) / 1e3 for n, b, e in rows if kernel + "(" in n or n.endswith(kernel) or ("prt::" + kernel) in n or ("3prt%d%s" % (len(kernel), kernel)) in n]
+            for layout in LAYOUTS for kernel in KERNEL_OF[layout]}
+    at = {kernel: 0 for kernel in mine}
+
+    def take(kernel, streamed):
+        us = mine[kernel][at[kernel] + 1:at[kernel] + rounds]                             # (the first call of a run is left out)
+        assert len(us) == rounds - 1, (kernel, at[kernel], len(mine[kernel]))
+        at[kernel] += rounds
+        rec = _spread(us)
+        rec = {"us_median": rec["median"], "us_iqr": rec["iqr"], "us_best": rec["min"], "streamed_bytes": int(streamed)}
+        rec["streamed_TB_per_s_median"] = round(streamed / rec["us_median"] / 1e6, 3) if rec["us_median"] else None
+        return rec
+    out = {}
+    for name in names:
+        T = doc["scenes"][name]["triangles"]
+        for n_targets, fraction in sets:
+            key = _name(n_targets, fraction)
+            rep = doc["scenes"][name]["sets"][key]["report"]
+            entries, planes = rep["planes"]["entries"], rep["planes"]["planes"]
+            streamed = {"corners": (64 + 8) * 3 * T + 32 * entries, "planes": 64 * 3 * T + 4 * ((3 * T + 63) // 64 + 1) + (16 + 1536) * planes}
+            rec = {}
+            for fused in (0, 1):
+                for layout in LAYOUTS:
+                    rec[KERNEL_OF[layout][fused]] = take(KERNEL_OF[layout][fused], streamed[layout] + 24 * 3 * T * fused)
+            c, p = rec["morph_kernel"], rec["morph_planes_kernel"]
+            rec["planes_over_corners"] = round(p["us_median"] / c["us_median"], 4)
+            if fraction >= 1.0 and n_targets > 1:
+                rec["dense_condition"] = {"holds": bool(c["us_median"] - p["us_median"] > c["us_iqr"] + p["us_iqr"]),
+                                          "corners_minus_planes_us": round(c["us_median"] - p["us_median"], 3),
+                                          "combined_iqr_us": round(c["us_iqr"] + p["us_iqr"], 3)}
+            if (n_targets, fraction) == act_set:
+                rec["active"] = {}
+                per_target = planes // n_targets
+                for k in ks:
+                    sk = 64 * 3 * T + 4 * ((3 * T + 63) // 64 + 1) + 16 * planes + 1536 * per_target * k
+                    rec["active"]["k_%d" % k] = {"morph_kernel": take("morph_kernel", streamed["corners"]), "morph_planes_kernel": take("morph_planes_kernel", sk)}
+                rec["active"]["one_empty_target"] = {"morph_planes_kernel": take("morph_planes_kernel", 64 * 3 * T + 4 * ((3 * T + 63) // 64 + 1))}
+            out.setdefault(name, {})[key] = rec
+    out["note"] = ("rocprofv3 --kernel-trace --stats, a run of its own, the layouts alternated call by call; streamed bytes: 64 per corner and the "
+                   "table (CORNERS: 8 per corner and 32 per entry; PLANES: 4 per block, 16 per plane and 1536 per plane of an active target), "
+                   "the fused kernels 24 more per corner; the weight and matrix tables not counted")
+    return out
+
+
+def main_layouts(prt, a, names, sets):
+    active = [int(k) for k in a.active.split(",") if k != ""]
+    if a.phase == "kernels":
+        layout_kernels_phase(prt, names, sets, active, a.calls)
+        return
+    doc = {"build_id": prt.build_id(), "layout": "both", "scenes": {name: measure_layouts(prt, name, a.calls, sets, active) for name in names}}
+    if a.phase == "all":
+        try:
+            doc["kernel_time"] = layout_kernel_times(prt, names, sets, active, a.calls, a.rocprof_timeout, doc)
+        except (subprocess.SubprocessError, AssertionError, KeyError, OSError) as e:
+            doc["kernel_time"] = {"error": repr(e)}
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--layout", default="corners", choices=["corners", "both"], help="both: the two table layouts against each other")
+    ap.add_argument("--active", default="0,1,8,64", help="--layout both: the numbers of non-zero weights of the active-targets arm")
     ap.add_argument("--scenes", default="cornell_coat,cornell_dragon")
     ap.add_argument("--sets", default=",".join("%d:%g" % s for s in SETS), help="n_targets:fraction, ...")
     ap.add_argument("--calls", type=int, default=20)
@@ -157,6 +376,9 @@ def main():
     prt = importlib.import_module("photorealistic-rendering-using-opencl_amd")
     names = a.scenes.split(",")
     sets = [(int(s.split(":")[0]), float(s.split(":")[1])) for s in a.sets.split(",")]
+    if a.layout == "both":
+        main_layouts(prt, a, names, sets)
+        return
     if a.phase == "kernels":
         kernels_phase(prt, names, sets)
         return
