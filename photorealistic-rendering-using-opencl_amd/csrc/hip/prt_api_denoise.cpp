@@ -34,6 +34,14 @@ static int temporal_param_checks(prt_ctx* c, const prt_temporal_params& t, const
     return PRT_OK;
 }
 
+// the context's frame holds a picture and its guides (the filter calls on it, and the export)
+static int picture_checks(prt_ctx* c, const std::string& w) {
+    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, w + ": a debug view is not a picture to filter");
+    if (!c->frame.guides_valid) return fail(c, PRT_ERR_NOT_READY, w + ": no guides for this scene, camera, map and frame (prt_render_guides)");
+    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, w + ": nothing rendered since the reset");
+    return PRT_OK;
+}
+
 // the checks prt_denoise and prt_denoise_temporal share; *spatial: the variance source the call resolves to
 static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* who, bool* spatial) {
     const std::string w(who);
@@ -43,9 +51,7 @@ static int denoise_checks(prt_ctx* c, const prt_denoise_params& p, const char* w
     if (rc) return rc;
     if (c->row0 != 0 || c->rows != c->full_height || c->n_parts != 1)
         return fail(c, PRT_ERR_UNSUPPORTED, w + ": the filter needs the whole frame (tile and row-block contexts are refused)");
-    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, w + ": a debug view is not a picture to filter");
-    if (!c->frame.guides_valid) return fail(c, PRT_ERR_NOT_READY, w + ": no guides for this scene, camera, map and frame (prt_render_guides)");
-    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, w + ": nothing rendered since the reset");
+    if ((rc = picture_checks(c, w))) return rc;
     const bool stats = c->frame.stats_valid && c->frame.adapt;
     if (p.var_source == PRT_DENOISE_VAR_STATS && !stats)
         return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs the last render since the reset to be prt_render_adaptive");
@@ -97,34 +103,55 @@ static int history_commit(prt_ctx* c, History& h, const float4* guides, size_t n
     h.valid = true;
     return PRT_OK;
 }
-// the last call's half of an npix-pixel history, interleaved per pixel: {c, n}, {m1, m2, v, 0}.  (With a temporal response the spare lane of
-// the moments plane holds the pixel's flag on the device: the read returns the 0 it always has)
-static int read_history_planes(prt_ctx* c, const History& h, size_t npix, float* out8) {
-    std::vector<float4> p(2 * npix);
-    HIPCHK(c, hipMemcpy(p.data(), h.planes + 2 * npix * (size_t)h.cur, 2 * npix * sizeof(float4), hipMemcpyDeviceToHost));
+// the four read-backs: the frame history (rec false: of the context's frame part) or the record history (of a W x H frame), and of either
+// the history itself -- the last call's half, interleaved per pixel: {c, n}, {m1, m2, v, 0} -- or (response) {f.rgb, flag}: the fast plane's
+// colour and the flag from the spare lane of the moments plane, which the history read returns as the 0 it always has
+static int read_back(prt_ctx* c, const char* who, bool rec, int W, int H, bool response, float* out) {
+    const std::string w(who);
+    const History& h = rec ? c->ctx.rec_hist : c->frame.hist;
+    if (!out || (rec ? W < 1 || H < 1 : !c->have_size)) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": bad arguments");
+    if (response && !c->response_on) return fail(c, PRT_ERR_NOT_READY, w + ": no temporal response is set (prt_set_temporal_response)");
+    if (!h.valid || (rec && !h.planes) || (response && !h.fast))
+        return fail(c, PRT_ERR_NOT_READY, w + (rec ? ": the record history is empty (prt_denoise_records_temporal)" : ": the history is empty (prt_denoise_temporal)"));
+    if (rec && (W != c->ctx.rec_hist_w || H != c->ctx.rec_hist_h)) return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": the record history has another size");
+    int rc = prt_synchronize(c);
+    if (rc) return rc;
+    const size_t npix = rec ? (size_t)W * (size_t)H : c->npix;
+    const float4* half = h.planes + 2 * npix * (size_t)h.cur;
+    std::vector<float4> p(2 * npix);                                    // {c, n} or the fast plane, then the moments
+    if (!response) HIPCHK(c, hipMemcpy(p.data(), half, 2 * npix * sizeof(float4), hipMemcpyDeviceToHost));
+    else {
+        HIPCHK(c, hipMemcpy(p.data(), h.fast + npix * (size_t)h.cur, npix * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(p.data() + npix, half + npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
+    }
     for (size_t k = 0; k < npix; ++k) {
         const float4 a = p[k], b = p[npix + k];
-        float* o = out8 + 8 * k;
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = 0.0f;
-    }
-    return PRT_OK;
-}
-// ... and its response: {f.rgb, flag} per pixel -- the fast plane's colour and the flag from the spare lane of the moments plane
-static int read_response_planes(prt_ctx* c, const History& h, size_t npix, float* out4) {
-    std::vector<float4> f(npix), m(npix);
-    HIPCHK(c, hipMemcpy(f.data(), h.fast + npix * (size_t)h.cur, npix * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(m.data(), h.planes + 2 * npix * (size_t)h.cur + npix, npix * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < npix; ++k) {
-        float* o = out4 + 4 * k;
-        o[0] = f[k].x; o[1] = f[k].y; o[2] = f[k].z; o[3] = m[k].w;
+        float* o = out + (response ? 4 : 8) * k;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z;
+        if (response) o[3] = b.w;
+        else { o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = 0.0f; }
     }
     return PRT_OK;
 }
 
-// the filter's buffers of the context's frame, on first use: two ping-pong planes and the output plane in dn, the Gaussian of v in dn_g
-static int filter_buffers(prt_ctx* c) {
+// the planes of a filter call on the context's own frame; its buffers on first use: two ping-pong planes and the output plane in dn, the
+// Gaussian of v in dn_g
+static int frame_planes(prt_ctx* c, FilterPlanes& pl) {
     HIPCHK(c, c->frame.dn.first_use(3 * c->npix));
     HIPCHK(c, c->frame.dn_g.first_use(c->npix));
+    float4* dn = c->frame.dn;
+    pl = FilterPlanes{c->frame.fb, c->frame.guides, dn, dn + c->npix, c->frame.dn_g, dn + 2 * c->npix, c->width, c->rows};
+    return PRT_OK;
+}
+// ... and on a W x H frame of records, in the context's record block (grown on demand): the framebuffer plane, the guide planes (2), the
+// filter's three, the Gaussian of v and, behind it, the "a record without stats" word
+static int record_planes(prt_ctx* c, int W, int H, FilterPlanes& pl, unsigned** no_stats) {
+    const size_t npix = (size_t)W * (size_t)H;
+    HIPCHK(c, c->ctx.rec.reserve(npix * (6 * sizeof(float4) + sizeof(float)) + sizeof(unsigned)));
+    float4* fb = reinterpret_cast<float4*>(c->ctx.rec.get());
+    float* g = reinterpret_cast<float*>(fb + 6 * npix);
+    pl = FilterPlanes{fb, fb + npix, fb + 3 * npix, fb + 4 * npix, g, fb + 5 * npix, W, H};
+    *no_stats = reinterpret_cast<unsigned*>(g + npix);
     return PRT_OK;
 }
 // the two buffers of an npix-pixel history, on first use, and with a temporal response its fast plane (two halves); anew: whatever it holds
@@ -137,18 +164,38 @@ static int history_buffers(prt_ctx* c, History& h, size_t npix, bool anew) {
     return PRT_OK;
 }
 
+// the temporal half of a filtering call: its parameters and camera, the history it continues (anew: what that holds goes first) and the
+// motion plane of the guides (W x H float4 {D, m}, device) or null
+struct TemporalCall { const prt_temporal_params& t; const DevCamera& cam; History& hist; bool anew; const float4* motion; };
+
+// what every filtering door ends in.  pending: the variance step of the frame doors, queued behind the history's allocations (the record
+// doors had to run theirs first, for the records' verdict: null)
+static int filter_and_output(prt_ctx* c, const FilterPlanes& pl, const VarianceSource* pending, const prt_denoise_params& p, const TemporalCall* tc,
+                             void* device_rgba, float* rgba, uint8_t* rgba8) {
+    const size_t npix = (size_t)pl.W * (size_t)pl.H;
+    TemporalHistory h{};
+    if (tc) {
+        if (int rc = history_buffers(c, tc->hist, npix, tc->anew)) return rc;
+        h = history_begin(c, tc->hist, npix);
+    }
+    if (pending) launch_filter_variance(pl, tc != nullptr, *pending, c->stream);
+    launch_filter_chain(pl, p, tc ? &tc->t : nullptr, tc ? &tc->cam : nullptr, &h, tc ? tc->motion : nullptr, c->stream);
+    HIPCHK(c, hipGetLastError());
+    if (tc)
+        if (int rc = history_commit(c, tc->hist, pl.guides, npix, tc->cam)) return rc;
+    return records_output(c, pl.out, pl.W, pl.H, device_rgba, rgba, rgba8);
+}
+
 extern "C" int prt_denoise(prt_ctx* c, const prt_denoise_params* params, float* rgba, uint8_t* rgba8) {
     CTX_CHECK(c);
     const prt_denoise_params p = params ? *params : default_denoise_params();
-    bool spatial = false;
-    int rc = denoise_checks(c, p, "prt_denoise", &spatial);
+    VarianceSource src{false, c->S.q4, c->frame.adapt};
+    int rc = denoise_checks(c, p, "prt_denoise", &src.spatial);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = filter_buffers(c))) return rc;
-    float4* out = c->frame.dn + 2 * c->npix;
-    launch_denoise(c->frame.fb, c->S.q4, c->frame.adapt, spatial, c->frame.guides, c->width, c->rows, p, c->frame.dn, c->frame.dn + c->npix, c->frame.dn_g, out, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return records_output(c, out, c->width, c->rows, nullptr, rgba, rgba8);
+    FilterPlanes pl;
+    if ((rc = frame_planes(c, pl))) return rc;
+    return filter_and_output(c, pl, &src, p, nullptr, nullptr, rgba, rgba8);
 }
 
 extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatial, const prt_temporal_params* temporal, float* rgba, uint8_t* rgba8) {
@@ -157,29 +204,20 @@ extern "C" int prt_denoise_temporal(prt_ctx* c, const prt_denoise_params* spatia
     const prt_temporal_params t = temporal ? *temporal : default_temporal_params();
     int rc = temporal_param_checks(c, t, "prt_denoise_temporal");
     if (rc) return rc;
-    bool spatial_var = false;
-    rc = denoise_checks(c, p, "prt_denoise_temporal", &spatial_var);
+    VarianceSource src{false, c->S.q4, c->frame.adapt};
+    rc = denoise_checks(c, p, "prt_denoise_temporal", &src.spatial);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = filter_buffers(c)) || (rc = history_buffers(c, c->frame.hist, c->npix, false))) return rc;
-    const TemporalHistory h = history_begin(c, c->frame.hist, c->npix);
-    float4* out = c->frame.dn + 2 * c->npix;
+    FilterPlanes pl;
+    if ((rc = frame_planes(c, pl))) return rc;
     // the context's motion plane when motion is on and the plane is the valid guides' own (prt.h)
-    const float4* motion = (c->motion && c->frame.motion_valid) ? c->frame.motion : nullptr;
-    launch_denoise_temporal(c->frame.fb, c->S.q4, c->frame.adapt, spatial_var, c->frame.guides, c->width, c->rows, p, t, c->cam, h, c->frame.dn,
-                            c->frame.dn + c->npix, c->frame.dn_g, out, c->stream, motion);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = history_commit(c, c->frame.hist, c->frame.guides, c->npix, c->cam))) return rc;
-    return records_output(c, out, c->width, c->rows, nullptr, rgba, rgba8);
+    const TemporalCall tc{t, c->cam, c->frame.hist, false, (c->motion && c->frame.motion_valid) ? c->frame.motion.get() : nullptr};
+    return filter_and_output(c, pl, &src, p, &tc, nullptr, rgba, rgba8);
 }
 
 extern "C" int prt_read_history(prt_ctx* c, float* out8) {
     CTX_CHECK(c);
-    if (!out8 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_history: bad arguments");
-    if (!c->frame.hist.valid) return fail(c, PRT_ERR_NOT_READY, "prt_read_history: the history is empty (prt_denoise_temporal)");
-    int rc = prt_synchronize(c);
-    if (rc) return rc;
-    return read_history_planes(c, c->frame.hist, c->npix, out8);
+    return read_back(c, "prt_read_history", false, 0, 0, false, out8);
 }
 
 extern "C" int prt_reset_history(prt_ctx* c) {
@@ -214,12 +252,7 @@ extern "C" int prt_set_temporal_response(prt_ctx* c, const prt_temporal_response
 
 extern "C" int prt_read_response(prt_ctx* c, float* out4) {
     CTX_CHECK(c);
-    if (!out4 || !c->have_size) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_response: bad arguments");
-    if (!c->response_on) return fail(c, PRT_ERR_NOT_READY, "prt_read_response: no temporal response is set (prt_set_temporal_response)");
-    if (!c->frame.hist.valid || !c->frame.hist.fast) return fail(c, PRT_ERR_NOT_READY, "prt_read_response: the history is empty (prt_denoise_temporal)");
-    int rc = prt_synchronize(c);
-    if (rc) return rc;
-    return read_response_planes(c, c->frame.hist, c->npix, out4);
+    return read_back(c, "prt_read_response", false, 0, 0, true, out4);
 }
 
 // ---- denoiser inputs as records (prt.h prt_export_denoise_inputs, prt_denoise_records; pt_records.hip) ---------------------------------------
@@ -228,9 +261,7 @@ extern "C" int prt_export_denoise_inputs(prt_ctx* c, void* device_records) {
     if (!device_records || !aligned16(device_records) || !c->have_size)
         return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_export_denoise_inputs: bad arguments (a 16-byte aligned device pointer, a context with a frame size)");
     if (c->state_undefined) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: an earlier render call failed half-way; prt_reset or prt_write_state first");
-    if (c->sc.view) return fail(c, PRT_ERR_UNSUPPORTED, "prt_export_denoise_inputs: a debug view is not a picture to filter");
-    if (!c->frame.guides_valid) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: no guides for this scene, camera, map and frame (prt_render_guides)");
-    if (c->fresh) return fail(c, PRT_ERR_NOT_READY, "prt_export_denoise_inputs: nothing rendered since the reset");
+    if (int rc = picture_checks(c, "prt_export_denoise_inputs")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const bool stats = c->frame.stats_valid && c->frame.adapt;
     launch_records_export(c->frame.fb, c->S.q4, stats ? c->frame.adapt : nullptr, c->frame.guides, c->width, c->rows, static_cast<float4*>(device_records), c->stream);
@@ -248,18 +279,13 @@ static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params
     if (W < 1 || H < 1 || !device_records || !aligned16(device_records) || (device_rgba && !aligned16(device_rgba)) || !aligned16(device_motion))
         return fail(c, PRT_ERR_INVALID_ARGUMENT, w + ": needs width >= 1, height >= 1 and 16-byte aligned device pointers (records not null)");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)W * (size_t)H;
-    HIPCHK(c, c->ctx.rec.reserve(npix * (6 * sizeof(float4) + sizeof(float)) + sizeof(unsigned)));
-    float4* fb = reinterpret_cast<float4*>(c->ctx.rec.get());
-    float4* guides = fb + npix;
-    float4* buf0 = fb + 3 * npix;
-    float4* buf1 = fb + 4 * npix;
-    float4* out = fb + 5 * npix;
-    float* g = reinterpret_cast<float*>(fb + 6 * npix);
-    unsigned* d_flag = reinterpret_cast<unsigned*>(g + npix);
-    float4* var = t ? buf1 : buf0;                   // (where the variance step of launch_denoise_temporal / launch_denoise leaves {rgb, v})
+    FilterPlanes pl;
+    unsigned* d_flag = nullptr;
+    if (int rc = record_planes(c, W, H, pl, &d_flag)) return rc;
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(unsigned), c->stream));
-    launch_records_import(static_cast<const float4*>(device_records), W, H, fb, guides, var, d_flag, c->stream);
+    VarianceSource src;
+    src.records = static_cast<const float4*>(device_records); src.no_stats = d_flag;
+    launch_filter_variance(pl, t != nullptr, src, c->stream);
     HIPCHK(c, hipGetLastError());
     bool spatial = p.var_source == PRT_DENOISE_VAR_SPATIAL;
     if (!spatial) {
@@ -270,28 +296,16 @@ static int denoise_records(prt_ctx* c, const char* who, const prt_denoise_params
             return fail(c, PRT_ERR_NOT_READY, w + ": PRT_DENOISE_VAR_STATS needs stats in every record (rendered by prt_render_adaptive)");
         spatial = no_stats != 0;
     }
-    if (spatial) launch_denoise_var(fb, nullptr, nullptr, true, W, H, var, c->stream);       // the 5x5 moments of the gathered colours
-    if (!t) {
-        float4* cur = buf0;
-        float4* nxt = buf1;
-        for (unsigned i = 0; i < p.passes; ++i) {
-            const bool last = i + 1 == p.passes;
-            launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, last ? out : nxt, c->stream);
-            float4* tmp = cur; cur = nxt; nxt = tmp;
-        }
-        HIPCHK(c, hipGetLastError());
-        return records_output(c, out, W, H, device_rgba, rgba, rgba8);
-    }
+    if (spatial) launch_filter_variance(pl, t != nullptr, VarianceSource{true}, c->stream);       // the 5x5 moments of the gathered colours
+    if (!t) return filter_and_output(c, pl, nullptr, p, nullptr, device_rgba, rgba, rgba8);
+    // the record history is this size's from here on: one of another size, or without its buffers, starts anew
     History& rh = c->ctx.rec_hist;
-    if (int rc = history_buffers(c, rh, npix, !rh.planes || !rh.guides || c->ctx.rec_hist_w != W || c->ctx.rec_hist_h != H)) return rc;
+    const bool anew = !rh.planes || !rh.guides || c->ctx.rec_hist_w != W || c->ctx.rec_hist_h != H;
     c->ctx.rec_hist_w = W; c->ctx.rec_hist_h = H;
     DevCamera dc;
     make_dev_camera(*cam, dc);
-    const TemporalHistory h = history_begin(c, rh, npix);
-    launch_denoise_temporal_var(fb, guides, W, H, p, *t, dc, h, buf0, buf1, g, out, c->stream, static_cast<const float4*>(device_motion));
-    HIPCHK(c, hipGetLastError());
-    if (int rc = history_commit(c, rh, guides, npix, dc)) return rc;
-    return records_output(c, out, W, H, device_rgba, rgba, rgba8);
+    const TemporalCall tc{*t, dc, rh, anew, static_cast<const float4*>(device_motion)};
+    return filter_and_output(c, pl, nullptr, p, &tc, device_rgba, rgba, rgba8);
 }
 
 extern "C" int prt_denoise_records(prt_ctx* c, const prt_denoise_params* params, int width, int height, const void* device_records,
@@ -330,25 +344,10 @@ extern "C" int prt_reset_records_history(prt_ctx* c) {
 
 extern "C" int prt_read_records_history(prt_ctx* c, int width, int height, float* out8) {
     CTX_CHECK(c);
-    if (!out8 || width < 1 || height < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: bad arguments");
-    if (!c->ctx.rec_hist.valid || !c->ctx.rec_hist.planes)
-        return fail(c, PRT_ERR_NOT_READY, "prt_read_records_history: the record history is empty (prt_denoise_records_temporal)");
-    if (width != c->ctx.rec_hist_w || height != c->ctx.rec_hist_h)
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_history: the record history has another size");
-    int rc = prt_synchronize(c);
-    if (rc) return rc;
-    return read_history_planes(c, c->ctx.rec_hist, (size_t)width * (size_t)height, out8);
+    return read_back(c, "prt_read_records_history", true, width, height, false, out8);
 }
 
 extern "C" int prt_read_records_response(prt_ctx* c, int width, int height, float* out4) {
     CTX_CHECK(c);
-    if (!out4 || width < 1 || height < 1) return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_response: bad arguments");
-    if (!c->response_on) return fail(c, PRT_ERR_NOT_READY, "prt_read_records_response: no temporal response is set (prt_set_temporal_response)");
-    if (!c->ctx.rec_hist.valid || !c->ctx.rec_hist.planes || !c->ctx.rec_hist.fast)
-        return fail(c, PRT_ERR_NOT_READY, "prt_read_records_response: the record history is empty (prt_denoise_records_temporal)");
-    if (width != c->ctx.rec_hist_w || height != c->ctx.rec_hist_h)
-        return fail(c, PRT_ERR_INVALID_ARGUMENT, "prt_read_records_response: the record history has another size");
-    int rc = prt_synchronize(c);
-    if (rc) return rc;
-    return read_response_planes(c, c->ctx.rec_hist, (size_t)width * (size_t)height, out4);
+    return read_back(c, "prt_read_records_response", true, width, height, true, out4);
 }

@@ -378,13 +378,9 @@ extern "C" int prt_render_guides(prt_ctx* c, uint32_t samples) {
     // ... and the primitive-motion instances only while a primitive snapshot is pending (prt_update_primitives), with the triangle term only
     // while a triangle snapshot is pending too: the two snapshots are independent of each other
     const bool prim_snap = c->motion && c->scene.snap.prim_snap_valid && c->scene.snap.spheres_prev && c->scene.snap.sdfs_prev && c->scene.snap.quads_prev;
-    if (prim_snap) {
-        const PrimPrev prims{c->scene.snap.spheres_prev, c->scene.snap.sdfs_prev, c->scene.snap.quads_prev};
-        launch_guides_prim_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides,
-                                  snap ? c->scene.snap.tri_prev.get() : nullptr, prims, c->frame.motion, c->stream);
-    } else if (snap) launch_guides_motion(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides, c->scene.snap.tri_prev,
-                                          c->frame.motion, c->stream);
-    else launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides, c->stream);
+    const PrimPrev prims{c->scene.snap.spheres_prev, c->scene.snap.sdfs_prev, c->scene.snap.quads_prev};
+    launch_guides(c->sc, c->cam, frame_args(c, 1, 0, nullptr, 0, false), samples, c->frame.guides, snap ? c->scene.snap.tri_prev.get() : nullptr,
+                  prim_snap ? &prims : nullptr, c->frame.motion, c->stream);
     HIPCHK(c, hipGetLastError());
     if (c->motion && !snap && !prim_snap) HIPCHK(c, hipMemsetAsync(c->frame.motion, 0, c->npix * sizeof(float4), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

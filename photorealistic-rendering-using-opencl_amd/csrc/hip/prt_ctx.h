@@ -146,7 +146,7 @@ struct Frame {
     DevBuf<uint32_t> live, live_aux;
     bool stats_valid = false;                      // the last render since prt_reset was prt_render_adaptive: adapt belongs to the framebuffer
     // prt_render_guides / prt_denoise (pt_denoise.hip): the guide plane (2 float4 per pixel), the motion plane ({D, m} per pixel) and the
-    // filter's buffers (filter_buffers)
+    // filter's buffers (frame_planes)
     DevBuf<float4> guides, motion;
     bool guides_valid = false;                     // cleared by everything that changes what a primary ray sees (prt.h)
     bool motion_valid = false;                     // motion was written by the guide render that made guides_valid

@@ -11,6 +11,7 @@
 //
 // The filter kernels run 16x16 workgroups over the frame and read straight from global memory: at 1080p the working set (guides,
 // ping-pong buffers, framebuffer) stays in the L2 / Infinity Cache, a tap costs three 16-byte loads.
+#include "pt_denoise_dev.h"
 #include "pt_guides.h"
 #include "pt_launch.h"
 #include "pt_motion.h"
@@ -114,74 +115,42 @@ __global__ __launch_bounds__(64) void filtered_guides_prim_motion_kernel(const D
     guide_pixel<false, true, TRI, true>(sc, cam, fa, samples, out, tri_prev, motion, prims);
 }
 
-// one launcher for the plain and the motion instances (MOTION: tri_prev and motion are the two further kernel arguments)
-template <bool SDF, bool FILTER, bool MOTION>
-static void launch_guides_t(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                            float4* motion, hipStream_t stream) {
+// the launch of any instance: one wave per 8x8 tile, the walk stack in LDS -- beyond 64 KiB of it (more than 256 stack levels) the kernel is
+// told first.  tail: the kernel's arguments behind `out`
+template <typename Kernel, typename... Tail>
+static void launch_guide_kernel(Kernel kernel, const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out,
+                                hipStream_t stream, Tail... tail) {
     const size_t lds = (size_t)sc.stack_levels * 64 * sizeof(unsigned);
-    static size_t lds_attr = 0;
-    const void* k;
-    if constexpr (MOTION) k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_motion_kernel) : reinterpret_cast<const void*>(&guide_motion_kernel<SDF>);
-    else k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_kernel) : reinterpret_cast<const void*>(&guide_kernel<SDF>);
-    if (lds > 65536u && lds > lds_attr) {
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        lds_attr = lds;
-    }
+    if (lds > 65536u) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const unsigned tiles = (unsigned)(((fa.width + 7) / 8) * ((fa.rows + 7) / 8));
-    if constexpr (MOTION) {
-        if constexpr (FILTER) hipLaunchKernelGGL(filtered_guides_motion_kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, motion);
-        else hipLaunchKernelGGL((guide_motion_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, motion);
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tail...);
+}
+// the instance by pixel filter (which excludes SDF scenes), SDF primitives, and the pending snapshots of triangles and of primitives.  (The
+// template instances stand in the code object in the order they are named here)
+void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                   const PrimPrev* prims, float4* motion, hipStream_t stream) {
+    const bool filter = fa.filter_kind != PRT_FILTER_NONE, sdf = !filter && sc.n_sdfs;
+    const auto go = [&](auto kernel, auto... tail) { launch_guide_kernel(kernel, sc, cam, fa, samples, out, stream, tail...); };
+    if (!prims && !tri_prev) {
+        if (filter) go(&filtered_guides_kernel);
+        else if (!sdf) go(&guide_kernel<false>);
+        else go(&guide_kernel<true>);
+    } else if (!prims) {
+        if (filter) go(&filtered_guides_motion_kernel, tri_prev, motion);
+        else if (!sdf) go(&guide_motion_kernel<false>, tri_prev, motion);
+        else go(&guide_motion_kernel<true>, tri_prev, motion);
+    } else if (tri_prev) {
+        if (filter) go(&filtered_guides_prim_motion_kernel<true>, tri_prev, *prims, motion);
+        else if (!sdf) go(&guide_prim_motion_kernel<false, true>, tri_prev, *prims, motion);
+        else go(&guide_prim_motion_kernel<true, true>, tri_prev, *prims, motion);
     } else {
-        if constexpr (FILTER) hipLaunchKernelGGL(filtered_guides_kernel, dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
-        else hipLaunchKernelGGL((guide_kernel<SDF>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out);
+        if (filter) go(&filtered_guides_prim_motion_kernel<false>, tri_prev, *prims, motion);
+        else if (!sdf) go(&guide_prim_motion_kernel<false, false>, tri_prev, *prims, motion);
+        else go(&guide_prim_motion_kernel<true, false>, tri_prev, *prims, motion);
     }
-}
-template <bool MOTION>
-static void launch_guides_m(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                            float4* motion, hipStream_t stream) {
-    if (fa.filter_kind != PRT_FILTER_NONE) launch_guides_t<false, true, MOTION>(sc, cam, fa, samples, out, tri_prev, motion, stream);
-    else if (sc.n_sdfs) launch_guides_t<true, false, MOTION>(sc, cam, fa, samples, out, tri_prev, motion, stream);
-    else launch_guides_t<false, false, MOTION>(sc, cam, fa, samples, out, tri_prev, motion, stream);
-}
-void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream) {
-    launch_guides_m<false>(sc, cam, fa, samples, out, nullptr, nullptr, stream);
-}
-void launch_guides_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                          float4* motion, hipStream_t stream) {
-    launch_guides_m<true>(sc, cam, fa, samples, out, tri_prev, motion, stream);
-}
-
-// the launcher of the primitive-motion instances
-template <bool SDF, bool FILTER, bool TRI>
-static void launch_guides_p(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                            const PrimPrev& prims, float4* motion, hipStream_t stream) {
-    const size_t lds = (size_t)sc.stack_levels * 64 * sizeof(unsigned);
-    static size_t lds_attr = 0;
-    const void* k = FILTER ? reinterpret_cast<const void*>(&filtered_guides_prim_motion_kernel<TRI>) : reinterpret_cast<const void*>(&guide_prim_motion_kernel<SDF, TRI>);
-    if (lds > 65536u && lds > lds_attr) {
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        lds_attr = lds;
-    }
-    const unsigned tiles = (unsigned)(((fa.width + 7) / 8) * ((fa.rows + 7) / 8));
-    if constexpr (FILTER) hipLaunchKernelGGL((filtered_guides_prim_motion_kernel<TRI>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, prims, motion);
-    else hipLaunchKernelGGL((guide_prim_motion_kernel<SDF, TRI>), dim3(tiles), dim3(64), lds, stream, sc, cam, fa, samples, out, tri_prev, prims, motion);
-}
-template <bool TRI>
-static void launch_guides_pt(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                             const PrimPrev& prims, float4* motion, hipStream_t stream) {
-    if (fa.filter_kind != PRT_FILTER_NONE) launch_guides_p<false, true, TRI>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
-    else if (sc.n_sdfs) launch_guides_p<true, false, TRI>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
-    else launch_guides_p<false, false, TRI>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
-}
-void launch_guides_prim_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                               const PrimPrev& prims, float4* motion, hipStream_t stream) {
-    if (tri_prev) launch_guides_pt<true>(sc, cam, fa, samples, out, tri_prev, prims, motion, stream);
-    else launch_guides_pt<false>(sc, cam, fa, samples, out, nullptr, prims, motion, stream);
 }
 
 // ---- the filter ----------------------------------------------------------------------------------------------------------------------
-PT_DEV float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-PT_DEV bool dn_finite3(float4 c) { return isfinite(c.x) && isfinite(c.y) && isfinite(c.z); }
 PT_DEV int dn_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // var_source: 0 = stats plane {l, s2} with the path count of the state, 1 = 5x5 moments of the luminance (window clamped to the frame,
@@ -194,12 +163,7 @@ __global__ __launch_bounds__(256) void dn_var_kernel(const float4* __restrict__ 
     const float4 c = fb[id];
     float v = 0.0f;
     if (!spatial) {
-        const unsigned n = q4[id].x;
-        if (n >= 2u) {
-            const float2 a = adapt[id];
-            const float m = a.x / (float)n;
-            v = fmaxf((a.y - a.x * m) / ((float)n * (float)(n - 1u)), 0.0f);
-        }
+        v = dn_stats_var(q4, adapt, id);
     } else {
         float s1 = 0.0f, s2 = 0.0f, cnt = 0.0f;
         for (int dy = -2; dy <= 2; ++dy)
@@ -231,21 +195,6 @@ __global__ __launch_bounds__(256) void dn_gauss_kernel(const float4* __restrict_
 struct DnParams { int step; float sigma_l, sigma_n, sigma_z, inv_sigma_a2; };
 
 PT_DEV float dn_k(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
-
-// one-sided / central difference of z at p towards (x + sx, y + sy) and (x - sx, y - sy); a neighbour outside the frame or without
-// coverage drops out (both out: 0)
-PT_DEV float dn_grad1(const float4* __restrict__ gd, int x, int y, int sx, int sy, int W, int H, float zp) {
-    const int xa = x + sx, ya = y + sy, xb = x - sx, yb = y - sy;
-    const bool a_in = xa < W && ya < H, b_in = xb >= 0 && yb >= 0;
-    bool ha = false, hb = false;
-    float za = 0.0f, zb = 0.0f;
-    if (a_in) { const size_t q = (size_t)ya * W + xa; ha = gd[2 * q].w > 0.0f; za = gd[2 * q + 1].w; }
-    if (b_in) { const size_t q = (size_t)yb * W + xb; hb = gd[2 * q].w > 0.0f; zb = gd[2 * q + 1].w; }
-    if (ha && hb) return 0.5f * fabsf(za - zb);
-    if (ha) return fabsf(za - zp);
-    if (hb) return fabsf(zp - zb);
-    return 0.0f;
-}
 
 // alpha_src: null for every pass but the last, which writes {c', alpha of the framebuffer} instead of {c', v'}
 __global__ __launch_bounds__(256) void dn_atrous_kernel(const float4* __restrict__ in, const float* __restrict__ g, const float4* __restrict__ gd,
@@ -299,31 +248,34 @@ __global__ __launch_bounds__(256) void dn_atrous_kernel(const float4* __restrict
     out[id] = r;
 }
 
-// the filter's pieces for prt_denoise_temporal (pt_temporal.hip): {rgb, v} of the framebuffer into out, and a-trous pass i (its Gaussian
-// into g first) from `in` to `out` -- alpha_src non-null for the last pass
-void launch_denoise_var(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, int W, int H, float4* out, hipStream_t stream) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
-    hipLaunchKernelGGL(dn_var_kernel, grd, blk, 0, stream, fb, q4, adapt, spatial ? 1 : 0, W, H, out);
-}
-void launch_denoise_pass(const float4* in, const float4* guides, int W, int H, const prt_denoise_params& p, unsigned i, float* g,
-                         const float4* alpha_src, float4* out, hipStream_t stream) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
-    DnParams P;
-    P.step = 1 << i; P.sigma_l = p.sigma_l; P.sigma_n = p.sigma_n; P.sigma_z = p.sigma_z; P.inv_sigma_a2 = 1.0f / (p.sigma_a * p.sigma_a);
-    hipLaunchKernelGGL(dn_gauss_kernel, grd, blk, 0, stream, in, W, H, g);
-    hipLaunchKernelGGL(dn_atrous_kernel, grd, blk, 0, stream, in, g, guides, W, H, P, alpha_src, out);
+// ---- the chain: variance -> [reprojection, clamp] -> (gauss, a-trous) x passes ------------------------------------------------------------
+// The passes ping-pong from buf0 to buf1 and back.  So the frame's {rgb, v} goes into buf0 where the passes read it first, and into buf1 where
+// the reprojection stands in between: it reads {rgb, v} there and writes the passes' input into buf0.  Nobody else knows which
+static float4* var_plane(const FilterPlanes& pl, bool temporal) { return temporal ? pl.buf1 : pl.buf0; }
+
+void launch_filter_variance(const FilterPlanes& pl, bool temporal, const VarianceSource& src, hipStream_t stream) {
+    float4* var = var_plane(pl, temporal);
+    if (src.records) launch_records_import(src.records, pl.W, pl.H, pl.fb, pl.guides, var, src.no_stats, stream);
+    else hipLaunchKernelGGL(dn_var_kernel, dn_grid(pl.W, pl.H), dn_block(), 0, stream, pl.fb, src.q4, src.adapt, src.spatial ? 1 : 0, pl.W, pl.H, var);
 }
 
-// passes of the filter: var -> (gauss, a-trous) x passes, ping-pong between buf0 and buf1, the last pass into `out` (rgba of the frame)
-void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
-                    const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream) {
-    launch_denoise_var(fb, q4, adapt, spatial, W, H, buf0, stream);
-    float4* cur = buf0;
-    float4* nxt = buf1;
+void launch_filter_chain(const FilterPlanes& pl, const prt_denoise_params& p, const prt_temporal_params* t, const DevCamera* cam,
+                         const TemporalHistory* h, const float4* motion, hipStream_t stream) {
+    const dim3 blk = dn_block(), grd = dn_grid(pl.W, pl.H);
+    if (t) launch_temporal_front(pl, var_plane(pl, true), pl.buf0, *t, *cam, *h, motion, stream);
+    DnParams P;
+    P.sigma_l = p.sigma_l; P.sigma_n = p.sigma_n; P.sigma_z = p.sigma_z; P.inv_sigma_a2 = 1.0f / (p.sigma_a * p.sigma_a);
+    float4* cur = pl.buf0;
+    float4* nxt = pl.buf1;
     for (unsigned i = 0; i < p.passes; ++i) {
+        // pass i: step 2^i, the Gaussian of v first; the last one writes the frame's rgba -- its colour with the framebuffer's alpha
         const bool last = i + 1 == p.passes;
-        launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, last ? out : nxt, stream);
-        float4* t = cur; cur = nxt; nxt = t;
+        float4* dst = last ? pl.out : nxt;
+        P.step = 1 << i;
+        hipLaunchKernelGGL(dn_gauss_kernel, grd, blk, 0, stream, cur, pl.W, pl.H, pl.g);
+        hipLaunchKernelGGL(dn_atrous_kernel, grd, blk, 0, stream, cur, pl.g, pl.guides, pl.W, pl.H, P, last ? pl.fb : nullptr, dst);
+        if (i == 0 && t && t->feedback == PRT_TEMPORAL_FEEDBACK_ATROUS) launch_temporal_feedback(dst, pl.W, pl.H, h->cn, stream);
+        float4* tmp = cur; cur = nxt; nxt = tmp;
     }
 }
 

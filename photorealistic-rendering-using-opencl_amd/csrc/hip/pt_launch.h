@@ -54,27 +54,27 @@ void launch_count(const DevState& S, size_t n, unsigned spp, unsigned long long*
 // in increasing order, into list; their number into *count (device).  wave_off: ceil(n / 64) words of scratch
 void launch_live_list(const DevState& S, size_t n, unsigned max_spp, uint32_t* wave_off, uint32_t* list, uint32_t* count, hipStream_t stream);
 // pt_denoise.hip.  prt_render_guides: `samples` guide samples per pixel of the frame part of `fa` into out (2 float4 per pixel: {albedo, coverage},
-// {normal, depth}).  prt_denoise: the filter of prt.h on the full frame W x H, out = filtered rgba (alpha of fb); buf0 / buf1: W x H float4,
-// g: W x H float of scratch
-void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, hipStream_t stream);
-// ... and the motion plane (prt.h prt_set_motion; one float4 {D, m} per pixel) from tri_prev, the triangle records (one per slot, as
-// sc.tri_geom) of the geometry before the update(s): the motion instances of the guide kernels
-void launch_guides_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                          float4* motion, hipStream_t stream);
-// ... with a primitive snapshot pending (prt.h prt_update_primitives): prims the sphere / SDF / quad tables before the update(s) (pt_prims.h);
-// tri_prev null = no triangle snapshot pending: the instances without the triangle term
+// {normal, depth}).  tri_prev non-null: a triangle snapshot is pending -- the triangle records (one per slot, as sc.tri_geom) of the geometry
+// before the update(s); prims non-null: a primitive snapshot is pending (prt.h prt_update_primitives) -- the sphere / SDF / quad tables before
+// the update(s) (pt_prims.h).  With either, the motion instances of the guide kernels, which also write the motion plane (prt.h
+// prt_set_motion; one float4 {D, m} per pixel); the two snapshots are independent, and without both `motion` is not written
 struct PrimPrev;
-void launch_guides_prim_motion(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
-                               const PrimPrev& prims, float4* motion, hipStream_t stream);
-void launch_denoise(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
-                    const prt_denoise_params& p, float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream);
-// ... its pieces: dn_var_kernel's {rgb, v} into out; a-trous pass i (step 2^i, its Gaussian into g first) from `in` into `out`, with the
-// framebuffer's alpha when alpha_src is non-null (the last pass)
-void launch_denoise_var(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, int W, int H, float4* out, hipStream_t stream);
-void launch_denoise_pass(const float4* in, const float4* guides, int W, int H, const prt_denoise_params& p, unsigned i, float* g,
-                         const float4* alpha_src, float4* out, hipStream_t stream);
-// pt_temporal.hip.  prt_denoise_temporal: the previous call's history (read) and the halves this call writes; `valid` false = empty history.
-// motion (both launchers): null, or the motion plane of `guides` (W x H float4 {D, m}, device)
+void launch_guides(const DevScene& sc, const DevCamera& cam, const FrameArgs& fa, unsigned samples, float4* out, const TriGeom* tri_prev,
+                   const PrimPrev* prims, float4* motion, hipStream_t stream);
+// the W x H planes of one filter call (prt_denoise and its temporal and record variants): the framebuffer {c, alpha}, the guides (2 float4
+// per pixel), two ping-pong planes of {rgb, v}, the Gaussian of v, and the filtered rgba (alpha of fb).  All device memory; the record calls
+// write fb and guides themselves (VarianceSource)
+struct FilterPlanes { float4* fb; float4* guides; float4* buf0; float4* buf1; float* g; float4* out; int W, H; };
+// what the variance step takes the frame's {rgb, v} from.  records (W x H records of prt.h, device): rec_import_kernel, which also writes
+// planes.fb and planes.guides, and 1 into *no_stats if any record has has_stats != 1 (the caller zeroes the word first).  Otherwise planes.fb
+// as it stands: spatial, the 5x5 moments of its luminance, else the stats plane adapt with the path counts q4
+struct VarianceSource {
+    bool spatial = false; const uint4* q4 = nullptr; const float2* adapt = nullptr;
+    const float4* records = nullptr; unsigned* no_stats = nullptr;
+};
+// the variance step: {rgb, v} of the frame to where launch_filter_chain, called with (temporal) or without temporal parameters, reads it
+void launch_filter_variance(const FilterPlanes& planes, bool temporal, const VarianceSource& src, hipStream_t stream);
+// pt_temporal.hip.  prt_denoise_temporal: the previous call's history (read) and the halves this call writes; `valid` false = empty history
 struct TemporalHistory {
     const float4* cn_prev;          // {c.rgb, n} per pixel
     const float4* m_prev;           // {m1, m2, v, 0}
@@ -90,16 +90,18 @@ struct TemporalHistory {
     uint32_t fast_cap = 0, radius = 0;
     float k = 0.0f;
 };
-void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
-                             const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
-                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream, const float4* motion = nullptr);
-// ... everything behind its variance step: buf1 holds the frame's {rgb, v} (dn_var_kernel's output, or a caller's) on entry
-void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, int H, const prt_denoise_params& p, const prt_temporal_params& t,
-                                 const DevCamera& cam, const TemporalHistory& h, float4* buf0, float4* buf1, float* g, float4* out,
-                                 hipStream_t stream, const float4* motion = nullptr);
+// everything behind the variance step.  t null: (gauss, a-trous) x p.passes, ping-pong between buf0 and buf1, the last pass into planes.out
+// with the framebuffer's alpha.  t non-null (cam and h with it; motion: null, or the motion plane of the guides, W x H float4 {D, m}): the
+// reprojection in front, the clamp behind it if h->fast is set, and under PRT_TEMPORAL_FEEDBACK_ATROUS pass 0's colour into h->cn
+void launch_filter_chain(const FilterPlanes& planes, const prt_denoise_params& p, const prt_temporal_params* t, const DevCamera* cam,
+                         const TemporalHistory* h, const float4* motion, hipStream_t stream);
+// ... its temporal steps (the kernels of pt_temporal.hip, for the chain alone): the reprojection of `var` ({rgb, v} of the frame) into `in`
+// (the passes' input) and the new history, then the clamp; and the feedback of pass 0's output
+void launch_temporal_front(const FilterPlanes& planes, const float4* var, float4* in, const prt_temporal_params& t, const DevCamera& cam,
+                           const TemporalHistory& h, const float4* motion, hipStream_t stream);
+void launch_temporal_feedback(const float4* pass0, int W, int H, float4* h_cn, hipStream_t stream);
 // pt_records.hip.  prt_export_denoise_inputs: the records (prt.h: 4 float4 per pixel) of a W x rows frame part; adapt null = no stats
-// (v = 0, has_stats = 0).  prt_denoise_records: W x H records into the planes the filter reads -- fb {c, alpha}, guides (2 float4 per
-// pixel), var {c, v of the record} -- and 1 into *no_stats if any record has has_stats != 1 (the caller zeroes the word first)
+// (v = 0, has_stats = 0).  launch_records_import: VarianceSource::records, for launch_filter_variance alone -- var the plane of {c, v of the record}
 void launch_records_export(const float4* fb, const uint4* q4, const float2* adapt, const float4* guides, int W, int rows, float4* records,
                            hipStream_t stream);
 void launch_records_import(const float4* records, int W, int H, float4* fb, float4* guides, float4* var, unsigned* no_stats, hipStream_t stream);

@@ -8,28 +8,20 @@
 //
 // 16x16 workgroups, one lane per pixel like the filter's kernels; a lane moves its record as four float4 (64 contiguous bytes, a wave's
 // rows are contiguous runs of 1 KiB).  Both kernels are copies with a handful of flops: 112 bytes per pixel, memory bound.
-#include "pt_device.h"
+#include "pt_denoise_dev.h"
 #include "pt_launch.h"
 
 namespace prt {
 
-// adapt null: the frame has no stats plane that belongs to its picture (v = 0, has_stats = 0).  v is dn_var_kernel's expression
-// (pt_denoise.hip), operation for operation
+// adapt null: the frame has no stats plane that belongs to its picture (v = 0, has_stats = 0).  v is dn_var_kernel's (pt_denoise.hip):
+// dn_stats_var
 __global__ __launch_bounds__(256) void rec_export_kernel(const float4* __restrict__ fb, const uint4* __restrict__ q4,
                                                          const float2* __restrict__ adapt, const float4* __restrict__ gd, int W, int H,
                                                          float4* __restrict__ rec) {
     const int x = (int)(blockIdx.x * 16 + threadIdx.x), y = (int)(blockIdx.y * 16 + threadIdx.y);
     if (x >= W || y >= H) return;
     const size_t id = (size_t)y * W + x;
-    float v = 0.0f;
-    if (adapt) {
-        const unsigned n = q4[id].x;
-        if (n >= 2u) {
-            const float2 a = adapt[id];
-            const float m = a.x / (float)n;
-            v = fmaxf((a.y - a.x * m) / ((float)n * (float)(n - 1u)), 0.0f);
-        }
-    }
+    const float v = adapt ? dn_stats_var(q4, adapt, id) : 0.0f;
     rec[4 * id] = fb[id];
     rec[4 * id + 1] = gd[2 * id];
     rec[4 * id + 2] = gd[2 * id + 1];
@@ -52,12 +44,10 @@ __global__ __launch_bounds__(256) void rec_import_kernel(const float4* __restric
 
 void launch_records_export(const float4* fb, const uint4* q4, const float2* adapt, const float4* guides, int W, int rows, float4* records,
                            hipStream_t stream) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((rows + 15) / 16));
-    hipLaunchKernelGGL(rec_export_kernel, grd, blk, 0, stream, fb, q4, adapt, guides, W, rows, records);
+    hipLaunchKernelGGL(rec_export_kernel, dn_grid(W, rows), dn_block(), 0, stream, fb, q4, adapt, guides, W, rows, records);
 }
 void launch_records_import(const float4* records, int W, int H, float4* fb, float4* guides, float4* var, unsigned* no_stats, hipStream_t stream) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
-    hipLaunchKernelGGL(rec_import_kernel, grd, blk, 0, stream, records, W, H, fb, guides, var, no_stats);
+    hipLaunchKernelGGL(rec_import_kernel, dn_grid(W, H), dn_block(), 0, stream, records, W, H, fb, guides, var, no_stats);
 }
 
 }  // namespace prt

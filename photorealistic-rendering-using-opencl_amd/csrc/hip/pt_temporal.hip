@@ -13,30 +13,13 @@
 // The history is double-buffered (taps read neighbours: never updated in place); the caller flips the two halves after each call.  16x16
 // workgroups, one lane per pixel, straight global loads as the filter's kernels: at 1080p the planes a call touches (~100 B per pixel) stay
 // in the L2 / Infinity Cache.  A pixel reads its 2x2 taps (2 guide float4 + 2 history float4 each) and its own and four neighbours' guides.
-#include "pt_device.h"
+#include "pt_denoise_dev.h"
 #include "pt_launch.h"
 
 namespace prt {
 using namespace dev;
 
 struct TmParams { float alpha_color, alpha_moments, tau_z, cos_n, cap; int has_hist; };
-
-PT_DEV float tm_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-PT_DEV bool tm_finite3(float4 c) { return isfinite(c.x) && isfinite(c.y) && isfinite(c.z); }
-
-// prt_denoise's depth gradient (pt_denoise.hip dn_grad1): central / one-sided difference of z towards (x + sx, y + sy) and (x - sx, y - sy)
-PT_DEV float tm_grad1(const float4* __restrict__ gd, int x, int y, int sx, int sy, int W, int H, float zp) {
-    const int xa = x + sx, ya = y + sy, xb = x - sx, yb = y - sy;
-    const bool a_in = xa < W && ya < H, b_in = xb >= 0 && yb >= 0;
-    bool ha = false, hb = false;
-    float za = 0.0f, zb = 0.0f;
-    if (a_in) { const size_t q = (size_t)ya * W + xa; ha = gd[2 * q].w > 0.0f; za = gd[2 * q + 1].w; }
-    if (b_in) { const size_t q = (size_t)yb * W + xb; hb = gd[2 * q].w > 0.0f; zb = gd[2 * q + 1].w; }
-    if (ha && hb) return 0.5f * fabsf(za - zb);
-    if (ha) return fabsf(za - zp);
-    if (hb) return fabsf(zp - zb);
-    return 0.0f;
-}
 
 // fb: framebuffer; var: dn_var_kernel's {c, v} of the current frame (v for n < 4); gd / gd_prev: current / previous guides (2 float4 per
 // pixel); h_cn_prev / h_m_prev: previous history {c, n} / {m1, m2, v, 0}.  Out: {c_i, v} and the new history.
@@ -57,10 +40,10 @@ __global__ __launch_bounds__(256) void tm_reproject_kernel(const float4* __restr
     if (x >= W || y >= H) return;
     const size_t id = (size_t)y * W + x;
     const float4 c = fb[id];
-    const float L = tm_lum(c.x, c.y, c.z);
+    const float L = dn_lum(c.x, c.y, c.z);
     float sw = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, h1 = 0.0f, h2 = 0.0f;
     float fr = 0.0f, fg = 0.0f, fbl = 0.0f;
-    if (P.has_hist && tm_finite3(c)) {
+    if (P.has_hist && dn_finite3(c)) {
         const float4 ap = gd[2 * id], np = gd[2 * id + 1];
         const bool covp = ap.w > 0.0f;
         // create_cam_ray's centre ray of the pixel (pt_device.h), then the point at its guide depth
@@ -88,7 +71,7 @@ __global__ __launch_bounds__(256) void tm_reproject_kernel(const float4* __restr
                 const float x0f = floorf(xp), y0f = floorf(yp);
                 const int x0 = (int)x0f, y0 = (int)y0f;
                 const float fx = xp - x0f, fy = yp - y0f;
-                const float grad = covp ? fmaxf(tm_grad1(gd, x, y, 1, 0, W, H, np.w), tm_grad1(gd, x, y, 0, 1, W, H, np.w)) : 0.0f;
+                const float grad = covp ? fmaxf(dn_grad1(gd, x, y, 1, 0, W, H, np.w), dn_grad1(gd, x, y, 0, 1, W, H, np.w)) : 0.0f;
                 const float ztol = P.tau_z * dist + grad;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
@@ -96,7 +79,7 @@ __global__ __launch_bounds__(256) void tm_reproject_kernel(const float4* __restr
                     if (tx < 0 || tx >= W || ty < 0 || ty >= H) continue;
                     const size_t qi = (size_t)ty * W + tx;
                     const float4 hc = h_cn_prev[qi];
-                    if (!tm_finite3(hc)) continue;
+                    if (!dn_finite3(hc)) continue;
                     if ((gd_prev[2 * qi].w > 0.0f) != covp) continue;
                     if (covp) {
                         const float4 nq = gd_prev[2 * qi + 1];
@@ -160,7 +143,7 @@ __global__ __launch_bounds__(256) void tm_clamp_kernel(const float4* __restrict_
         float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
             const float4 g = fast[(size_t)gy * W + gx];
-            if (tm_finite3(g)) f = make_float4(g.x, g.y, g.z, 1.0f);
+            if (dn_finite3(g)) f = make_float4(g.x, g.y, g.z, 1.0f);
         }
         tile[i] = f;                                                   // an invalid texel is all zeros
     }
@@ -170,7 +153,7 @@ __global__ __launch_bounds__(256) void tm_clamp_kernel(const float4* __restrict_
     const size_t id = (size_t)y * W + x;
     if (!(fast[id].w > 0.0f)) return;                                  // no history: the pixel passes through
     const float4 cn = h_cn[id];
-    if (!tm_finite3(cn)) return;
+    if (!dn_finite3(cn)) return;
     const float4* t0 = tile + threadIdx.y * T + threadIdx.x;           // the window's first texel: (x - R, y - R)
     float m = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
 #pragma unroll
@@ -210,41 +193,28 @@ __global__ __launch_bounds__(256) void tm_feedback_kernel(const float4* __restri
     h_cn[id] = make_float4(p.x, p.y, p.z, h_cn[id].w);
 }
 
-void launch_denoise_temporal(const float4* fb, const uint4* q4, const float2* adapt, bool spatial, const float4* guides, int W, int H,
-                             const prt_denoise_params& p, const prt_temporal_params& t, const DevCamera& cam, const TemporalHistory& h,
-                             float4* buf0, float4* buf1, float* g, float4* out, hipStream_t stream, const float4* motion) {
-    launch_denoise_var(fb, q4, adapt, spatial, W, H, buf1, stream);
-    launch_denoise_temporal_var(fb, guides, W, H, p, t, cam, h, buf0, buf1, g, out, stream, motion);
-}
-
-void launch_denoise_temporal_var(const float4* fb, const float4* guides, int W, int H, const prt_denoise_params& p, const prt_temporal_params& t,
-                                 const DevCamera& cam, const TemporalHistory& h, float4* buf0, float4* buf1, float* g, float4* out,
-                                 hipStream_t stream, const float4* motion) {
-    const dim3 blk(16, 16), grd((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+// the temporal steps of launch_filter_chain (pt_denoise.hip), which says where `var` and `in` are
+void launch_temporal_front(const FilterPlanes& pl, const float4* var, float4* in, const prt_temporal_params& t, const DevCamera& cam,
+                           const TemporalHistory& h, const float4* motion, hipStream_t stream) {
+    const dim3 blk = dn_block(), grd = dn_grid(pl.W, pl.H);
+    const int W = pl.W, H = pl.H;
     TmParams P;
     P.alpha_color = t.alpha_color; P.alpha_moments = t.alpha_moments; P.tau_z = t.tau_z; P.cos_n = t.cos_n; P.cap = (float)t.history_cap;
     P.has_hist = h.valid ? 1 : 0;
     if (!h.fast) {
-        hipLaunchKernelGGL(tm_reproject_kernel<false>, grd, blk, 0, stream, fb, buf1, guides, h.guides_prev, h.cn_prev, h.m_prev, cam, h.cam_prev,
-                           W, H, P, buf0, h.cn, h.m, motion, nullptr, nullptr, 0.0f);
+        hipLaunchKernelGGL(tm_reproject_kernel<false>, grd, blk, 0, stream, pl.fb, var, pl.guides, h.guides_prev, h.cn_prev, h.m_prev, cam,
+                           h.cam_prev, W, H, P, in, h.cn, h.m, motion, nullptr, nullptr, 0.0f);
     } else {
         const float fast_cap = (float)h.fast_cap;
-        hipLaunchKernelGGL(tm_reproject_kernel<true>, grd, blk, 0, stream, fb, buf1, guides, h.guides_prev, h.cn_prev, h.m_prev, cam,
-                           h.cam_prev, W, H, P, buf0, h.cn, h.m, motion, h.fast_prev, h.fast, fast_cap);
-        if (h.radius == 1) hipLaunchKernelGGL(tm_clamp_kernel<1>, grd, blk, 0, stream, h.fast, W, H, h.k, fast_cap, buf0, h.cn, h.m);
-        else if (h.radius == 2) hipLaunchKernelGGL(tm_clamp_kernel<2>, grd, blk, 0, stream, h.fast, W, H, h.k, fast_cap, buf0, h.cn, h.m);
-        else hipLaunchKernelGGL(tm_clamp_kernel<3>, grd, blk, 0, stream, h.fast, W, H, h.k, fast_cap, buf0, h.cn, h.m);
+        hipLaunchKernelGGL(tm_reproject_kernel<true>, grd, blk, 0, stream, pl.fb, var, pl.guides, h.guides_prev, h.cn_prev, h.m_prev, cam,
+                           h.cam_prev, W, H, P, in, h.cn, h.m, motion, h.fast_prev, h.fast, fast_cap);
+        if (h.radius == 1) hipLaunchKernelGGL(tm_clamp_kernel<1>, grd, blk, 0, stream, h.fast, W, H, h.k, fast_cap, in, h.cn, h.m);
+        else if (h.radius == 2) hipLaunchKernelGGL(tm_clamp_kernel<2>, grd, blk, 0, stream, h.fast, W, H, h.k, fast_cap, in, h.cn, h.m);
+        else hipLaunchKernelGGL(tm_clamp_kernel<3>, grd, blk, 0, stream, h.fast, W, H, h.k, fast_cap, in, h.cn, h.m);
     }
-    float4* cur = buf0;
-    float4* nxt = buf1;
-    for (unsigned i = 0; i < p.passes; ++i) {
-        const bool last = i + 1 == p.passes;
-        float4* dst = last ? out : nxt;
-        launch_denoise_pass(cur, guides, W, H, p, i, g, last ? fb : nullptr, dst, stream);
-        if (i == 0 && t.feedback == PRT_TEMPORAL_FEEDBACK_ATROUS)
-            hipLaunchKernelGGL(tm_feedback_kernel, grd, blk, 0, stream, dst, W, H, h.cn);
-        float4* tmp = cur; cur = nxt; nxt = tmp;
-    }
+}
+void launch_temporal_feedback(const float4* pass0, int W, int H, float4* h_cn, hipStream_t stream) {
+    hipLaunchKernelGGL(tm_feedback_kernel, dn_grid(W, H), dn_block(), 0, stream, pass0, W, H, h_cn);
 }
 
 }  // namespace prt

@@ -8,6 +8,12 @@ the minimum of every round.  Kernel time: the durations of the reprojection (bot
 passes of the same calls, from `rocprofv3 --kernel-trace --stats` in a run of its own.  One JSON document on stdout (and into --out).
 
     python tools/response_rate.py [--parent-root DIR] [--out profiles/r26_response.json]
+
+--doors: the same scheme over every filtering door instead -- prt_denoise, prt_denoise_temporal with the response off and on,
+prt_denoise_records and prt_denoise_records_temporal (records of the same frame, output into device memory): per door and checkout the
+pooled calls' median and quartiles, and the kernel names one call of each door launches, in order, from one kernel trace per checkout.
+
+    python tools/response_rate.py --doors --parent-root DIR
 """
 import argparse
 import importlib
@@ -54,19 +60,97 @@ def _call(r):
     assert rc == 0, rc
 
 
+# --doors: label -> (door, the response setting it runs under; None: --on)
+DOORS = {"prt_denoise": ("denoise", "off"), "prt_denoise_temporal, off": ("temporal", "off"), "prt_denoise_temporal, on": ("temporal", None),
+         "prt_denoise_records": ("records", "off"), "prt_denoise_records_temporal": ("records_temporal", "off")}
+
+
+def _door(prt, r, door, W, H):
+    """one call of a door on r's frame as a closure: default parameters, no host output (the record doors write device memory)"""
+    import ctypes as C
+    lib, keep = r.lib, ()
+    if door == "temporal":
+        return lambda: _call(r)
+    if door == "denoise":
+        def fn():
+            return lib.prt_denoise(r.ctx, None, None, None)
+    else:
+        import torch
+        records = torch.zeros((H, W, 16), dtype=torch.float32, device="cuda:0")
+        out = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        r.export_denoise_inputs(records)
+        rec, dst, cam = C.c_void_p(records.data_ptr()), C.c_void_p(out.data_ptr()), prt.default_camera(W, H)
+        keep = (records, out)
+
+        def fn():
+            if door == "records":
+                return lib.prt_denoise_records(r.ctx, None, W, H, rec, dst, None, None)
+            return lib.prt_denoise_records_temporal(r.ctx, None, None, C.byref(cam), W, H, rec, dst, None, None)
+
+    def call(keep=keep):                                                 # (the tensors live as long as the closure)
+        rc = fn()
+        assert rc == 0, rc
+    return call
+
+
 def arm_phase(a):
     prt, r = _frame(a.root, a.width, a.height)
     _set(r, a.response)
+    call = _door(prt, r, a.door, a.width, a.height)
     for _ in range(4):
-        _call(r)
+        call()
     ms = []
     for _ in range(a.calls):
         r.synchronize()
         t = time.perf_counter()
-        _call(r)                                                         # (complete on return: the call ends with a stream synchronise)
+        call()                                                           # (complete on return: the call ends with a stream synchronise)
         ms.append(1e3 * (time.perf_counter() - t))
     r.close()
-    print(json.dumps({"median_ms": round(float(np.median(ms)), 4), "min_ms": round(min(ms), 4)}))
+    print(json.dumps({"median_ms": round(float(np.median(ms)), 4), "min_ms": round(min(ms), 4), "ms": [round(x, 4) for x in ms]}))
+
+
+def sequence_phase(a):
+    """one call of every door, each behind a one-sample guide render: the guide kernel marks where a door's launches begin in the trace"""
+    prt, r = _frame(a.root, a.width, a.height)
+    calls = [(response or a.on, _door(prt, r, door, a.width, a.height)) for door, response in DOORS.values()]     # (the exports run here)
+    for response, call in calls:
+        _set(r, response)
+        r.render_guides(1)
+        call()
+    r.render_guides(1)
+    r.close()
+
+
+def door_sequences(a, root):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from _trace import kernel_rows
+    rows = kernel_rows(["--phase", "sequence", "--root", root, "--on", a.on, "--width", str(a.width), "--height", str(a.height)], "doors", a.timeout)
+    names = [name.split("(")[0].replace("prt::", "").replace("void ", "") for name, _, _ in rows]
+    marks = [i for i, n in enumerate(names) if "guide" in n][-(len(DOORS) + 1):]
+    return {label: names[b + 1:e] for label, b, e in zip(DOORS, marks[:-1], marks[1:])}
+
+
+def doors_main(a):
+    roots = [("tree", ROOT)] + ([("parent", os.path.abspath(a.parent_root))] if a.parent_root else [])
+    doc = {"frame": [a.width, a.height], "calls_per_round": a.calls, "rounds": a.rounds, "wall ms per call (host clock; every call ends with a stream synchronise)": {},
+           "kernels of one call, in launch order": {}}
+    for label, (door, response) in DOORS.items():
+        ms = {name: [] for name, _ in roots}
+        for _ in range(a.rounds):
+            for name, root in reversed(roots):
+                cmd = [sys.executable, os.path.abspath(__file__), "--phase", "arm", "--root", root, "--door", door, "--response", response or a.on,
+                       "--width", str(a.width), "--height", str(a.height), "--calls", str(a.calls)]
+                p = subprocess.run(cmd, check=True, timeout=a.timeout, capture_output=True, text=True)
+                ms[name] += json.loads(p.stdout.strip().splitlines()[-1])["ms"]
+        doc["wall ms per call (host clock; every call ends with a stream synchronise)"][label] = {
+            name: dict(zip(("q25", "median", "q75"), (round(float(q), 4) for q in np.percentile(v, (25, 50, 75))))) for name, v in ms.items()}
+    for name, root in roots:
+        doc["kernels of one call, in launch order"][name] = door_sequences(a, root)
+    if a.parent_root:
+        seq = doc["kernels of one call, in launch order"]
+        doc["launch sequences equal the parent's"] = seq["tree"] == seq["parent"]
+    return doc
 
 
 def kernels_phase(a):
@@ -98,7 +182,9 @@ def kernel_times(a, root=ROOT):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--phase", default="all", choices=["all", "arm", "kernels"])
+    ap.add_argument("--phase", default="all", choices=["all", "arm", "kernels", "sequence"])
+    ap.add_argument("--doors", action="store_true", help="every filtering door instead of the response's cost")
+    ap.add_argument("--door", default="temporal", choices=["denoise", "temporal", "records", "records_temporal"], help="(arm phase) the call timed")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--calls", type=int, default=40)
@@ -115,6 +201,15 @@ def main():
         return arm_phase(a)
     if a.phase == "kernels":
         return kernels_phase(a)
+    if a.phase == "sequence":
+        return sequence_phase(a)
+    if a.doors:
+        text = json.dumps(doors_main(a), indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(text + "\n")
+        return
     arms = [("tree, off", ROOT, "off"), ("tree, on (%s)" % a.on, ROOT, a.on)]
     if a.parent_root:
         arms.insert(0, ("parent, off", os.path.abspath(a.parent_root), "off"))
