@@ -10,8 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, VARIANTS, variant_camera, variant_config
-from support import bytes_rows as _bytes, pkg as _pkg
+from conftest import ROOT, variant_camera
+from support import bytes_rows as _bytes, pkg as _pkg, variant_case
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 HIP = os.path.join(PKG, "csrc", "hip")
@@ -103,12 +103,7 @@ def test_adaptive_build_keeps_uniform_loads_scalar(tmp_path):
 # ---- on the GPU ------------------------------------------------------------------------------------------------------------------------
 
 def _setup(prt, variant, W, H):
-    scene_json, phase, use_env = VARIANTS[variant]
-    scene = prt.HostScene(scene_json)
-    cfg = variant_config(scene, variant)
-    cfg.phase_function = phase
-    cam = variant_camera(prt, variant, W, H)
-    env = prt.make_sky(64, 32) if use_env else None
+    scene, cfg, cam, env = variant_case(prt, variant, W, H)
     r = prt.Renderer(cfg, device=0)
     r.upload_scene(scene)
     if env is not None:

@@ -11,18 +11,14 @@ and the policy against the sequence of calls it stands for -- update, prt_bvh_co
 import ctypes as C
 import os
 import struct
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import PKG_NAME, ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_refit import Case, _bytes, deform                                             # noqa: E402
-from test_rebuild import _leaf_root_desc, _soup                                         # noqa: E402
+from cases import (callers_tree, Case, _chain_desc, _leaf_root_desc, morph_case, pose_context, _skin, skin_case, _soup, T_TEAPOT,
+                   teapot as posed_teapot)
+from support import assert_api, bytes_flat as _bytes
 
 f32, f64 = np.float32, np.float64
 INNER = 0xFFFFFFFF
@@ -129,11 +125,7 @@ def mirror_nodes(nodes):
 # ---- CPU: the bodies on the host -------------------------------------------------------------------------------------------------------------
 
 def test_api_is_declared_exported_and_bound(prt):
-    header = open(os.path.join(ROOT, "include", "prt.h")).read()
-    lib = prt.load_library()
-    for name in NEW_API:
-        assert ("int %s(prt_ctx*" % name) in header, name
-        assert hasattr(lib, name), name
+    assert_api(NEW_API, prt)
     assert callable(prt.Renderer.bvh_cost) and callable(prt.Renderer.set_rebuild_policy) and callable(prt.Renderer.rebuild_report)
     assert "hip/pt_cost.hip" in open(os.path.join(ROOT, PKG_NAME, "build.py")).read()
     assert C.sizeof(prt._capi.RebuildPolicy) == 8 and C.sizeof(prt._capi.RebuildReport) == 24
@@ -264,7 +256,7 @@ _cache = {}
 
 
 def teapot(prt):
-    """cornell_coat through test_refit.Case with a camera of this file's frame size"""
+    """cornell_coat through cases.Case with a camera of this file's frame size"""
     if "teapot" not in _cache:
         from conftest import variant_camera
         case = Case(prt, "cornell_coat")
@@ -419,7 +411,6 @@ def test_device_cost_equals_the_mirror(prt, emu, variant):
 
 @pytest.mark.gpu
 def test_cost_of_a_tree_too_deep_to_refit(prt, emu):
-    from test_refit import _chain_desc
     case = Case(prt, "cornell_coat", seed=11)
     desc, keep = _chain_desc(prt, case.scene, 300)
     p = emu.Packed(case.cfg, desc)
@@ -526,10 +517,8 @@ def test_policy_equals_the_manual_sequence(prt, build_emu, motion):
 @pytest.mark.parametrize("through", ["skin", "morph"])
 def test_policy_through_a_pose_and_a_morph(prt, build_emu, through):
     """one frame that triggers, through pose(rebuild=False) on a skin and through morph(rebuild=False): the rebuild is over the posed buffers"""
-    import test_pose
-    import test_morph
-    case = test_pose.teapot(prt)
-    s = test_pose.skin_case(prt, test_pose.T_TEAPOT, 4) if through == "skin" else test_morph.morph_case(prt, test_pose.T_TEAPOT, 3)
+    case = posed_teapot(prt)
+    s = skin_case(prt, T_TEAPOT, 4) if through == "skin" else morph_case(prt, T_TEAPOT, 3)
     p = build_emu.Packed(case.cfg, case.desc)
     first = mirror_packed(p.get(), p.root_is_leaf, p.root_leaf_count)
     assert p.update(s["v"], s["n"]) == 0
@@ -537,13 +526,13 @@ def test_policy_through_a_pose_and_a_morph(prt, build_emu, through):
     assert planned >= 1.05 * _limit_times(first), "the frame does not pass the limit by 5 %"
     got = []
     for policy in (True, False):
-        r = test_pose._context(prt, s, leaf_root=False)
+        r = pose_context(prt, s, leaf_root=False)
         r.set_camera(teapot(prt).cam)
         r.resize(W, H)
         if through == "skin":
-            test_pose._skin(r, s)
+            _skin(r, s)
         else:
-            test_morph._set(r, s)
+            r.set_morph_targets(s["v0"], s["n0"], s["targets"])          # (tests/test_morph.py's _set)
         if policy:
             r.set_rebuild_policy(LIMIT, MAX_LEAF)
         nodes_before = r.bvh_node_count
@@ -658,7 +647,6 @@ def test_refusals_and_lifetime(prt, oracle):
     r.close()
     # a caller's tree that references 100 of T triangles, normals None: the update that triggers returns the rebuild's refusal, and the scene
     # is the refitted one -- what a context without a policy holds after the same update
-    from test_emu import callers_tree
     scene, cdesc, keep = callers_tree(prt, oracle)
     a, b = _context(prt, case, cdesc), _context(prt, case, cdesc)
     a.update_vertices(frames[2][0], None)                                  # (a pose in which the caller's tree is cheap: the baseline)

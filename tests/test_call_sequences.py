@@ -16,20 +16,17 @@ every (creator, call) pair of the table occurs in one of them with the state rea
 by anything in between (a checkpoint's own calls included), and followed by a checkpoint."""
 import hashlib
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_rebuild import DEFAULT_LEAF, FRAMES, H, NODE_T, W, Teapot, _assert_same, _bytes, _leaf_root_desc, _soup, _with, deform, mirror_build  # noqa: E402
-from test_refit import mirror_refit  # noqa: E402
+from cases import deform, desc_with, _leaf_root_desc, meshes_of, move_quad, move_sdf, move_sphere, random_rays, _soup, Teapot, TILT, _with
+from mirrors import DEFAULT_LEAF, mirror_build, mirror_normals, mirror_refit, mirror_weld, NODE_T
+from support import assert_same_render as _assert_same, bytes_flat as _bytes
 
 f32 = np.float32
+W, H, FRAMES = Teapot.W, Teapot.H, Teapot.FRAMES
 OK, INVALID, NOT_READY, UNSUPPORTED = 0, -1, -4, -5
 ADAPT_MIN, ADAPT_MAX, ADAPT_REL = 8, 64, 0.2          # tests/test_adaptive.py MIN, MAX, REL
 ADAPT_FRAMES = ADAPT_MAX * 16 + 64                    # ... and its _frames(MAX)
@@ -106,7 +103,7 @@ class Scene:
                 a.setflags(write=False)
 
     def pose(self, name):
-        """(vertices, normals) of a pose: the uploaded ones, or test_rebuild.deform of them"""
+        """(vertices, normals) of a pose: the uploaded ones, or cases.deform of them"""
         if name not in self._poses:
             v, n = (self.v0, self.n0) if POSES[name] is None else deform(self.v0, self.n0, POSES[name])
             v.setflags(write=False)
@@ -117,7 +114,6 @@ class Scene:
 
 def _moved(m0, counts, which):
     """the primitive records in a moved pose: every sphere, SDF primitive and the last quad (test_update_primitives' movers)"""
-    from test_update_primitives import TILT, move_quad, move_sdf, move_sphere
     m = m0.copy()
     s = 1.0 if which == "mB" else -0.6
     n_sph, n_sdf, n_quad = int(counts[0]), int(counts[1]), int(counts[3])
@@ -138,7 +134,6 @@ class Family:
     def __new__(cls, prt, name):
         if name in cls._cache:
             return cls._cache[name]
-        from test_update_primitives import meshes_of
         self = super().__new__(cls)
         tp = Teapot(prt, seed=None, variant=name)
         self.prt, self.name, self.tp, self.cfg = prt, name, tp, tp.cfg
@@ -164,16 +159,14 @@ class Family:
         return self
 
     def rays(self):
-        """130 rays of test_cast_rays.random_rays through the uploaded scene's root box"""
+        """130 rays of cases.random_rays through the uploaded scene's root box"""
         if self._rays is None:
             import cast_api
-            from test_cast_rays import random_rays
             cast_api.lib()
             self._rays = random_rays(self.prt, cast_api, self.name, n=N_RAYS)
         return self._rays
 
     def groups(self, scene):
-        from test_smooth_normals import mirror_weld
         if not hasattr(scene, "_groups"):
             scene._groups = mirror_weld(scene.v0)
         return scene._groups
@@ -229,7 +222,6 @@ class Model:
             return given
         if self.smooth is None:
             return self.n
-        from test_smooth_normals import mirror_normals
         groups, _, weighting, crease = self.smooth
         n = mirror_normals(v, groups, 0 if weighting == "unit" else 1, crease)
         n.setflags(write=False)
@@ -552,7 +544,6 @@ class Model:
         return nodes, prims
 
     def oracle_render(self, oracle):
-        from test_update_primitives import desc_with
         sc, prt = self.scene, self.prt
         if sc.T:
             nodes, prims = self.oracle_tree()
@@ -840,7 +831,6 @@ def test_checkpoint_and_resume_across_a_change(prt, oracle):
     state, img = r.read_state(), r.read_framebuffer()
     r.close()
     _agree(("ok", (want_state, want_img)), ("ok", (state, img)), "resumed against uninterrupted")
-    from test_update_primitives import desc_with
     nodes, prims = model.oracle_tree()
     base = _with(prt, model.scene.desc, model.v, model.n, nodes, prims, T=model.scene.T)
     desc = desc_with(prt, base, np.ascontiguousarray(model.m))

@@ -18,39 +18,12 @@ run, and together with the 32-bit offsets it was slower than the offsets alone i
 profiles/r16_addressing_ab.txt).  This tree holds the parent's 34."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 from conftest import ROOT
-
-HIP = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd", "csrc", "hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-HEADLINE = "_ZN3prt13render_kernelILj3ELb0ELi6ELb0EEE"        # render_kernel<3, false, 6, false>
-
-
-def kernel_lines(text, symbol=HEADLINE):
-    lines = text.split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith(symbol) and ":" in l)
-    end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    return [l for l in lines[start:end] if not re.match(r"\s*(;|\.loc|\.file|\.cfi|\.Ltmp)", l)]
-
-
-def frame_loop(lines):
-    """the longest backward-branch span of the kernel"""
-    labels = {}
-    for i, l in enumerate(lines):
-        m = re.match(r"^(\.LBB\d+_\d+):", l)
-        if m:
-            labels[m.group(1)] = i
-    best = (0, 0)
-    for i, l in enumerate(lines):
-        m = re.search(r"\ss_c?branch\S*\s+(\.LBB\d+_\d+)", l)
-        if m and labels.get(m.group(1), i) < i and i - labels[m.group(1)] > best[1] - best[0]:
-            best = (labels[m.group(1)], i)
-    assert best[1] > best[0], "no loop in the kernel"
-    return lines[best[0]:best[1] + 1]
+from cases import frame_loop, HIP, HIPCC, kernel_lines
 
 
 def addressing_counts(text):

@@ -14,8 +14,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_denoise import _setup, denoise_ref, spatial_variance, stats_variance
-from support import bits as _bits, to_device as _to_device
+from cases import denoise_setup as _setup, _export, _synthetic, _torch
+from mirrors import denoise_ref, spatial_variance, stats_variance
+from support import assert_api, bits as _bits, pkg as _pkg, to_device as _to_device
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 HIP = os.path.join(PKG, "csrc", "hip")
@@ -26,26 +27,11 @@ NEW_API = ("prt_export_denoise_inputs", "prt_denoise_records", "prt_denoise_reco
 # ---- no GPU --------------------------------------------------------------------------------------------------------------------------------
 
 def test_api_is_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "prt.h")) as f:
-        header = f.read()
-    for name in NEW_API:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+    header = assert_api(NEW_API)
     assert re.search(r"#define\s+PRT_DENOISE_RECORD_FLOATS\s+16\b", header)
-    import importlib
-    capi = importlib.import_module("photorealistic-rendering-using-opencl_amd._capi")
-    bound = {n for n, _, _ in capi.PRT_API}
-    assert set(NEW_API) <= bound
-    assert capi.DENOISE_RECORD_FLOATS == 16
-    lib = os.path.join(PKG, "libprt.so")
-    if not os.path.exists(lib):
-        import __graft_entry__ as ge
-        ge.build()
-    dll = C.CDLL(lib)
-    for name in NEW_API:
-        assert hasattr(dll, name), name
-    pkg = importlib.import_module("photorealistic-rendering-using-opencl_amd")
+    assert _pkg()._capi.DENOISE_RECORD_FLOATS == 16
     for name in ("export_denoise_inputs", "denoise_records", "denoise_records_temporal", "reset_records_history"):
-        assert callable(getattr(pkg.Renderer, name)), name
+        assert callable(getattr(_pkg().Renderer, name)), name
 
 
 def test_records_kernels_have_no_scratch():
@@ -79,20 +65,6 @@ W1, H1 = 100, 70                        # no multiple of 8 or 16; the 62 rows an
 SOURCES, PASSES = ("stats", "spatial"), (1, 5)
 # ("blocks", block_rows, n_parts) | ("tiles", cuts)
 SPLITS = [("blocks", 8, 2), ("blocks", 8, 3), ("tiles", (0, 40, 70)), ("tiles", (0, 24, 50, 70)), ("tiles", (0, 1, 70))]
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _export(r):
-    """the records of r's frame part: a [rows, width, 16] tensor on cuda:0"""
-    torch = _torch()
-    t = torch.full((r.rows, r.width, 16), 7.0, dtype=torch.float32, device="cuda:0")
-    torch.cuda.synchronize()
-    r.export_denoise_inputs(t)
-    return t
 
 
 def _split_parts(split, H):
@@ -284,30 +256,6 @@ def test_temporal_split_equals_whole(prt, feedback, adaptive):
     assert (_bits(dev.cpu().numpy()) == _bits(first)).all()
     for r in (rw, rp, rc, fresh):
         r.close()
-
-
-def _synthetic(W, H, seed=5):
-    """records [H, W, 16] no render reliably produces: O(1) colours, two planes of depth meeting at a vertical edge, unit normals, an uncovered
-    band, one covered pixel with a zero normal, one pixel with a NaN colour.  Returns (records, (y, x) of the NaN pixel)"""
-    rng = np.random.default_rng(seed)
-    rec = np.zeros((H, W, 16), dtype=np.float32)
-    ys, xs = np.mgrid[0:H, 0:W]
-    left = xs < W // 2
-    rec[..., 0:3] = rng.uniform(0.2, 1.5, (H, W, 3))
-    rec[..., 3] = rng.uniform(0.0, 1.0, (H, W))
-    rec[..., 4:7] = np.where(left[..., None], [0.7, 0.6, 0.5], [0.2, 0.5, 0.8]) + rng.uniform(-0.02, 0.02, (H, W, 3))
-    rec[..., 7] = 1.0
-    nl, nr = np.array([0.1, 0.2, 1.0]), np.array([-0.6, 0.1, 0.8])
-    rec[..., 8:11] = np.where(left[..., None], nl / np.linalg.norm(nl), nr / np.linalg.norm(nr))
-    rec[..., 11] = np.where(left, 3.0 + 0.02 * xs + 0.01 * ys, 5.0 - 0.03 * xs + 0.015 * ys)
-    rec[10:13, :, 4:7] = [0.3, 0.4, 0.6]                 # the band: no hit -- the environment's albedo, no normal, no depth
-    rec[10:13, :, 7:12] = 0.0
-    rec[20, 7, 8:11] = 0.0                               # covered, but the normals summed to zero
-    nan_at = (25, 30)
-    rec[25, 30, 0] = np.nan
-    rec[..., 12] = rng.uniform(0.005, 0.1, (H, W))
-    rec[..., 13] = 1.0
-    return rec, nan_at
 
 
 @pytest.mark.gpu

@@ -5,15 +5,13 @@ compiled for the host and run by the wave emulator of tests/emu/pt_emu.cpp, agai
 bit for bit, under the kernel's default schedule and under RANDOM walk-phase lengths (lanes drift in frame number:
 which lanes walk together must not change a bit).  No GPU involved: code generation for gfx950 is what -m gpu checks."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ALPHA_VARIANTS, variant_config, GOLDEN, ROOT, VARIANTS, VIEW_VARIANTS, variant_camera
-from support import assert_same_render as _same
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+from conftest import ALPHA_VARIANTS, GOLDEN, VARIANTS, VIEW_VARIANTS
+from cases import callers_tree
+from support import assert_same_render as _same, variant_case as _scene
 
 
 @pytest.fixture(scope="module")
@@ -21,14 +19,6 @@ def emu():
     import emu_api
     emu_api.lib()
     return emu_api
-
-
-def _scene(prt, variant, W, H):
-    scene_json, phase, use_env = VARIANTS[variant]
-    scene = prt.HostScene(scene_json)
-    cfg = variant_config(scene, variant)
-    cfg.phase_function = phase
-    return scene, cfg, variant_camera(prt, variant, W, H), (prt.make_sky(64, 32) if use_env else None)
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
@@ -165,25 +155,6 @@ def test_environment_importance_sampling_has_the_same_expectation_on_host(prt, o
     (m0, e0), (m1, e1) = out[0], out[1]
     z = (m1 - m0) / np.sqrt(e0 ** 2 + e1 ** 2)
     assert (np.abs(z) < 4.5).all() and (np.abs(m1 / m0 - 1.0) < 0.05).all(), "means %s vs %s (z = %s)" % (m0, m1, z)
-
-
-def callers_tree(prt, oracle):
-    """a CALLER'S tree, legal for the reference kernel but unlike anything the builder makes: loose boxes (the whole scene), a leaf of 40
-    triangles, two sibling leaves that SHARE triangles (ranges 20..59 and 30..99), 100 of the mesh's triangles referenced in all"""
-    import ctypes as C
-    scene = prt.HostScene("cornell_coat.json")
-    node_t = np.dtype([("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)])
-    nodes = np.zeros(5, dtype=node_t)
-    nodes["bounds"] = np.array([-3, 3, -1, 5, -3, 3], dtype=np.float32)
-    nodes[0]["first"], nodes[0]["leaf"] = 1, 0                                   # root: children 1, 2
-    nodes[1]["first"], nodes[1]["count"], nodes[1]["leaf"] = 0, 40, 1            # a fat leaf
-    nodes[2]["first"], nodes[2]["leaf"] = 3, 0                                   # inner: children 3, 4
-    nodes[3]["first"], nodes[3]["count"], nodes[3]["leaf"] = 20, 40, 1
-    nodes[4]["first"], nodes[4]["count"], nodes[4]["leaf"] = 30, 70, 1
-    desc = prt.SceneDesc.from_buffer_copy(bytes(scene.desc))
-    desc.bvh_nodes = nodes.ctypes.data_as(C.c_void_p)
-    desc.bvh_node_count = len(nodes)
-    return scene, desc, nodes
 
 
 def test_callers_tree_with_shared_and_fat_leaves_on_host(prt, oracle, emu):

@@ -7,9 +7,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-import _emu  # noqa: E402
+import support                          # noqa: F401  (its import puts tests/emu, where _emu lives, on the path)
+import _emu
 
 SOURCE = '#include "answer.h"\n#include "other.h"\nextern "C" int answer() { return ANSWER + SHIFT + OTHER; }\n'
 

@@ -7,15 +7,13 @@ function by function").  Every function-level test runs on the host compilation 
 that asserts device output == host output bit for bit and then runs the same checks on the device output."""
 import functools
 import json
-import os
-import sys
 import time
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
-import emu_api  # noqa: E402
+import support                          # (its import puts tests/emu, where emu_api lives, on the path)
+import emu_api
 
 F32 = np.float32
 PI = np.pi
@@ -83,9 +81,7 @@ def _ulps(a, b):
 
 @functools.lru_cache(maxsize=None)
 def _tables(name):
-    import importlib
-    from conftest import PKG_NAME
-    return importlib.import_module(PKG_NAME).env_cdf(_maps()[name])
+    return support.pkg().env_cdf(_maps()[name])
 
 
 # ---- tables -----------------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 The filter path draws nothing from the RNG: a filtered render is the reference's algorithm with another image-plane point per path.  The oracle
 (oracle/pt_oracle.c) takes those points as a table of per-path offsets {dx, dy} from OUTSIDE -- it knows neither the warps nor the hash -- and
 applies the "Camera ray" sentence of include/prt.h.  The tables fed to it here:
-  * box and tent: the numpy mirror of tests/test_pixel_filter.py (bit-exact with the host function for these kinds);
+  * box and tent: the numpy mirror of tests/mirrors.py (bit-exact with the host function for these kinds);
   * Gaussian and Blackman-Harris: on the host emulator the mirror's own table(kind, r), handed to both sides; on the GPU
     prt.pixel_filter_offsets (the product's table is internal; the host function is held to the mirror within 2 ulp and to the device bit for
     bit by test_pixel_filter.py).
@@ -11,23 +11,22 @@ No tolerance anywhere: equality of bits, path state (oracle.state_fields_equal) 
 
 Without a GPU: tests/emu (pt_device.h compiled for the host) against the oracle -- every filter set, kinds and radii, frames / "N spp" / resumed
 runs, ragged frames, row tiles and row blocks (global pixel coordinates), schedules.  With one (-m gpu): the same through the C ABI -- the seven
-rows of test_pixel_filter.SETS in frames, "N spp" and adaptive mode, the 5- and 6-wave builds under both pixel mappings, the ordered build, the
+rows of mirrors.SETS in frames, "N spp" and adaptive mode, the 5- and 6-wave builds under both pixel mappings, the ordered build, the
 live-pixel-list launches, compiled set == generic dispatch, splits, checkpoints, walk_min_lanes -- and the filtered guides' coverage at K = 16
 against a float64 caster.
 
 Left out, and why: nothing of the issue's list.  The ordered ("expensive first") build only runs through trees of more than 64 k node pairs, so
 its case renders a strip of the 871 k-triangle stand-in (as test_adaptive.py does for the big tree), not a Cornell box."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, VARIANTS, variant_camera, variant_config
-from test_pixel_filter import DEFAULT_R, KINDS, SETS, _quad_scene, sample_u, table, warp
-from support import assert_same_render as _same
+from conftest import GOLDEN
+from cases import filter_setup as _setup, _quad_scene
+from mirrors import camera_basis, DEFAULT_R, KINDS, offsets_ref, sample_u, SETS, table, warp
+from support import assert_same_render as _same, variant_case
 
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
 TABLE_KINDS = ("gaussian", "blackman-harris")
 
@@ -35,7 +34,7 @@ TABLE_KINDS = ("gaussian", "blackman-harris")
 # ---- the offsets handed to the oracle ------------------------------------------------------------------------------------------------------------
 
 def mirror_offsets(kind, r, W, H, K, T=None):
-    """float32 (H, W, K, 2): offsets_ref of test_pixel_filter.py for every pixel of a W x H frame, paths 0 .. K-1 (the same functions, whole
+    """float32 (H, W, K, 2): offsets_ref of tests/mirrors.py for every pixel of a W x H frame, paths 0 .. K-1 (the same functions, whole
     arrays at a time).  T: the 257-entry table of the table kinds (default: the mirror's own)"""
     gy = np.arange(H, dtype=np.uint32)[:, None, None]
     gx = np.arange(W, dtype=np.uint32)[None, :, None]
@@ -63,7 +62,6 @@ def gpu_offsets(prt, kind, r, W, H, K, rows=None):
 
 def test_the_whole_frame_mirror_is_offsets_ref():
     """mirror_offsets is offsets_ref pixel by pixel (bits), so what holds for one holds for the other"""
-    from test_pixel_filter import offsets_ref
     for kind in KINDS:
         tab = mirror_offsets(kind, DEFAULT_R[kind], 7, 5, 9)
         for gx, gy in ((0, 0), (6, 4), (3, 2)):
@@ -88,14 +86,10 @@ FILTERS = [("box", 0.5), ("tent", 1.0), ("gaussian", 1.5), ("blackman-harris", 2
 
 
 def _scene(prt, variant, W, H, pinhole=False):
-    scene_json, phase, use_env = VARIANTS[variant]
-    scene = prt.HostScene(scene_json)
-    cfg = variant_config(scene, variant)
-    cfg.phase_function = phase
-    cam = variant_camera(prt, variant, W, H)
+    scene, cfg, cam, env = variant_case(prt, variant, W, H)
     if pinhole:
         cam.apertureRadius = 0.0
-    return scene, cfg, cam, (prt.make_sky(64, 32) if use_env else None)
+    return scene, cfg, cam, env
 
 
 def _emu_filter(kind, r):
@@ -275,7 +269,6 @@ GPU_ROWS = [row + kr for row, kr in zip(SETS, SET_KINDS)]
 
 
 def _gpu_setup(prt, scene_json, W, H, env, generic=False, pinhole=False):
-    from test_pixel_filter import _setup
     scene, cfg, cam, r = _setup(prt, scene_json, W, H, env=env, pinhole=pinhole)
     if generic:
         r.set_option("generic", 1)
@@ -524,7 +517,6 @@ def guide_points(kind, r, K):
 def cast_quad(cam, W, H, c, e0, e1, dx, dy, dtype):
     """the K sample rays of every pixel through the pinhole camera model of test_pixel_filter._coverage against the quad (hit_quad's region), all
     arithmetic in `dtype`.  Returns hits (H, W, K) and the hit distance along the normalised ray"""
-    from test_temporal import camera_basis
     t_ = lambda a: np.asarray(a, dtype=dtype)
     Pc, M, Hz, Vt = (t_(a) for a in camera_basis(cam))
     c, e0, e1 = t_(c), t_(e0), t_(e1)

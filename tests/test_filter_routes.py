@@ -5,8 +5,7 @@ comes from the stats plane and from the 5x5 moments; the temporal calls run twic
 feedback "atrous" and once with the temporal response on.  The histories and the response planes of both routes are compared as well."""
 import pytest
 
-from test_denoise import _setup
-from test_denoise_records import _export
+from cases import denoise_setup as _setup, _export
 from support import bits as _bits
 
 W, H = 24, 17                           # 2 x 2 workgroups of 16 x 16: the last column of them has 8 live columns, the last row 1 live row

@@ -7,19 +7,16 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ALPHA_VARIANTS, variant_config, GOLDEN, PKG_NAME, ROOT, VARIANTS, VIEW_VARIANTS, variant_camera
-from support import assert_same_render as _assert_same
+from conftest import ALPHA_VARIANTS, GOLDEN, PKG_NAME, ROOT, VARIANTS, VIEW_VARIANTS, variant_camera
+from cases import callers_tree
+from mirrors import assert_kat_equal, check_env_lookup, kat_tables
+from support import assert_same_render as _assert_same, variant_case
 
 pytestmark = pytest.mark.gpu
 
 
 def _setup(prt, variant, W, H, rows=None, row0=0):
-    scene_json, phase, use_env = VARIANTS[variant]
-    scene = prt.HostScene(scene_json)
-    cfg = variant_config(scene, variant)
-    cfg.phase_function = phase
-    cam = variant_camera(prt, variant, W, H)
-    env = prt.make_sky(64, 32) if use_env else None
+    scene, cfg, cam, env = variant_case(prt, variant, W, H)
     r = prt.Renderer(cfg, device=0)
     r.upload_scene(scene)
     if env is not None:
@@ -368,17 +365,13 @@ def test_debug_views_match_reference_golden(prt, oracle, fixture):
     base, view = VIEW_VARIANTS[fixture]
     g = np.load(os.path.join(GOLDEN, fixture + ".npz"))
     W, H, frames = int(g["width"]), int(g["height"]), int(g["frames"])
-    scene_json, phase, use_env = VARIANTS[base]
-    scene = prt.HostScene(scene_json)
-    cfg = scene.config()
-    cfg.phase_function = phase
+    scene, cfg, cam, env = variant_case(prt, base, W, H)        # (neither base is an alpha or a pick-light variant: scene.config() as it was)
     cfg.view_option = view
-    env = prt.make_sky(64, 32) if use_env else None
     r = prt.Renderer(cfg, device=0)
     r.upload_scene(scene)
     if env is not None:
         r.upload_envmap(env)
-    r.set_camera(variant_camera(prt, base, W, H))
+    r.set_camera(cam)
     r.resize(W, H)
     seeds = prt.seed_pairs(frames)
     r.render_frames(seeds[:2 * 40])
@@ -617,8 +610,6 @@ def test_environment_importance_sampling_converges_to_the_lookup_render(prt, ora
     assert (np.abs(z) < 4.5).all() and (np.abs(m1 / m0 - 1.0) < 0.01).all(), "means %s vs %s (z = %s)" % (m0, m1, z)
     assert n1 < 0.9 * n0, "noise with importance sampling %.4f, without %.4f" % (n1, n0)
     # device == host compilation of the same code, bit for bit
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
     import emu_api
     W2, H2, f2 = 29, 19, 96
     cfg = scene.config()
@@ -894,7 +885,6 @@ def _chain_bvh(levels):
 def test_callers_tree_with_shared_and_fat_leaves(prt, oracle):
     """a tree the builder would never make but the reference kernel accepts: loose boxes, a 40-triangle leaf, sibling leaves that share
     triangles (one slot per reference after packing; pending runs of 110 triangles)"""
-    from test_emu import callers_tree
     scene, desc, keep = callers_tree(prt, oracle)
     W, H, frames = 40, 24, 16
     cfg = scene.config()
@@ -1207,7 +1197,6 @@ def test_tonemap_matches_the_reference_shader_and_cli_writes_png(prt, oracle, tm
 
 def test_device_functions_match_reference_kat(prt):
     """prt_selftest_fn on the GPU against the per-function known-answer vectors of the reference build (tests/test_kat.py)"""
-    from test_kat import assert_kat_equal, kat_tables
     scene = prt.HostScene("cornell_diffuse.json")
     r = prt.Renderer(scene.config(), device=0)
     n = 0
@@ -1215,7 +1204,6 @@ def test_device_functions_match_reference_kat(prt):
         assert_kat_equal(name, r.selftest_fn(fn, params, cases), expect, cols)
         n += 1
     assert n >= 40
-    from test_kat import check_env_lookup
     check_env_lookup(r.selftest_fn)             # read_imagef semantics worked out from the OpenCL 1.2 specification
     r.close()
 

@@ -1,9 +1,9 @@
 """prt_set_morph_targets / prt_morph / prt_pose_morphed: the mesh morphed on the device from per-frame target weights, alone or in front of
 the skin (include/prt.h; csrc/hip/pt_morph.h / .hip).
 
-`mirror_morph_raw` below restates prt.h's formulas in float32 numpy -- a loop over the targets in ascending t, a target whose weight is zero
+`mirror_morph_raw` (tests/mirrors.py) restates prt.h's formulas in float32 numpy -- a loop over the targets in ascending t, a target whose weight is zero
 skipped, otherwise p[corner_t] = p[corner_t] + w * dp_t as one fancy-indexed statement (a target's corners are distinct) -- and shares no
-code with the body.  `mirror_morph` adds prt_morph's output rule; the fused case feeds the raw output to test_pose.mirror_pose.  The body
+code with the body.  `mirror_morph` adds prt_morph's output rule; the fused case feeds the raw output to mirror_pose.  The body
 (run on the host by tests/emu/morph_emu.cpp, over the table the library's own builder makes) and the device (through the C ABI) must give
 its bytes.
 
@@ -12,23 +12,17 @@ numpy stable sort.  GPU tests: prt_read_morphed / prt_read_posed against the mir
 wrong (3, 66, 258 and 18 960 corners; 1, 3, 257 and 65 536 targets), and the scene after a morph against a second context that was given the
 mirror's arrays through prt_update_vertices / prt_rebuild_bvh."""
 import ctypes as C
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_refit import _bytes                                                           # noqa: E402
-from test_pose import (FRAMES, H, REBUILD, REFIT, T_TEAPOT, W, _assert_equal, _context, _everything, _refused, _scene, _skin,      # noqa: E402
-                       identity, mirror_pose, skin_case, teapot)
+from cases import (_assert_equal, _everything, fused_case, identity, morph_cache as _cache, morph_case, planted, pose_context as _context,
+                   POSE_FRAME, pose_scene as _scene, REBUILD, REFIT, _refused, _skin, T_TEAPOT, teapot)
+from mirrors import mirror_morph, mirror_morph_raw, mirror_pose
+from support import assert_api, bytes_flat as _bytes
 
 f32 = np.float32
+W, H, FRAMES = POSE_FRAME
 NAMES = ("prt_set_morph_targets", "prt_morph", "prt_morph_device", "prt_pose_morphed", "prt_pose_morphed_device", "prt_read_morphed")
 
 
@@ -37,112 +31,6 @@ def emu():
     import morph_api
     morph_api.lib()
     return morph_api
-
-
-# ---- the mirror ------------------------------------------------------------------------------------------------------------------------------
-
-def mirror_morph_raw(base_v, base_n, targets, weights):
-    """(p, n) float32 [corners, 4], un-normalised, lane 3 the base's; n None without base normals"""
-    p = np.array(base_v, dtype=f32).reshape(-1, 4)
-    n = None if base_n is None else np.array(base_n, dtype=f32).reshape(-1, 4)
-    w = np.asarray(weights, dtype=f32).reshape(-1)
-    assert len(w) == len(targets)
-    with np.errstate(all="ignore"):
-        for t, (corner, dp, dn) in enumerate(targets):
-            if w[t] == 0 or len(corner) == 0:
-                continue
-            corner = np.asarray(corner, dtype=np.int64)
-            p[corner, :3] = p[corner, :3] + w[t] * np.asarray(dp, dtype=f32).reshape(-1, 4)[:, :3]
-            if n is not None:
-                delta = np.zeros((len(corner), 3), dtype=f32) if dn is None else np.asarray(dn, dtype=f32).reshape(-1, 4)[:, :3]
-                n[corner, :3] = n[corner, :3] + w[t] * delta
-    assert p.dtype == f32 and (n is None or n.dtype == f32)
-    return p, n
-
-
-def mirror_morph(base_v, base_n, targets, weights):
-    """(vertices, normals) float32 [corners, 4] of prt_morph by the formulas of prt.h; normals None without base normals"""
-    p, n = mirror_morph_raw(base_v, base_n, targets, weights)
-    out_v = np.zeros_like(p)
-    out_v[:, :3] = p[:, :3]
-    if n is None:
-        return out_v, None
-    with np.errstate(all="ignore"):
-        x, y, z = n[:, 0], n[:, 1], n[:, 2]
-        L = np.sqrt((x * x + y * y) + z * z)
-        out_n = np.zeros_like(n)
-        out_n[:, :3] = np.where((L > 0)[:, None], n[:, :3] / L[:, None], n[:, :3])
-        assert L.dtype == f32
-    return out_v, out_n
-
-
-# ---- target sets -----------------------------------------------------------------------------------------------------------------------------
-
-def _target(rng, corner, normal_deltas=True):
-    corner = np.sort(np.asarray(corner, dtype=np.uint32))
-    dp = np.zeros((len(corner), 4), dtype=f32)
-    dp[:, :3] = rng.uniform(-0.03, 0.03, (len(corner), 3))
-    dp[:, 3] = 5.0                                          # (lane 3 is never looked at)
-    dn = None
-    if normal_deltas:
-        dn = np.zeros((len(corner), 4), dtype=f32)
-        dn[:, :3] = rng.uniform(-0.3, 0.3, (len(corner), 3))
-    return corner, dp, dn
-
-
-def target_set(corners, n_targets, seed, fraction=0.05):
-    """1 target: a dense one.  3 (and 4: the CPU case): random subsets of `fraction` of the corners, one of them without normal deltas, and a
-    dense one last.  257: a handful of entries each, corner 0 listed by all of them, the last corner by the last one.  65 536: only the last has
-    an entry, on the last corner.  Weights in [-0.5, 1] without zeros, but for 257 targets, where every seventh is a zero of alternating sign"""
-    rng = np.random.default_rng(seed)
-    if n_targets == 65536:
-        targets = [(np.zeros(0, dtype=np.uint32), np.zeros((0, 4), dtype=f32), None)] * 65535 + [_target(rng, [corners - 1])]
-    elif n_targets == 257:
-        targets = []
-        for t in range(257):
-            corner = {0, corners - 1} if t == 256 else {0}
-            corner |= set(rng.choice(np.arange(1, corners), size=min(4, corners - 1), replace=False).tolist())
-            targets.append(_target(rng, sorted(corner), normal_deltas=(t % 5 != 3)))
-    else:
-        k = max(1, int(round(fraction * corners)))
-        targets = [_target(rng, rng.choice(corners, size=k, replace=False), normal_deltas=(t != 1)) for t in range(n_targets - 1)]
-        targets.append(_target(rng, np.arange(corners)))
-    weights = rng.uniform(0.1, 1.0, n_targets).astype(f32) * np.where(rng.uniform(size=n_targets) < 0.3, f32(-0.5), f32(1))
-    if n_targets == 257:
-        weights[0::14], weights[7::14] = 0.0, -0.0
-    return targets, np.ascontiguousarray(weights, dtype=f32)
-
-
-_cache = {}
-
-
-def morph_case(prt, T, n_targets, seed=11):
-    """the first T triangles of the teapot as the base, a target set and the frame's weights; the mirror's morph (computed once, shared,
-    read-only)"""
-    key = (T, n_targets, seed)
-    if key not in _cache:
-        case = teapot(prt)
-        v0, n0 = case.v0[:3 * T].copy(), case.n0[:3 * T].copy()
-        targets, weights = target_set(3 * T, n_targets, seed)
-        raw_p, raw_n = mirror_morph_raw(v0, n0, targets, weights)
-        want_v, want_n = mirror_morph(v0, n0, targets, weights)
-        for a in (v0, n0, weights, raw_p, raw_n, want_v, want_n) + tuple(x for t in targets for x in t if x is not None):
-            a.setflags(write=False)
-        assert np.isfinite(want_v).all() and not np.array_equal(want_v[:, :3], v0[:, :3])
-        _cache[key] = dict(T=T, n_targets=n_targets, v0=v0, n0=n0, targets=targets, weights=weights, raw_p=raw_p, raw_n=raw_n, v=want_v, n=want_n)
-    return _cache[key]
-
-
-def fused_case(prt, T, rigid):
-    """skin_case(T, 4 bones) posed over morph_case(T, 3 targets): the mirror's arrays"""
-    key = ("fused", T, rigid)
-    if key not in _cache:
-        s, m = skin_case(prt, T, 4, rigid), morph_case(prt, T, 3)
-        v, n = mirror_pose(m["raw_p"], m["raw_n"], s["index"], s["weight"], s["M"])
-        v.setflags(write=False), n.setflags(write=False)
-        assert np.isfinite(v).all() and not np.array_equal(v, s["v"])
-        _cache[key] = dict(s=s, m=m, v=v, n=n)
-    return _cache[key]
 
 
 # ---- CPU: the bodies on the host -------------------------------------------------------------------------------------------------------------
@@ -183,29 +71,6 @@ def test_fused_body_equals_the_pose_of_the_raw_morph(prt, emu, rigid):
     # all weights zero: the pose of the base
     got_v, got_n = emu.pose_morphed(m["v0"], m["n0"], m["targets"], m["weights"] * 0, s["index"], s["weight"], s["M"])
     assert np.array_equal(_bytes(got_v), _bytes(s["v"])) and np.array_equal(_bytes(got_n), _bytes(s["n"]))
-
-
-def planted():
-    """two triangles, five targets.  Corner 0: no target lists it (-0 coordinates).  Corner 1: every target lists it.  Target 1 has no entries.
-    Corner 5, the last one: only the last target lists it.  Target 2 holds NaN deltas and is only ever given a zero weight.  Corner 2: deltas
-    that cancel the normal to length 0.  Corner 3: denormal deltas.  Corner 4: a delta that overflows under a large weight"""
-    nan = np.nan
-    v = np.zeros((6, 4), dtype=f32)
-    n = np.zeros((6, 4), dtype=f32)
-    v[:, :3] = [[-0.0, 2, -0.0], [0.5, -0.25, 4], [1, 1, 1], [0, -0.0, 1e-45], [3, -2, 1], [0.1, 0.2, 0.3]]
-    v[:, 3] = 3.0
-    n[:, :3] = [[0, 3, 4], [0, 0, 1], [0.5, 0, 0], [1e-30, 0, 0], [1, 0, 0], [0, 0.6, 0.8]]
-
-    def q(rows):
-        a = np.zeros((len(rows), 4), dtype=f32)
-        a[:, :3] = rows
-        return a
-    targets = [(np.array([1, 2, 3], dtype=np.uint32), q([[0.25, 0, 0], [0.125, 0, -1], [1e-42, -2e-44, 1e-45]]), q([[0, 1, 0], [-1, 0, 0], [0, 0, 0]])),
-               (np.zeros(0, dtype=np.uint32), np.zeros((0, 4), dtype=f32), None),
-               (np.array([1, 3, 4], dtype=np.uint32), q([[nan] * 3] * 3), q([[nan] * 3] * 3)),
-               (np.array([1, 4], dtype=np.uint32), q([[0, -0.5, 0], [1e38, 0, 0]]), None),
-               (np.array([1, 5], dtype=np.uint32), q([[0, 0, 0.75], [1, 1, 1]]), q([[0.5, 0.5, 0], [0, -0.6, -0.8]]))]
-    return v, n, targets
 
 
 def test_planted_cases(emu):
@@ -297,12 +162,7 @@ def test_table_builder_against_a_stable_sort(prt, emu, n_targets):
 
 
 def test_api_is_declared_exported_and_bound(prt):
-    header = open(os.path.join(ROOT, "include", "prt.h")).read()
-    declared = set(re.findall(r"\b(prt_[a-z_0-9]+)\s*\(", header))
-    lib = C.CDLL(os.path.join(ROOT, prt.__name__, "libprt.so"))
-    bound = {name for name, _, _ in prt._capi.PRT_API}
-    for name in NAMES:
-        assert name in declared and hasattr(lib, name) and name in bound, name
+    assert_api(NAMES, prt)
     assert C.sizeof(prt._capi.MorphTarget) == 32 and C.sizeof(prt._capi.MorphSet) == 32
     for method in ("set_morph_targets", "morph", "pose_morphed", "read_morphed"):
         assert callable(getattr(prt.Renderer, method))

@@ -1,33 +1,27 @@
 """prt_set_morph_targets_layout / prt_get_morph_report: the morph targets as planes of 64 corners per target (include/prt.h
 PRT_MORPH_LAYOUT_PLANES; csrc/hip/pt_morph.h / .hip), a second table layout for the same sets with the same bits out.
 
-The yardstick is test_morph.py's float32 numpy mirror, which shares no code with either body, and the per-corner layout itself: the plane
+The yardstick is the float32 numpy mirror of tests/mirrors.py (mirror_morph), which shares no code with either body, and the per-corner layout itself: the plane
 body (run on the host by tests/emu/morph_planes_emu.cpp in the kernel's launch shape, over the table the library's own builder makes) and
 the device (through the C ABI) must give the mirror's bytes and those of the same set under PRT_MORPH_LAYOUT_CORNERS.
 
 CPU tests: the builder against a numpy restatement written here from the targets' corner lists, the bodies against the mirror on the
-teapot and on planted cases -- test_morph.py's, and those a plane can get wrong: the two sides of a block boundary, the two halves of the
+teapot and on planted cases -- cases.planted(), and those a plane can get wrong: the two sides of a block boundary, the two halves of the
 mask, its first and last bit, a -0 on an unlisted lane, a NaN weight on a plane with one listed lane, 257 planes in one block -- and the
 report's arithmetic.  GPU tests: the read-backs through every door at 3, 66, 192, 258 and 18 960 corners (a ragged block; a block and two
 lanes; exactly three blocks; a workgroup and a tail; many), the scene after a morph, replacement, lifetime, refusals and row blocks."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_refit import _bytes                                                           # noqa: E402
-from test_pose import (FRAMES, H, REBUILD, REFIT, T_TEAPOT, W, _assert_equal, _context, _everything, _refused, _scene, _skin,      # noqa: E402
-                       identity, mirror_pose, teapot)
-from test_morph import fused_case, mirror_morph, mirror_morph_raw, morph_case, planted, target_set      # noqa: E402,F401
+from cases import (_assert_equal, _everything, fused_case, identity, morph_case, planted, pose_context as _context, POSE_FRAME, pose_scene as _scene,
+                   REBUILD, REFIT, _refused, _skin, T_TEAPOT, teapot)
+from mirrors import mirror_morph, mirror_morph_raw, mirror_pose
+from support import assert_api, bytes_flat as _bytes
 
 f32 = np.float32
+W, H, FRAMES = POSE_FRAME
 NAMES = ("prt_set_morph_targets_layout", "prt_get_morph_report")
 CORNERS, PLANES = 0, 1
 
@@ -171,7 +165,7 @@ def test_fused_body_equals_the_pose_of_the_raw_morph(prt, emu, rigid):
 
 
 def test_planted_cases_of_the_per_corner_layout(emu, corners_emu):
-    """test_morph.planted() with its weight vectors: a -0 weight over NaN deltas, all zero, overflow, negative, a NaN weight"""
+    """cases.planted() with its weight vectors: a -0 weight over NaN deltas, all zero, overflow, negative, a NaN weight"""
     v, n, targets = planted()
     w = np.array([0.5, np.nan, -0.0, 1.0, 1.0], dtype=f32)
     got_v, got_n = _check(emu, v, n, targets, w, "planted", corners_emu)
@@ -265,12 +259,7 @@ def test_report_arithmetic(prt, emu, T, n_targets):
 
 def test_api_is_declared_exported_and_bound(prt):
     import re
-    header = open(os.path.join(ROOT, "include", "prt.h")).read()
-    declared = set(re.findall(r"\b(prt_[a-z_0-9]+)\s*\(", header))
-    lib = C.CDLL(os.path.join(ROOT, prt.__name__, "libprt.so"))
-    bound = {name for name, _, _ in prt._capi.PRT_API}
-    for name in NAMES:
-        assert name in declared and hasattr(lib, name) and name in bound, name
+    header = assert_api(NAMES, prt)
     assert re.search(r"#define\s+PRT_MORPH_LAYOUT_CORNERS\s+0u", header) and re.search(r"#define\s+PRT_MORPH_LAYOUT_PLANES\s+1u", header)
     assert C.sizeof(prt._capi.MorphReport) == 32
     assert callable(prt.Renderer.morph_report)

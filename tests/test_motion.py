@@ -1,6 +1,6 @@
 """Motion of deforming meshes in the temporal reprojection (prt_set_motion, prt_read_motion, prt_export_motion,
 prt_denoise_records_temporal_motion; include/prt.h).  What is checked: the bodies of csrc/hip/pt_motion.h, compiled for the host, against a
-float32 numpy mirror byte for byte; a float64 mirror of the temporal step with the motion plane (test_temporal's temporal_ref plus D), which
+float32 numpy mirror byte for byte; a float64 mirror of the temporal step with the motion plane (temporal_ref plus D: temporal_ref_motion of tests/mirrors.py), which
 without a plane and with a plane of zeros is temporal_ref; a synthetic world with a card that moves by pixels per frame, where the plane
 must cut the error of the integrated colour at least in half (on the mirror alone, and on the device); the motion plane of rendered scenes
 against a float64 caster; the snapshot rule; the plumbing (guides unchanged, splits of the frame, export, the records call, motion off,
@@ -8,22 +8,16 @@ refusals, the read-only property, parallel.denoise_on_rank0)."""
 import ctypes as C
 import importlib
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT
-from test_denoise import EPS, MAT_COND, MAT_DIEL, MAT_ROUGH_COND, MAT_ROUGH_DIEL, Caster, _grad, denoise_ref, lum
-from test_refit import deform
-from test_temporal import _close, camera_basis, centre_dirs, project, temporal_ref
-from test_temporal_records import H0, T_DEFAULTS, W0, World, _plain_records, _unit
-from support import bits as _bits, pkg as _pkg, rodrigues as _rodrigues
+from conftest import PKG_NAME
+from cases import _cmp, H0, _plain_records, Rendered, RH, RW, T_DEFAULTS, _unit, W0, World
+from mirrors import camera_basis, centre_dirs, _close, D_BOUND, denoise_ref, _mirror_history, project, temporal_ref, temporal_ref_motion
+from support import assert_api, bits as _bits, pkg as _pkg, rodrigues as _rodrigues, to_device as _to_device
 
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
-PKG = os.path.join(ROOT, PKG_NAME)
 NEW_API = ("prt_set_motion", "prt_read_motion", "prt_export_motion", "prt_denoise_records_temporal_motion")
 f32 = np.float32
 
@@ -31,20 +25,8 @@ f32 = np.float32
 # ---- no GPU: the API -----------------------------------------------------------------------------------------------------------------------------
 
 def test_api_is_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "prt.h")) as f:
-        header = f.read()
-    for name in NEW_API:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+    header = assert_api(NEW_API)
     assert "PRT_ABI_VERSION 3" in header and "GHOSTS" not in header
-    capi = importlib.import_module(PKG_NAME + "._capi")
-    assert set(NEW_API) <= {n for n, _, _ in capi.PRT_API}
-    lib = os.path.join(PKG, "libprt.so")
-    if not os.path.exists(lib):
-        import __graft_entry__ as ge
-        ge.build()
-    dll = C.CDLL(lib)
-    for name in NEW_API:
-        assert hasattr(dll, name), name
     R = _pkg().Renderer
     for name in ("set_motion", "read_motion", "export_motion"):
         assert callable(getattr(R, name)), name
@@ -151,88 +133,8 @@ def test_pixel_reduction_equals_the_mirror(emu, K):
 
 # ---- no GPU: prt.h prt_denoise_temporal with a motion plane, in float64 ------------------------------------------------------------------------------
 
-def temporal_ref_motion(fb, g, g_prev, hist_prev, cam, cam_prev, v_frame, motion=None, alpha_color=0.2, alpha_moments=0.2, tau_z=0.05,
-                        cos_n=0.9, history_cap=32):
-    """test_temporal.temporal_ref plus the motion plane: motion [H, W, 4] = {D, m} or None.  A covered pixel with m > 0 and D != 0 reprojects
-    X + D; nothing else differs"""
-    old = np.seterr(all="ignore")
-    H, W = fb.shape[:2]
-    c = fb[..., :3].astype(np.float64)
-    L = lum(c)
-    fin = np.isfinite(c).all(-1)
-    g, g_prev = g.astype(np.float64), g_prev.astype(np.float64)
-    cov, nrm, z = g[..., 3] > 0, g[..., 4:7], g[..., 7]
-    B, Bp = camera_basis(cam), camera_basis(cam_prev)
-    d = centre_dirs(B, W, H)
-    X = B[0] + d * z[..., None]
-    if motion is not None:
-        mo = np.asarray(motion, dtype=np.float64)
-        moved = cov & (mo[..., 3] > 0) & (mo[..., :3] != 0).any(-1)
-        X = np.where(moved[..., None], X + mo[..., :3], X)
-    e = np.where(cov[..., None], X - Bp[0], d)
-    dist = np.where(cov, np.linalg.norm(e, axis=-1), 0.0)
-    xp, yp, ef = project(Bp, e, W, H)
-    f = Bp[1] - Bp[0]
-    front = ef > 0
-    margin = np.abs(ef) > 1e-6 * np.linalg.norm(e, axis=-1) * np.linalg.norm(f)
-    inr = front & (xp > -1) & (xp < W) & (yp > -1) & (yp < H)
-    grad = _grad(z, g[..., 3])
-    x0, y0 = np.floor(np.where(inr, xp, 0)), np.floor(np.where(inr, yp, 0))
-    fx, fy = np.where(inr, xp, 0) - x0, np.where(inr, yp, 0) - y0
-    sw = np.zeros((H, W)); sc = np.zeros((H, W, 3)); sn = np.zeros((H, W)); s1 = np.zeros((H, W)); s2 = np.zeros((H, W))
-    cmax = np.abs(c).max(-1); m1max = np.abs(L); m2max = L * L
-    have = hist_prev is not None
-    hp = hist_prev.astype(np.float64) if have else np.zeros((H, W, 8))
-    for t in range(4):
-        tx, ty = x0.astype(np.int64) + (t & 1), y0.astype(np.int64) + (t >> 1)
-        w = (fx if t & 1 else 1 - fx) * (fy if t >> 1 else 1 - fy)
-        inside = inr & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-        txc, tyc = np.clip(tx, 0, W - 1), np.clip(ty, 0, H - 1)
-        h, gq = hp[tyc, txc], g_prev[tyc, txc]
-        ok = inside & np.isfinite(h[..., :3]).all(-1) & ((gq[..., 3] > 0) == cov)
-        dz = np.abs(gq[..., 7] - dist)
-        tol = tau_z * dist + grad
-        dn = (nrm * gq[..., 4:7]).sum(-1)
-        ok_geo = ~cov | ((dz <= tol) & (dn >= cos_n))
-        weighty = ok & (w > 1e-6) & cov
-        margin &= ~weighty | ((np.abs(dz - tol) > 1e-4 * np.maximum(tol, 1e-6)) & (np.abs(dn - cos_n) > 1e-4))
-        ok &= ok_geo
-        wv = np.where(ok, w, 0.0)
-        hv = np.where(ok[..., None], h, 0.0)
-        sw += wv; sc += wv[..., None] * hv[..., :3]; sn += wv * hv[..., 3]; s1 += wv * hv[..., 4]; s2 += wv * hv[..., 5]
-        big = ok & (w > 1e-6)
-        cmax = np.maximum(cmax, np.where(big, np.abs(hv[..., :3]).max(-1), 0))
-        m1max = np.maximum(m1max, np.where(big, np.abs(hv[..., 4]), 0))
-        m2max = np.maximum(m2max, np.where(big, np.abs(hv[..., 5]), 0))
-    hist = have & fin & inr & (sw >= 0.01)
-    margin &= np.abs(sw - 0.01) > 1e-4
-    inv = np.where(hist, 1.0 / np.where(sw > 0, sw, 1.0), 0.0)
-    ch, nh, m1h, m2h = sc * inv[..., None], sn * inv, s1 * inv, s2 * inv
-    n = np.where(hist, np.minimum(nh + 1, history_cap), 1.0)
-    ac, am = np.maximum(alpha_color, 1 / n), np.maximum(alpha_moments, 1 / n)
-    ci = np.where(hist[..., None], ch + ac[..., None] * (c - ch), c)
-    m1 = np.where(hist, m1h + am * (L - m1h), L)
-    m2 = np.where(hist, m2h + am * (L * L - m2h), L * L)
-    margin_other = margin.copy()
-    near4 = np.abs(n - 4) <= 1e-3
-    margin &= ~near4
-    v = np.where(n >= 4, np.maximum(m2 - m1 * m1, 0.0), v_frame)
-    np.seterr(**old)
-    return dict(ci=ci, n=n, m1=m1, m2=m2, v=v, hist=hist, margin=margin, cscale=cmax, m1scale=m1max, m2scale=m2max,
-                margin_other=margin_other, near4=near4, sw=sw)
-
-
-def _mirror_history(ref, fb):
-    H, W = fb.shape[:2]
-    fin = np.isfinite(fb[..., :3]).all(-1)
-    h = np.concatenate([ref["ci"], ref["n"][..., None], ref["m1"][..., None], ref["m2"][..., None], ref["v"][..., None], np.zeros((H, W, 1))],
-                       -1).astype(f32)
-    h[..., :3] = np.where(fin[..., None], h[..., :3], fb[..., :3])
-    return h
-
-
 def test_mirror_without_motion_is_temporal_ref():
-    """D = None and D = 0 return arrays equal to temporal_ref's, on the synthetic world of test_temporal_records.py with a moving camera"""
+    """D = None and D = 0 return arrays equal to temporal_ref's, on the synthetic world of tests/cases.py with a moving camera"""
     prt = _pkg()
     world = World(prt)
     cams = [prt.default_camera(W0, H0), prt.orbit_camera(W0, H0, d_yaw=0.04, d_pitch=0.012), prt.orbit_camera(W0, H0, d_yaw=0.10, d_pitch=0.03, d_radius=0.06)]
@@ -386,21 +288,10 @@ def _call(rc, rec_t, W, H, cam, motion, **kw):
     return out
 
 
-def _cmp(label, k, what, got, ref, scale, mask, worst):
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    if got.ndim == 3:
-        scale, mask = scale[..., None], np.broadcast_to(mask[..., None], got.shape)
-    if mask.any():
-        worst[what] = max(worst.get(what, 0.0), float((np.abs(got - ref) / (1e-4 * np.maximum(scale, 1e-6) * np.ones_like(got)))[mask].max()))
-    bad = mask & ~_close(got, ref, scale, rel=1e-4)
-    assert not bad.any(), (label, k, what, np.argwhere(bad)[:4].tolist())
-
-
 def run_card(world, mode, rc=None, label=""):
     """the moving-card sequence with the plane (mode "plane"), without (mode "none") or with a plane of zeros ("zeros") through the mirror
     (rc None: its own history, as float32, stands in for the device's) or through context rc, whose history and picture are compared with the
     mirror after every call.  Returns the per-frame list of (mirror dict, history, picture, sid, plane, clean, rec)"""
-    from test_denoise_records import _to_device
     W, H, cam = W0, H0, world.cam
     prev, out, worst = None, [], {}
     for k in range(CARD_FRAMES):
@@ -540,7 +431,6 @@ def _rec_ctx(prt):
 def test_moving_card_on_the_device(prt, card_mirror):
     """the sequence through prt_denoise_records_temporal_motion: every call equals the mirror (fed with the device's own history); a null plane
     and a plane of zeros equal prt_denoise_records_temporal bit for bit; the plane halves the error on the device's output too"""
-    from test_denoise_records import _to_device
     world = card_mirror[0]
     ctx = [_rec_ctx(prt) for _ in range(4)]
     with_plane = run_card(world, "plane", rc=ctx[0], label="card, plane")
@@ -570,7 +460,6 @@ def test_one_row_and_one_pixel_with_a_plane(prt, W, H):
     plane when there is no projection: records with O(1) colours and depths and a plane with m = 1 and displacements of 0.3 on every
     pixel must give the bits of the call without a plane -- no history, n = 1 -- and stay finite; the frame is narrower than the 16 x 16
     workgroup in one or both directions."""
-    from test_denoise_records import _to_device
     a, b = _rec_ctx(prt), _rec_ctx(prt)
     cam = prt.default_camera(W, H)
     for k in range(2):
@@ -587,128 +476,6 @@ def test_one_row_and_one_pixel_with_a_plane(prt, W, H):
 
 
 # ---- on the GPU: the motion plane of rendered scenes ---------------------------------------------------------------------------------------------------
-
-RW, RH = 64, 48
-# the largest |D - caster's D| over the matching pixels measured on an MI355X (cornell_coat, seed 11; DESIGN.md s4 "Motion"), and the bound: 4 x
-# that -- never looser than 1e-3 of the mesh's bounding-box diagonal, under which a wrong vertex or swapped (u, v) (an edge length off) cannot fit
-D_MEASURED = 1.1e-7
-D_BOUND = 4 * D_MEASURED
-
-
-class MotionCaster(Caster):
-    """test_denoise's Caster on given vertices; first_hits() also names the triangle and barycentrics of every primary ray that ends on the mesh"""
-
-    def __init__(self, scene, cfg, vertices):
-        super().__init__(scene, cfg)
-        v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3, 4)[..., :3]
-        self.vtx = v
-        self.p0, self.e1, self.e2 = v[:, 0], v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
-        self.lo, self.hi = v.min(1), v.max(1)
-
-    def first_hits(self, cam, W, H):
-        """per pixel of the pinhole centre rays: mesh (the first hit is a mesh triangle of a non-delta material), tri, u, v"""
-        B = camera_basis(cam)
-        d = centre_dirs(B, W, H).reshape(-1, 3)
-        o = np.broadcast_to(B[0], d.shape).copy()
-        t, n, mid = self.trace(o, d)
-        col, tb, eta = self.obj_mat
-        delta = bool(((tb & MAT_COND) and not (tb & MAT_ROUGH_COND)) or ((tb & MAT_DIEL) and not (tb & MAT_ROUGH_DIEL)))
-        R = d.shape[0]
-        mesh = np.isfinite(t) & (mid == -1) & (not delta)
-        tri, uu, vv = np.zeros(R, dtype=np.int64), np.zeros(R), np.zeros(R)
-        for r in np.nonzero(mesh)[0]:
-            pv = np.cross(d[r], self.e2)
-            det = (self.e1 * pv).sum(1)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                inv = 1.0 / det
-                tv = o[r] - self.p0
-                u = (tv * pv).sum(1) * inv
-                qv = np.cross(tv, self.e1)
-                v = (d[r] * qv).sum(1) * inv
-                tt = (self.e2 * qv).sum(1) * inv
-            ok = (u >= 0) & (v >= 0) & (u + v <= 1) & (tt > EPS)
-            k = np.nonzero(ok)[0][np.argmin(tt[ok])]
-            assert abs(tt[k] - t[r]) <= 1e-9 * max(t[r], 1.0)
-            tri[r], uu[r], vv[r] = k, u[k], v[k]
-        # pixels whose first hit is a smooth conductor (a mirror) and whose reflected ray ends on the mesh: the mesh behind a delta chain
-        mirror = np.zeros(R, dtype=bool)
-        for r in np.nonzero(np.isfinite(t) & (mid >= 0))[0]:
-            tb_r = self.mat(mid[r])[1]
-            mirror[r] = bool((tb_r & MAT_COND) and not (tb_r & MAT_ROUGH_COND))
-        behind = np.zeros(R, dtype=bool)
-        rows = np.nonzero(mirror)[0]
-        if rows.size:
-            o2 = o[rows] + d[rows] * t[rows, None]
-            d2 = d[rows] - 2 * (d[rows] * n[rows]).sum(-1, keepdims=True) * n[rows]
-            d2 = d2 / np.linalg.norm(d2, axis=-1, keepdims=True)
-            t2, _, mid2 = self.trace(o2, d2)
-            behind[rows] = np.isfinite(t2) & (mid2 == -1)
-        shp = (H, W)
-        return (mesh.reshape(shp), tri.reshape(shp), uu.reshape(shp), vv.reshape(shp), mid.reshape(shp), np.isfinite(t).reshape(shp),
-                np.where(np.isfinite(t), t, 0.0).reshape(shp), behind.reshape(shp))
-
-
-def _point(vtx, tri, u, v):
-    a = vtx[tri]
-    return a[..., 0, :] * (1 - u - v)[..., None] + a[..., 1, :] * u[..., None] + a[..., 2, :] * v[..., None]
-
-
-class Rendered:
-    """a scene, its vertices, two deformations A (seed 21) and B (seed 11) and the caster's motion plane from the uploaded geometry to B at
-    RW x RH: computed once per scene, shared, never written to"""
-    _cache = {}
-
-    def __new__(cls, prt, scene_json, **orbit):
-        key = (scene_json, tuple(sorted(orbit.items())))
-        if key not in cls._cache:
-            self = super().__new__(cls)
-            self.scene = prt.HostScene(scene_json)
-            self.cfg = self.scene.config()
-            self.cam = prt.orbit_camera(RW, RH, **orbit) if orbit else prt.default_camera(RW, RH)
-            self.cam.apertureRadius = 0.0
-            a = prt.scene_arrays(self.scene.desc)
-            self.v0, self.n0 = a["vertices"].copy(), a["normals"].copy()
-            self.vA, self.nA = deform(self.v0, self.n0, 21)
-            self.vB, self.nB = deform(self.v0, self.n0, 11)
-            self.env = prt.make_sky(64, 32)
-            caster = MotionCaster(self.scene, self.cfg, self.vB)
-            self.mesh, tri, u, v, self.mid, self.hit, self.t, self.behind_mirror = caster.first_hits(self.cam, RW, RH)
-            v0 = np.asarray(self.v0, dtype=np.float64).reshape(-1, 3, 4)[..., :3]
-            self.D = np.where(self.mesh[..., None], _point(v0, tri, u, v) - _point(caster.vtx, tri, u, v), 0.0)
-            self.diag = float(np.linalg.norm(caster.vtx.reshape(-1, 3).max(0) - caster.vtx.reshape(-1, 3).min(0)))
-            for arr in (self.mesh, self.D, self.mid, self.hit, self.t, self.behind_mirror, self.v0, self.n0, self.vA, self.nA, self.vB, self.nB):
-                arr.setflags(write=False)
-            cls._cache[key] = self
-        return cls._cache[key]
-
-    def context(self, prt, motion=True, part=None, pixel_filter=None):
-        r = prt.Renderer(self.cfg, device=0)
-        r.upload_scene(self.scene)
-        if pixel_filter is not None:
-            r.set_pixel_filter(*pixel_filter)
-        r.upload_envmap(self.env)
-        r.set_camera(self.cam)
-        if part is None:
-            r.resize(RW, RH)
-        elif part[0] == "tile":
-            r.set_tile(RW, RH, part[1], part[2])
-        else:
-            r.set_row_blocks(RW, RH, 16, 2, part[1])
-        if motion:
-            r.set_motion(True)
-        return r
-
-    def check(self, plane, what):
-        """the plane of a K = 1 guide render after the geometry went from the uploaded one to B, against the caster; returns the largest
-        deviation of D over the matching pixels"""
-        m, D = plane[..., 3], plane[..., :3].astype(np.float64)
-        assert ((m == 0) | (m == 1)).all(), what
-        dev = np.abs(D - self.D).max(-1)
-        match = ((m > 0) == self.mesh) & (dev <= 1e-3 * self.diag)
-        assert (~match).mean() <= 0.005, "%s: %.2f %% of the pixels differ from the caster" % (what, 100 * (~match).mean())
-        assert (D[m == 0] == 0).all(), what
-        return float(dev[match].max())
-
 
 MIN_BEHIND_MIRROR = 20          # pixels of cornell_mixed (the camera of test_only_direct_mesh_hits_move) that see the mesh in the mirror sphere
 

@@ -20,11 +20,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from mirrors import NODE_T
 from support import assert_same_render
 
 HIP = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd", "csrc", "hip")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-NODE_T = np.dtype([("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)])
 f32 = np.float32
 
 MAX_SLOTS = (2 ** 32 - 1) // 48          # 89 478 485 records of 48 bytes stay below 4 GiB
@@ -159,8 +159,6 @@ def _render(r, prt):
 
 def test_the_packed_far_end_is_where_the_test_says(prt, far_end):
     """pack_scene of the case (host only): three pairs, 40 slots, the view-filling triangle in the last slot, and the OBJ material last"""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
     import refit_api
     p = refit_api.Packed(far_end.cfg, far_end.desc)
     got = p.get()

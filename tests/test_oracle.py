@@ -3,46 +3,20 @@ build, against the reference build itself where it is present (development conta
 through size-independent properties.  The tests that compare with the reference build on inputs of
 their own find its outputs in tests/golden/ref_checks.json (digests of the exact bits) and
 tests/golden/ref_libm_images.npz (tests/golden/make_ref_checks.py)."""
-import hashlib
 import json
 import os
 
 import numpy as np
 import pytest
 
-from conftest import ALPHA_VARIANTS, variant_config, GOLDEN, VARIANTS, VIEW_VARIANTS, variant_camera
-
-
-def setup(prt, variant, W, H):
-    scene_json, phase, use_env = VARIANTS[variant]
-    scene = prt.HostScene(scene_json)
-    cfg = variant_config(scene, variant)
-    cfg.phase_function = phase
-    return scene, cfg, variant_camera(prt, variant, W, H), (prt.make_sky(64, 32) if use_env else None)
+from conftest import ALPHA_VARIANTS, GOLDEN, VARIANTS, VIEW_VARIANTS
+from cases import (dragon_inputs, DRAGON_SIZE, EQUALS_CAMERA, equals_inputs, EQUALS_SIZE, LIBM_CASES, libm_inputs, LIBM_SIZE, nan_slabs_inputs,
+                   NAN_SLABS_SIZE, output_digests)
+from support import variant_case as setup
 
 
 REF_CHECKS = os.path.join(GOLDEN, "ref_checks.json")
 REF_LIBM_IMAGES = os.path.join(GOLDEN, "ref_libm_images.npz")
-EQUALS_SIZE, EQUALS_FRAMES, EQUALS_CAMERA = (45, 27), 70, (-0.3, 0.15, -0.1)      # (d_yaw, d_pitch, d_radius) of the orbit camera
-DRAGON_SIZE, DRAGON_FRAMES = (40, 24), 40
-NAN_SLABS_SIZE, NAN_SLABS_FRAMES = (33, 21), 60
-LIBM_SIZE, LIBM_FRAMES = 48, 768
-
-
-def _digest(bits):
-    bits = np.ascontiguousarray(bits)
-    return hashlib.sha256(("%s %s " % (bits.dtype.str, bits.shape)).encode() + bits.tobytes()).hexdigest()
-
-
-def output_digests(oracle, state, img):
-    """SHA-256 of exactly the bits oracle.state_fields_equal (per field) and oracle.images_equal compare"""
-    fields = {}
-    for f in oracle.STATE_FIELDS:
-        x = state[f]
-        if f in ("origin", "dir", "mask"):
-            x = x[..., :3]
-        fields[f] = _digest(oracle.float_bits(x) if x.dtype.kind == "f" else x)
-    return {"state": fields, "image": _digest(oracle.float_bits(img))}
 
 
 def assert_reference_outputs(oracle, key, state, img):
@@ -51,31 +25,6 @@ def assert_reference_outputs(oracle, key, state, img):
     got = output_digests(oracle, state, img)
     assert [f for f in oracle.STATE_FIELDS if got["state"][f] != want["state"][f]] == []
     assert got["image"] == want["image"]
-
-
-def equals_inputs(prt, variant):
-    """different size / frame count / camera than the goldens"""
-    W, H = EQUALS_SIZE
-    scene, cfg, _, env = setup(prt, variant, W, H)
-    d_yaw, d_pitch, d_radius = EQUALS_CAMERA
-    return scene, cfg, prt.orbit_camera(W, H, d_yaw=d_yaw, d_pitch=d_pitch, d_radius=d_radius), env, prt.seed_pairs(EQUALS_FRAMES)
-
-
-def dragon_inputs(prt):
-    prt.ensure_dragon_standin()
-    scene = prt.HostScene("cornell_dragon.json")
-    return scene, scene.config(), prt.default_camera(*DRAGON_SIZE), prt.seed_pairs(DRAGON_FRAMES)
-
-
-def nan_slabs_inputs(prt):
-    W, H = NAN_SLABS_SIZE
-    scene, cfg, _, env = setup(prt, "cornell_coat", W, H)
-    return scene, cfg, prt.orbit_camera(W, H, d_aperture=-1.0), env, prt.seed_pairs(NAN_SLABS_FRAMES)   # apertureRadius clamps to 0: pinhole
-
-
-def libm_inputs(prt, std):
-    scene, cfg, _, env = setup(prt, std, LIBM_SIZE, LIBM_SIZE)
-    return scene, cfg, prt.default_camera(LIBM_SIZE, LIBM_SIZE), env, prt.seed_pairs(LIBM_FRAMES)
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS) + ["cornell_diffuse_spp"])
@@ -198,10 +147,6 @@ def test_axis_parallel_rays_nan_slabs(prt, oracle):
         assert oracle.state_fields_equal(rstate, state) == [] and oracle.images_equal(rimg, img)
     # premise (by construction, camera.cl:26-52): view.x = up.x = position.x = 0 -> hAxis = (+-1,0,0), vAxis.x = 0,
     # and at x = (W-1)/2 the factor 2*sx-1 is exactly 0, so origin.x = dir.x = 0 for the whole centre column
-
-
-LIBM_CASES = [("cornell_diffuse", "cornell_diffuse_libm", False, 0), ("cornell_roughcond", "cornell_roughcond_libm", True, 0),
-              ("cornell_media_hg", "cornell_media_hg_libm", True, 1)]
 
 
 @pytest.mark.parametrize("std,libm,use_env,phase", LIBM_CASES)

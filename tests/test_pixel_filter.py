@@ -4,7 +4,6 @@ radius with the table rebuilt in float64), their distribution is the filter's ma
 filter instances equals the unfiltered kernels bit for bit in every mode, an emitter's edge pixels carry the filter-weighted coverage, the device
 offsets are the host's, splits, adaptive freezing, checkpoints and guides keep their invariants, refused configs and the CLI."""
 import ctypes as C
-import math
 import os
 import subprocess
 
@@ -12,93 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from cases import filter_setup as _setup, _quad_scene
+from mirrors import camera_basis, DEFAULT_R, KINDS, lowbias32, marginal_cdf, offsets_ref, sample_u, SETS
 from support import bits as _bits, pkg as _pkg
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
-KINDS = {"box": 1, "tent": 2, "gaussian": 3, "blackman-harris": 4}
-DEFAULT_R = {"box": 0.5, "tent": 1.0, "gaussian": 1.5, "blackman-harris": 2.0}
-BH = (0.35875, 0.48829, 0.14128, 0.01168)
-
-
-# ---- prt.h in numpy ----------------------------------------------------------------------------------------------------------------------------
-
-def lowbias32(v):
-    v = np.asarray(v, dtype=np.uint32)
-    with np.errstate(over="ignore"):
-        v = v ^ (v >> np.uint32(16)); v = v * np.uint32(0x7FEB352D)
-        v = v ^ (v >> np.uint32(15)); v = v * np.uint32(0x846CA68B)
-        return v ^ (v >> np.uint32(16))
-
-
-def sample_u(gx, gy, k):
-    """(u, v) of paths k (uint32 array) of global pixel (gx, gy): float32, exact"""
-    k = np.asarray(k, dtype=np.uint32)
-    with np.errstate(over="ignore"):
-        s = np.uint32(gy) * np.uint32(0x9E3779B9) + np.uint32(gx)
-        ux = k * np.uint32(3242174889) + lowbias32(s)
-        uy = k * np.uint32(2447445414) + lowbias32(s ^ np.uint32(0x68E31DA4))
-    f = lambda x: (x >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    return f(ux), f(uy)
-
-
-def marginal_cdf(kind, x, r):
-    """the normalised CDF of the kind's 1-D profile on [-r, r], float64, closed form"""
-    x = np.clip(np.asarray(x, dtype=np.float64), -r, r)
-    if kind == "box":
-        return (x + r) / (2 * r)
-    if kind == "tent":
-        return np.where(x < 0, (x + r) ** 2 / (2 * r * r), 1 - (r - x) ** 2 / (2 * r * r))
-    if kind == "gaussian":
-        s = r / 3.0
-        c = math.exp(-r * r / (2 * s * s))
-        erf = np.vectorize(math.erf)
-        G = lambda t: s * math.sqrt(math.pi / 2) * erf(t / (s * math.sqrt(2))) - c * t
-    else:
-        a0, a1, a2, a3 = BH
-        G = lambda t: (a0 * t + a1 * r / math.pi * np.sin(math.pi * t / r) + a2 * r / (2 * math.pi) * np.sin(2 * math.pi * t / r)
-                       + a3 * r / (3 * math.pi) * np.sin(3 * math.pi * t / r))
-    return (G(x) - G(-r)) / (G(r) - G(-r))
-
-
-def table(kind, r):
-    """T[0 .. 256] of prt.h: F^-1(i / 256) by bisection in float64, rounded to float32, antisymmetric"""
-    T = np.zeros(257, dtype=np.float64)
-    if r > 0:
-        p = np.arange(1, 128) / 256.0
-        lo, hi = np.full(127, -float(r)), np.zeros(127)
-        for _ in range(80):
-            mid = 0.5 * (lo + hi)
-            below = marginal_cdf(kind, mid, r) < p
-            lo, hi = np.where(below, mid, lo), np.where(below, hi, mid)
-        T[1:128] = 0.5 * (lo + hi)
-        T[0] = -r
-    T[129:] = -T[127::-1]
-    T[128] = 0.0
-    return T.astype(np.float32)
-
-
-def warp(kind, r, u, T=None):
-    f = np.float32
-    u = np.asarray(u, dtype=f)
-    r = f(r)
-    if kind == "box":
-        return (u - f(0.5)) * (f(2) * r)
-    if kind == "tent":
-        with np.errstate(invalid="ignore"):
-            lo = r * (np.sqrt(f(2) * u) - f(1))
-            hi = r * (f(1) - np.sqrt(f(2) - f(2) * u))
-        return np.where(u < f(0.5), lo, hi).astype(f)
-    t = u * f(256)
-    j = np.minimum(t.astype(np.int64), 255)
-    t = t - j.astype(f)
-    return (T[j] + t * (T[j + 1] - T[j])).astype(f)
-
-
-def offsets_ref(kind, r, gx, gy, k0, n):
-    k = (np.uint64(k0) + np.arange(n, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
-    u, v = sample_u(gx, gy, k.astype(np.uint32))
-    T = table(kind, r) if kind in ("gaussian", "blackman-harris") else None
-    return np.stack([warp(kind, r, u, T), warp(kind, r, v, T)], -1)
 
 
 # ---- no GPU ------------------------------------------------------------------------------------------------------------------------------------
@@ -171,23 +88,6 @@ def test_cli_refuses_an_unknown_filter():
 
 # ---- on the GPU --------------------------------------------------------------------------------------------------------------------------------
 
-def _setup(prt, scene_json, W, H, pinhole=False, env=False, cfg_edit=None, text=False):
-    scene = prt.HostScene(scene_json, text=text)
-    cfg = scene.config()
-    if cfg_edit:
-        cfg_edit(cfg)
-    cam = prt.default_camera(W, H)
-    if pinhole:
-        cam.apertureRadius = 0.0
-    r = prt.Renderer(cfg, device=0)
-    r.upload_scene(scene)
-    if env:
-        r.upload_envmap(prt.make_sky(64, 32))
-    r.set_camera(cam)
-    r.resize(W, H)
-    return scene, cfg, cam, r
-
-
 def _state_fb(r):
     return np.ascontiguousarray(r.read_state()).view(np.uint8), _bits(r.read_framebuffer())
 
@@ -225,11 +125,6 @@ def test_default_unchanged(prt):
     r.close()
 
 
-SETS = [("cornell_diffuse.json", False, "LIGHT|DIFF"), ("cornell_coat.json", False, "COAT"), ("cornell_roughcond.json", True, "ROUGH_COND"),
-        ("cornell_roughdiel.json", True, "ROUGH_DIEL"), ("cornell_diffuse.json", False, "generic"), ("cornell_media.json", True, "medium"),
-        ("cornell_mixed.json", True, "generic")]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("scene_json,env,tag", SETS)
 def test_zero_radius_through_the_filter_instances_equals_none(prt, scene_json, env, tag):
@@ -253,31 +148,10 @@ def test_zero_radius_through_the_filter_instances_equals_none(prt, scene_json, e
     r.close()
 
 
-def _quad_scene(prt, W, H):
-    """a quad emitter with slanted edges 5 units ahead of the default camera, its normal cross(e0, e1) pointing away from the camera (hit_quad
-    takes rays with dot(n, dir) > 0); black default environment, no OBJ"""
-    cam = prt.default_camera(W, H)
-    cam.apertureRadius = 0.0
-    P, view, up = (np.array(x[:3], dtype=np.float64) for x in (cam.position, cam.view, cam.up))
-    view, up = view / np.linalg.norm(view), up / np.linalg.norm(up)
-    h = np.cross(view, up); h /= np.linalg.norm(h)
-    v = np.cross(h, view); v /= np.linalg.norm(v)
-    c = P + 5.0 * view
-    e0 = -0.35 * h + 1.0 * v
-    e1 = 1.2 * h + 0.3 * v
-    q = [float(x) for x in np.concatenate([c, e0, e1])]
-    js = ('{"settings":{"MAX_BOUNCES":4,"MAX_DIFF_BOUNCES":4,"MAX_SPEC_BOUNCES":4,"MAX_TRANS_BOUNCES":4,"MAX_SCATTERING_EVENTS":4,'
-          '"MARCHING_STEPS":16,"SHADOW_MARCHING_STEPS":16},"scene":{"spheres":[],"quads":[{"vertices":%s,"material":{"color":[3.0,3.0,3.0],"type":0}}]}}'
-          % ("[" + ",".join("%.9g" % x for x in q) + "]"))
-    q = np.array(q, dtype=np.float32).astype(np.float64)
-    return js, cam, q[:3], q[3:6], q[6:9]
-
-
 def _coverage(prt, cam, W, H, c, e0, e1, kind, r, N=96):
     """the filter-weighted coverage of each pixel by the quad through the pinhole camera model of prt.h (float64): an N x N grid over [-r, r]^2 per
     pixel, each cell weighted by its exact filter mass.  The quad is hit_quad's region: 0 <= (X - anchor).e <= e.e for both edges, anchor =
     c - (e0 + e1) / 2 (with edges that are not orthogonal not the parallelogram they span)"""
-    from test_temporal import camera_basis
     Pc, M, Hz, Vt = camera_basis(cam)
     edges = np.linspace(-r, r, N + 1)
     w1 = np.diff(marginal_cdf(kind, edges, r))

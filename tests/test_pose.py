@@ -1,6 +1,6 @@
 """prt_set_skin / prt_pose: the mesh posed on the device from per-frame bone matrices (include/prt.h; csrc/hip/pt_pose.h / .hip).
 
-`mirror_pose` below restates prt.h's formulas in float32 numpy -- every operation rounded to f32, the blend summed left to right from +0 with
+`mirror_pose` (tests/mirrors.py) restates prt.h's formulas in float32 numpy -- every operation rounded to f32, the blend summed left to right from +0 with
 np.where(w != 0, w * m, 0) -- and shares no code with the body.  The body (run on the host by tests/emu/pose_emu.cpp) and the device (through
 the C ABI) must give its bytes.
 
@@ -9,24 +9,17 @@ the mirror at the sizes where a one-lane-per-corner kernel can go wrong (3, 66, 
 scene after a pose against a second context that was given the mirror's arrays through prt_update_vertices / prt_rebuild_bvh -- the path
 tests/test_refit.py and tests/test_rebuild.py pin to the CPU oracle."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, variant_camera
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_refit import Case, _bytes                                                     # noqa: E402
-from test_rebuild import _leaf_root_desc                                                # noqa: E402
+from cases import (_assert_equal, bones, _everything, identity, pose_cache as _cache, pose_context as _context, POSE_FRAME, pose_scene as _scene,
+                   REBUILD, REFIT, _refused, _skin, skin_case, T_TEAPOT, teapot)
+from mirrors import mirror_pose
+from support import bytes_flat as _bytes
 
 f32 = np.float32
-W, H, FRAMES = 32, 24, 48
-REFIT, REBUILD = 0, 1
-T_TEAPOT = 6320
+W, H, FRAMES = POSE_FRAME
 
 
 @pytest.fixture(scope="module")
@@ -34,106 +27,6 @@ def emu():
     import pose_api
     pose_api.lib()
     return pose_api
-
-
-# ---- the mirror ------------------------------------------------------------------------------------------------------------------------------
-
-def mirror_pose(rest_v, rest_n, index, weight, matrices):
-    """(vertices, normals) float32 [n, 4] by the formulas of prt.h; normals None without rest normals"""
-    v = np.ascontiguousarray(rest_v, dtype=f32).reshape(-1, 4)
-    idx = np.ascontiguousarray(index, dtype=np.uint16).reshape(-1, 4).astype(np.int64)
-    w = np.ascontiguousarray(weight, dtype=f32).reshape(-1, 4)
-    M = np.ascontiguousarray(matrices, dtype=f32).reshape(-1, 3, 4)
-    n = len(v)
-    A = np.zeros((n, 3, 4), dtype=f32)
-    with np.errstate(all="ignore"):
-        for k in range(4):
-            wk = w[:, k][:, None, None]
-            A = A + np.where(wk != 0, wk * M[idx[:, k]], f32(0))
-        x, y, z = v[:, 0], v[:, 1], v[:, 2]
-        out_v = np.zeros((n, 4), dtype=f32)
-        for i in range(3):
-            out_v[:, i] = ((A[:, i, 0] * x + A[:, i, 1] * y) + A[:, i, 2] * z) + A[:, i, 3]
-        assert A.dtype == f32
-        if rest_n is None:
-            return out_v, None
-        r = np.ascontiguousarray(rest_n, dtype=f32).reshape(-1, 4)
-        nx, ny, nz = r[:, 0], r[:, 1], r[:, 2]
-        q = np.stack([(A[:, i, 0] * nx + A[:, i, 1] * ny) + A[:, i, 2] * nz for i in range(3)], axis=1)
-        L = np.sqrt((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2])
-        out_n = np.zeros((n, 4), dtype=f32)
-        out_n[:, :3] = np.where((L > 0)[:, None], q / L[:, None], q)
-        assert q.dtype == f32 and L.dtype == f32
-    return out_v, out_n
-
-
-# ---- skins -----------------------------------------------------------------------------------------------------------------------------------
-
-def bones(n_bones, seed, amount=0.35):
-    """n_bones row-major 3x4 matrices float32 [n_bones, 12]: a rotation by up to `amount` rad about a random axis, a scale near 1, a small shift"""
-    rng = np.random.default_rng(seed)
-    axis = rng.normal(size=(n_bones, 3))
-    axis /= np.linalg.norm(axis, axis=1)[:, None]
-    ang = rng.uniform(-amount, amount, n_bones)
-    K = np.zeros((n_bones, 3, 3))
-    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -axis[:, 2], axis[:, 1], axis[:, 2], -axis[:, 0], -axis[:, 1], axis[:, 0]
-    R = np.eye(3)[None] + np.sin(ang)[:, None, None] * K + (1 - np.cos(ang))[:, None, None] * (K @ K)
-    M = np.zeros((n_bones, 3, 4))
-    M[:, :, :3] = R * rng.uniform(0.9, 1.1, n_bones)[:, None, None]
-    M[:, :, 3] = rng.uniform(-0.05, 0.05, (n_bones, 3))
-    return np.ascontiguousarray(M.reshape(n_bones, 12), dtype=f32)
-
-
-def identity(n_bones):
-    return np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=f32), (n_bones, 1))
-
-
-def influences(corners, n_bones, seed, rigid=False):
-    """(index uint16 [corners, 4], weight float32 [corners, 4]): four random influences with positive weights that sum to about 1, or rigid
-    parts -- w = (1, 0, 0, 0), part = triangle index mod min(3, n_bones), the three unused indices random"""
-    rng = np.random.default_rng(seed)
-    index = rng.integers(0, n_bones, (corners, 4)).astype(np.uint16)
-    if rigid:
-        index[:, 0] = (np.arange(corners) // 3) % min(3, n_bones)
-        weight = np.zeros((corners, 4), dtype=f32)
-        weight[:, 0] = 1
-        return index, weight
-    w = rng.uniform(0.05, 1.0, (corners, 4))
-    return index, np.ascontiguousarray(w / w.sum(axis=1)[:, None], dtype=f32)
-
-
-_cache = {}
-
-
-def teapot(prt):
-    """cornell_coat through test_refit.Case at this file's frame size: rest pose v0, n0"""
-    if "teapot" not in _cache:
-        case = Case(prt, "cornell_coat")
-        case.cam = variant_camera(prt, "cornell_coat", W, H)
-        assert len(case.v0) == 3 * T_TEAPOT
-        _cache["teapot"] = case
-    return _cache["teapot"]
-
-
-def skin_case(prt, T, n_bones, rigid=False, seed=5):
-    """the first T triangles of the teapot with a skin of n_bones and the frame's matrices; the mirror's pose (computed once, shared, read-only).
-    65 536 bones: index 65 535 is used once, by the last corner's heaviest influence"""
-    key = ("skin", T, n_bones, rigid, seed)
-    if key not in _cache:
-        case = teapot(prt)
-        v0, n0 = case.v0[:3 * T].copy(), case.n0[:3 * T].copy()
-        index, weight = influences(3 * T, n_bones, seed, rigid)
-        if n_bones == 65536:
-            index[index == 65535] = 0
-            index[-1, int(np.argmax(weight[-1]))] = 65535
-            assert (index == 65535).sum() == 1
-        M = bones(n_bones, seed + 1)
-        want_v, want_n = mirror_pose(v0, n0, index, weight, M)
-        for a in (v0, n0, index, weight, M, want_v, want_n):
-            a.setflags(write=False)
-        assert np.isfinite(want_v).all() and not np.array_equal(want_v[:, :3], v0[:, :3])
-        _cache[key] = dict(T=T, n_bones=n_bones, v0=v0, n0=n0, index=index, weight=weight, M=M, v=want_v, n=want_n)
-    return _cache[key]
 
 
 # ---- CPU: the body on the host ---------------------------------------------------------------------------------------------------------------
@@ -240,47 +133,6 @@ def test_skin_checks(prt, emu):
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------------
-
-def _context(prt, s, leaf_root=True):
-    """a context over the first T triangles of the teapot (rest pose) under a leaf root, or over the whole teapot under its own tree"""
-    case = teapot(prt)
-    desc = _leaf_root_desc(prt, case.desc, s["v0"], s["n0"]) if leaf_root else case.desc
-    assert leaf_root or s["T"] == T_TEAPOT
-    r = prt.Renderer(case.cfg, device=0)
-    r.upload_scene(desc)
-    r.set_camera(case.cam)
-    r.resize(W, H)
-    return r
-
-
-def _skin(r, s, normals=True):
-    r.set_skin(s["v0"], s["n0"] if normals else None, s["index"], s["weight"], s["n_bones"])
-
-
-def _scene(r):
-    nodes, prims = r.read_bvh()
-    return {"bounds": r.read_bvh_bounds(), "nodes": nodes, "prims": prims, "normals": r.read_normals()}
-
-
-def _everything(prt, r):
-    out = _scene(r)
-    r.reset()
-    r.render_frames(prt.seed_pairs(FRAMES))
-    out["state"], out["framebuffer"] = r.read_state(), r.read_framebuffer()
-    return out
-
-
-def _assert_equal(got, want, what):
-    for k in want:
-        assert got[k].shape == want[k].shape and np.array_equal(_bytes(got[k]), _bytes(want[k])), "%s: %s differs" % (what, k)
-
-
-def _refused(prt, call, code=None):
-    with pytest.raises(prt.PrtError) as e:
-        call()
-    assert e.value.code == (prt.PRT_ERR_INVALID_ARGUMENT if code is None else code), e.value
-    return e.value
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("T,n_bones", [(T, nb) for T in (1, 22, 86, T_TEAPOT) for nb in (1, 4, 257)] + [(86, 65536)])

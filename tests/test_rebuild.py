@@ -1,37 +1,29 @@
 """prt_rebuild_bvh: new vertices into the uploaded scene and a new Morton-order tree over all T triangles, built on the device (include/prt.h;
 csrc/hip/pt_build.h / .hip), and prt_read_bvh.
 
-`mirror_build` restates rules 1 - 8 of prt.h in numpy and Python ints (the integer trie on the sorted keys, boxes by test_refit's mirror_refit);
+`mirror_build` (tests/mirrors.py) restates rules 1 - 8 of prt.h in numpy and Python ints (the integer trie on the sorted keys, boxes by mirror_refit);
 pack_scene of the mirror's tree under PRT_PAIR_ORDER=bfs is what every buffer and table must equal, byte for byte.  Every comparison here is
 equality of bytes; the one exception is the motion plane, held to what tests/test_motion.py's caster check allows.
 
 CPU tests run the kernels' bodies on the host (tests/emu/build_emu.cpp); GPU tests run the library against oracle/pt_oracle.c."""
-import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT, VARIANTS, variant_camera, variant_config
-from support import assert_same_render as _assert_same, bytes_flat as _bytes
+from conftest import PKG_NAME, ROOT
+from cases import callers_tree, Case, deform, _leaf_root_desc, refit_oracle_render as refit_oracle, Rendered, _soup, Teapot, _with
+from mirrors import D_BOUND, DEFAULT_LEAF, mirror_build, mirror_keys, mirror_refit
+from support import assert_api, assert_same_render as _assert_same, bytes_flat as _bytes
 
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-NODE_T = np.dtype([("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)])
-W, H, FRAMES = 48, 32, 24
+W, H, FRAMES = Teapot.W, Teapot.H, Teapot.FRAMES
 f32 = np.float32
 NEW_API = ("prt_rebuild_bvh", "prt_rebuild_bvh_device", "prt_read_bvh")
-DEFAULT_LEAF = 4                # what max_leaf = 0 stands for (prt.h)
 
 
 def test_api_is_declared_exported_and_bound(prt):
-    header = open(os.path.join(ROOT, "include", "prt.h")).read()
-    lib = prt.load_library()
-    for name in NEW_API:
-        assert ("int %s(prt_ctx*" % name) in header, name
-        assert hasattr(lib, name), name
+    assert_api(NEW_API, prt)
     assert callable(prt.Renderer.rebuild_bvh) and callable(prt.Renderer.read_bvh)
     assert "hip/pt_build.hip" in open(os.path.join(ROOT, PKG_NAME, "build.py")).read()
 
@@ -52,163 +44,7 @@ def monkeypatch_module():
     mp.undo()
 
 
-# ---- the mirror ------------------------------------------------------------------------------------------------------------------------------
-
-def mirror_refit(nodes, primitive_indices, vertices):
-    """test_refit.mirror_refit re-stated: leaf boxes from the vertices in leaf order (vertices 0, 1, 2 of each triangle), inner boxes = child 0's
-    with child 1's merged, children before parents"""
-    out = nodes.copy()
-    v = np.ascontiguousarray(vertices, dtype=f32).reshape(-1, 4)
-    order, stack = [], [0]
-    while stack:
-        n = stack.pop()
-        order.append(n)
-        if not out[n]["leaf"]:
-            stack += [int(out[n]["first"]), int(out[n]["first"]) + 1]
-    for n in reversed(order):
-        first, count = int(out[n]["first"]), int(out[n]["count"])
-        if out[n]["leaf"]:
-            if count == 0:
-                continue
-            fv = primitive_indices[first:first + count].astype(np.uint32) * np.uint32(3)
-            pts = v[(fv[:, None] + np.arange(3, dtype=np.uint32)[None, :]).reshape(-1), :3]
-            lo, hi = pts[0].copy(), pts[0].copy()
-            for c in pts[1:]:
-                lo = np.where(c < lo, c, lo)
-                hi = np.where(c > hi, c, hi)
-        else:
-            b0, b1 = out[first]["bounds"], out[first + 1]["bounds"]
-            lo, hi = b0[0::2].copy(), b0[1::2].copy()
-            lo = np.where(b1[0::2] < lo, b1[0::2], lo)
-            hi = np.where(b1[1::2] > hi, b1[1::2], hi)
-        out[n]["bounds"][0::2] = lo
-        out[n]["bounds"][1::2] = hi
-    return out
-
-
-def deform(vertices, normals, seed):
-    """test_refit.deform re-stated: a scale of y plus a twist about y, float32, from a seed"""
-    rng = np.random.default_rng(seed)
-    sy, tw = f32(rng.uniform(0.8, 1.25)), f32(rng.uniform(-0.6, 0.6))
-    v, n = np.array(vertices, dtype=f32).reshape(-1, 4), np.array(normals, dtype=f32).reshape(-1, 4)
-    ang = tw * v[:, 1]
-    c, s = np.cos(ang).astype(f32), np.sin(ang).astype(f32)
-    for a in (v, n):
-        x, z = a[:, 0].copy(), a[:, 2].copy()
-        a[:, 0] = c * x + s * z
-        a[:, 2] = c * z - s * x
-    v[:, 1] = v[:, 1] * sy
-    return v, n
-
-
-def mirror_keys(vertices):
-    """rules 1 - 4: the sorted keys as Python ints"""
-    v = np.ascontiguousarray(vertices, dtype=f32).reshape(-1, 3, 4)[:, :, :3]
-    lo, hi = v[:, 0].copy(), v[:, 0].copy()
-    for k in (1, 2):
-        lo = np.where(v[:, k] < lo, v[:, k], lo)
-        hi = np.where(v[:, k] > hi, v[:, k], hi)
-    c = lo * f32(0.5) + hi * f32(0.5)
-    assert c.dtype == f32
-    elo, ehi = c.min(0) + f32(0.0), c.max(0) + f32(0.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        scale = np.where(ehi > elo, f32(1024.0) / (ehi - elo), f32(0.0)).astype(f32)
-    t = (c - elo) * scale
-    assert t.dtype == f32
-    q = np.where(t < f32(1023.0), t, f32(1023.0)).astype(np.uint32)
-    keys = []
-    for i in range(len(v)):
-        code = 0
-        for bit in range(10):
-            for axis in range(3):                  # x in the highest bit of each triple, then y, then z
-                code |= ((int(q[i, axis]) >> bit) & 1) << (3 * bit + 2 - axis)
-        keys.append((code << 32) | i)
-    return sorted(keys), q
-
-
-_built = {}
-
-
-def mirror_build(vertices, max_leaf):
-    """rules 1 - 8: (nodes, primitive_indices, levels of pairs, stack_levels); computed once per input, shared, never written to"""
-    key = (hash(np.ascontiguousarray(vertices, dtype=f32).tobytes()), int(max_leaf))
-    if key not in _built:
-        _built[key] = _mirror_build(vertices, max_leaf)
-        for a in _built[key][:2]:
-            a.setflags(write=False)
-    return _built[key]
-
-
-def _mirror_build(vertices, max_leaf):
-    keys, _ = mirror_keys(vertices)
-    T = len(keys)
-    assert len(set(keys)) == T
-    prims = np.zeros(T, dtype=np.uint64)
-    if T <= max_leaf:
-        nodes = np.zeros(1, dtype=NODE_T)
-        nodes[0]["count"], nodes[0]["leaf"] = T, 1
-        prims[:] = [k & 0xFFFFFFFF for k in keys]
-        return mirror_refit(nodes, prims, vertices), prims, 0, 1
-    queue = [(0, T - 1, 0, 0)]                     # inner ranges in breadth-first order: (a, b, depth, pairs with two inner children above)
-    recs, slot, head, deepest, most_two = [], 0, 0, 0, 0
-    while head < len(queue):
-        a, b, depth, two_above = queue[head]
-        head += 1
-        bit = (keys[a] ^ keys[b]).bit_length() - 1
-        lo_, hi_ = a, b                            # the largest g in [a, b) whose key has a 0 in `bit`: the keys are sorted
-        while lo_ < hi_:
-            mid = (lo_ + hi_ + 1) // 2
-            if (keys[mid] >> bit) & 1:
-                hi_ = mid - 1
-            else:
-                lo_ = mid
-        g = lo_
-        assert a <= g < b and not (keys[g] >> bit) & 1 and (keys[g + 1] >> bit) & 1
-        kids = [(a, g), (g + 1, b)]
-        inner = [y - x + 1 > max_leaf for x, y in kids]
-        two = two_above + (1 if all(inner) else 0)
-        most_two, deepest = max(most_two, two), max(deepest, depth)
-        rec = []
-        for (x, y), is_inner in zip(kids, inner):
-            if is_inner:
-                rec.append((0, 2 * len(queue) + 1, 0))
-                queue.append((x, y, depth + 1, two))
-            else:
-                rec.append((1, slot, y - x + 1))
-                prims[slot:slot + y - x + 1] = [k & 0xFFFFFFFF for k in keys[x:y + 1]]
-                slot += y - x + 1
-        recs.append(rec)
-    assert slot == T
-    nodes = np.zeros(2 * len(recs) + 1, dtype=NODE_T)
-    nodes[0]["first"] = 1
-    for k, rec in enumerate(recs):
-        for ch, (leaf, first, count) in enumerate(rec):
-            nodes[2 * k + 1 + ch]["leaf"], nodes[2 * k + 1 + ch]["first"], nodes[2 * k + 1 + ch]["count"] = leaf, first, count
-    return mirror_refit(nodes, prims, vertices), prims, deepest + 1, most_two + 1
-
-
-def _with(prt, desc, v, n, nodes=None, prims=None, T=None):
-    """a copy of `desc` holding the given buffers; the arrays are kept alive on the copy"""
-    d = prt.SceneDesc.from_buffer_copy(bytes(desc))
-    d._keep = [np.ascontiguousarray(v, dtype=f32), np.ascontiguousarray(n, dtype=f32)]
-    d.vertices, d.normals = (a.ctypes.data_as(C.c_void_p) for a in d._keep)
-    if nodes is not None:
-        nodes, prims = np.ascontiguousarray(nodes), np.ascontiguousarray(prims, dtype=np.uint64)
-        d._keep += [nodes, prims]
-        d.bvh_nodes, d.bvh_node_count, d.primitive_indices = nodes.ctypes.data_as(C.c_void_p), len(nodes), prims.ctypes.data_as(C.c_void_p)
-    if T is not None:
-        d.triangle_count = T
-    return d
-
-
-def _leaf_root_desc(prt, desc, v, n):
-    """the trivial tree: a leaf root that names every triangle"""
-    T = len(v) // 3
-    nodes = np.zeros(1, dtype=NODE_T)
-    nodes["bounds"] = np.array([-1e3, 1e3] * 3, dtype=f32)
-    nodes[0]["count"], nodes[0]["leaf"] = T, 1
-    return _with(prt, desc, v, n, nodes, np.arange(T, dtype=np.uint64), T=T)
-
+# ---- against the mirror (tests/mirrors.py) -------------------------------------------------------------------------------------------------
 
 _TABLES = ("pairs", "tri_geom", "tri_nrm", "root", "slot_vtx", "level_pairs", "level_first", "node_box", "scalars")
 
@@ -228,43 +64,6 @@ def _check_against_the_mirror(prt, build, p, cfg, desc, v, n, max_leaf, what):
     want = build.Packed(cfg, _with(prt, desc, v, n, nodes, prims, T=len(prims)))
     _assert_tables_equal(p.get(), want.get(), what)
     return nodes, prims
-
-
-class Teapot:
-    """cornell_coat's scene and buffers, and a deformation of it"""
-
-    def __init__(self, prt, seed=11, variant="cornell_coat"):
-        scene_json, phase, use_env = VARIANTS[variant]
-        self.prt, self.scene = prt, prt.HostScene(scene_json)
-        self.cfg = variant_config(self.scene, variant)
-        self.cfg.phase_function = phase
-        self.cam = variant_camera(prt, variant, W, H)
-        self.env = prt.make_sky(64, 32) if use_env else None
-        self.desc = self.scene.desc
-        a = prt.scene_arrays(self.desc)
-        self.v0, self.n0 = a["vertices"].copy(), a["normals"].copy()
-        self.v, self.n = deform(self.v0, self.n0, seed) if seed is not None else (self.v0, self.n0)
-
-
-def _soup(kind, T):
-    rng = np.random.default_rng(1000 + T)
-    v = np.zeros((3 * T, 4), dtype=f32)
-    n = np.zeros((3 * T, 4), dtype=f32)
-    n[:, 1] = 1
-    if kind == "random":
-        v[:, :3] = rng.uniform(-1, 1, (3 * T, 3)).astype(f32)
-    elif kind == "identical":                      # zero extent on all axes: ordered by index alone
-        v[:, :3] = np.tile(np.array([[0, 0, 0.5], [1, 0, 0.5], [0, 1, 0.5]], dtype=f32), (T, 1))
-    elif kind == "planar":                         # one zero-extent axis (every triangle spans the same z range)
-        v[:, :2] = rng.uniform(-1, 1, (3 * T, 2)).astype(f32)
-        v[:, 2] = np.tile(np.array([0.25, 0.25, 0.25], dtype=f32), T)
-    elif kind == "clusters":                       # centres at the extent's ends: codes 0 and 1023, the clamp
-        tri = np.repeat(np.arange(T), 3)
-        off = rng.uniform(0, 1e-3, (3 * T, 3)).astype(f32)
-        v[:, :3] = np.where((tri % 2 == 0)[:, None], f32(-100.0) + off, f32(100.0) - off)
-        v[0:3, :3] = f32(-100.0)                   # (exact ends: degenerate triangles whose centres ARE lo and hi)
-        v[3:6, :3] = f32(100.0)
-    return v, n
 
 
 # ---- CPU: the kernels' bodies on the host ----------------------------------------------------------------------------------------------------
@@ -363,7 +162,6 @@ def test_update_after_a_rebuild_refits_the_new_topology(prt, build):
 
 
 def test_the_old_tree_does_not_matter(prt, oracle, build):
-    from test_emu import callers_tree
     scene, cdesc, keep = callers_tree(prt, oracle)
     tp = Teapot(prt)
     a, b = build.Packed(tp.cfg, cdesc), build.Packed(tp.cfg, tp.desc)
@@ -432,7 +230,6 @@ def test_motion_snapshot_moves_to_the_new_slot_order(prt, build, pending):
 
 
 def test_motion_snapshot_of_triangles_the_old_tree_did_not_hold(prt, oracle, build):
-    from test_emu import callers_tree
     scene, cdesc, keep = callers_tree(prt, oracle)
     tp = Teapot(prt)
     p = build.Packed(tp.cfg, cdesc)
@@ -545,7 +342,6 @@ def test_fresh_upload_of_the_read_back_tree_renders_the_same(prt, oracle):
 
 @pytest.mark.gpu
 def test_update_update_rebuild_update(prt, oracle):
-    from test_refit import Case, _oracle_render as refit_oracle
     a, b = Case(prt, "cornell_coat", seed=21), Case(prt, "cornell_coat", seed=11)
     tp = Teapot(prt)
     r = _context(tp)
@@ -581,7 +377,6 @@ def test_soup_through_a_leaf_root_upload(prt, oracle, T, max_leaf):
 
 @pytest.mark.gpu
 def test_refusals_leave_the_scene_as_it_was(prt, oracle):
-    from test_emu import callers_tree
     tp = Teapot(prt)
     r = prt.Renderer(tp.cfg, device=0)
     with pytest.raises(prt.PrtError) as e:
@@ -646,7 +441,6 @@ def test_lifetime(prt, oracle):
 
 @pytest.mark.gpu
 def test_motion_plane_after_a_rebuild_matches_the_caster(prt):
-    from test_motion import D_BOUND, Rendered
     sc = Rendered(prt, "cornell_coat.json")
     r = sc.context(prt)
     r.rebuild_bvh(sc.vB, sc.nB, 4)

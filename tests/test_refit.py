@@ -1,25 +1,20 @@
 """prt_update_vertices: new vertices into the uploaded scene, the tree refitted on the device (include/prt.h; csrc/hip/pt_refit.h / .hip).
 
 The contract is the one everything here has: bit-identical to the CPU oracle, which is fed the same refitted buffers in the reference's
-layout.  `mirror_refit` below restates prt.h's box rules in numpy on the CALLER'S tree (children before parents, the comparison form that
+layout.  `mirror_refit` (tests/mirrors.py) restates prt.h's box rules in numpy on the CALLER'S tree (children before parents, the comparison form that
 fixes the sign of a zero bound); the triangle records are pack_scene's own expressions, so pack_scene of (new vertices, mirror's nodes) is
 what every buffer must equal, byte for byte.
 
 CPU tests run the kernels' bodies on the host (tests/emu/refit_emu.cpp); GPU tests run the library against oracle/pt_oracle.c."""
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, VARIANTS, variant_camera, variant_config
+from cases import callers_tree, Case, _chain_desc, refit_context as _context, refit_oracle_render as _oracle_render, refit_render as _render
+from mirrors import NODE_T
 from support import assert_same_render as _assert_same, bytes_flat as _bytes
 
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
-NODE_T = np.dtype([("bounds", "<f4", 6), ("first", "<u4"), ("count", "<u4"), ("leaf", "u1"), ("_p", "u1", 3)])
-W, H, FRAMES = 48, 32, 24
+FRAMES = Case.FRAMES
 f32 = np.float32
 
 
@@ -30,82 +25,7 @@ def refit():
     return refit_api
 
 
-# ---- the mirror ------------------------------------------------------------------------------------------------------------------------------
-
-def mirror_refit(nodes, primitive_indices, vertices):
-    """the nodes refitted by the rules of prt.h: leaf boxes from the vertices in leaf order (vertices 0, 1, 2 of each triangle), inner boxes
-    = child 0's with child 1's merged, children before parents; an empty leaf and a node the root does not reach keep their boxes"""
-    out = nodes.copy()
-    v = np.ascontiguousarray(vertices, dtype=f32).reshape(-1, 4)
-    order, stack = [], [0]
-    while stack:
-        n = stack.pop()
-        order.append(n)
-        if not out[n]["leaf"]:
-            stack += [int(out[n]["first"]), int(out[n]["first"]) + 1]
-    for n in reversed(order):                    # reversed pre-order: every child before its parent
-        first, count = int(out[n]["first"]), int(out[n]["count"])
-        if out[n]["leaf"]:
-            if count == 0:
-                continue
-            fv = primitive_indices[first:first + count].astype(np.uint32) * np.uint32(3)
-            pts = v[(fv[:, None] + np.arange(3, dtype=np.uint32)[None, :]).reshape(-1), :3]
-            lo, hi = pts[0].copy(), pts[0].copy()
-            for c in pts[1:]:
-                lo = np.where(c < lo, c, lo)
-                hi = np.where(c > hi, c, hi)
-        else:
-            b0, b1 = out[first]["bounds"], out[first + 1]["bounds"]
-            lo, hi = b0[0::2].copy(), b0[1::2].copy()
-            lo = np.where(b1[0::2] < lo, b1[0::2], lo)
-            hi = np.where(b1[1::2] > hi, b1[1::2], hi)
-        out[n]["bounds"][0::2] = lo
-        out[n]["bounds"][1::2] = hi
-    return out
-
-
-def deform(vertices, normals, seed):
-    """a scale of y plus a twist about y, float32, from a seed (positions and normals turn together)"""
-    rng = np.random.default_rng(seed)
-    sy, tw = f32(rng.uniform(0.8, 1.25)), f32(rng.uniform(-0.6, 0.6))
-    v, n = np.array(vertices, dtype=f32).reshape(-1, 4), np.array(normals, dtype=f32).reshape(-1, 4)
-    ang = tw * v[:, 1]
-    c, s = np.cos(ang).astype(f32), np.sin(ang).astype(f32)
-    for a in (v, n):
-        x, z = a[:, 0].copy(), a[:, 2].copy()
-        a[:, 0] = c * x + s * z
-        a[:, 2] = c * z - s * x
-    v[:, 1] = v[:, 1] * sy
-    return v, n
-
-
-class Case:
-    """a scene, its buffers as numpy, a deformation and the desc holding (new vertices, new normals, mirror's nodes)"""
-
-    def __init__(self, prt, variant, seed=None, desc=None, scene=None, normals_too=True):
-        scene_json, phase, use_env = VARIANTS[variant]
-        self.scene = scene or prt.HostScene(scene_json)
-        self.cfg = variant_config(self.scene, variant)
-        self.cfg.phase_function = phase
-        self.cam = variant_camera(prt, variant, W, H)
-        self.env = prt.make_sky(64, 32) if use_env else None
-        self.desc = desc if desc is not None else self.scene.desc
-        a = prt.scene_arrays(self.desc)
-        self.v0, self.n0, self.pi = a["vertices"].copy(), a["normals"].copy(), a["primitive_indices"].copy()
-        self.nodes0 = a["nodes"].view(NODE_T).copy()
-        self.prt = prt
-        self.set(*(deform(self.v0, self.n0, seed) if seed is not None else (self.v0, self.n0)), normals_too=normals_too)
-
-    def set(self, v, n, normals_too=True):
-        self.v, self.n = np.ascontiguousarray(v, dtype=f32), np.ascontiguousarray(n if normals_too else self.n0, dtype=f32)
-        self.nodes = mirror_refit(self.nodes0, self.pi, self.v)
-        d = self.prt.SceneDesc.from_buffer_copy(bytes(self.desc))
-        d.vertices = self.v.ctypes.data_as(C.c_void_p)
-        d.normals = self.n.ctypes.data_as(C.c_void_p)
-        d.bvh_nodes = self.nodes.ctypes.data_as(C.c_void_p)
-        self.new_desc = d
-        return self
-
+# ---- what the packed tables hold --------------------------------------------------------------------------------------------------------------
 
 def _node_bounds(got):
     """[n_nodes, 6] from a Packed.get(): every node's box where pack_scene put it (node_box), the root's from `root`"""
@@ -159,8 +79,7 @@ def test_bodies_equal_the_mirror(prt, refit, monkeypatch, variant, order):
 
 
 def test_bodies_tighten_a_callers_loose_tree(prt, oracle, refit):
-    """test_emu.callers_tree with UNCHANGED vertices: a fat leaf, leaves sharing triangles, loose boxes that must come out tight"""
-    from test_emu import callers_tree
+    """cases.callers_tree with UNCHANGED vertices: a fat leaf, leaves sharing triangles, loose boxes that must come out tight"""
     scene, desc, keep = callers_tree(prt, oracle)
     case = Case(prt, "cornell_coat", desc=desc, scene=scene)
     p = refit.Packed(case.cfg, case.desc)
@@ -173,22 +92,6 @@ def test_bodies_tighten_a_callers_loose_tree(prt, oracle, refit):
     loose = np.array([-3, 3, -1, 5, -3, 3], dtype=f32)
     assert (b[:, :, 0::2] > loose[0::2]).all() and (b[:, :, 1::2] < loose[1::2]).all(), "a box stayed loose"
     assert p.n_slots == 40 + 40 + 70
-
-
-def _chain_desc(prt, scene, levels):
-    """a caller's chain: every inner node has one single-triangle leaf and the rest of the chain; `levels` pairs nested one in the other (no pair
-    has two inner children: the traversal stack needs one entry)"""
-    nodes = np.zeros(2 * levels + 1, dtype=NODE_T)
-    nodes["bounds"] = np.array([-3, 3, -1, 5, -3, 3], dtype=f32)
-    for k in range(levels):
-        at = 0 if k == 0 else 2 * k
-        nodes[at]["first"], nodes[at]["leaf"] = 2 * k + 1, 0
-        nodes[2 * k + 1]["first"], nodes[2 * k + 1]["count"], nodes[2 * k + 1]["leaf"] = k, 1, 1
-    nodes[2 * levels]["first"], nodes[2 * levels]["count"], nodes[2 * levels]["leaf"] = levels, 1, 1
-    desc = prt.SceneDesc.from_buffer_copy(bytes(scene.desc))
-    desc.bvh_nodes = nodes.ctypes.data_as(C.c_void_p)
-    desc.bvh_node_count = len(nodes)
-    return desc, nodes
 
 
 @pytest.mark.parametrize("order", ["bfs", "dfs"])
@@ -255,35 +158,6 @@ def test_update_without_normals_keeps_trinrm(prt, refit):
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------------------
 
-_oracle_cache = {}
-
-
-def _oracle_render(oracle, case, key):
-    """the oracle's render of the case's new desc (computed once per key, shared, never written to)"""
-    if key not in _oracle_cache:
-        st, img = oracle.Restatement().render(case.cfg, case.new_desc, case.cam, W, H, case.prt.seed_pairs(FRAMES), env=case.env, threads=8)
-        st.setflags(write=False)
-        img.setflags(write=False)
-        _oracle_cache[key] = (st, img)
-    return _oracle_cache[key]
-
-
-def _context(case, desc=None):
-    r = case.prt.Renderer(case.cfg, device=0)
-    r.upload_scene(desc if desc is not None else case.desc)
-    if case.env is not None:
-        r.upload_envmap(case.env)
-    r.set_camera(case.cam)
-    r.resize(W, H)
-    return r
-
-
-def _render(case, r):
-    r.reset()
-    r.render_frames(case.prt.seed_pairs(FRAMES))
-    return r.read_state(), r.read_framebuffer()
-
-
 def _update_render_check(oracle, case, key, device=False):
     r = _context(case)
     if device:
@@ -317,7 +191,6 @@ def test_device_variant_matches_the_host_variant(prt, oracle):
 
 @pytest.mark.gpu
 def test_callers_tree_comes_out_tight(prt, oracle):
-    from test_emu import callers_tree
     scene, desc, keep = callers_tree(prt, oracle)
     case = Case(prt, "cornell_coat", desc=desc, scene=scene)
     r = _context(case)

@@ -19,17 +19,14 @@ bit for bit, and where C <= 0 it returns before it draws."""
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, VARIANTS, variant_config
-from support import assert_same_render as _same
-from support import bits
-from test_codegen_addressing import HEADLINE, HIP, HIPCC, frame_loop, kernel_lines
+from conftest import GOLDEN, ROOT
+from cases import frame_loop, HEADLINE, HIP, HIPCC, kernel_lines
+from support import assert_same_render as _same, bits, variant_case
 
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
 W, H = 24, 20                                   # ragged edge tiles in both directions
 SPP = 3                                         # of the prt_render_spp runs
@@ -50,10 +47,7 @@ CASES = {
 
 def _case(prt, name):
     variant, camera, pick, frames, build = CASES[name]
-    scene_json, phase, use_env = VARIANTS[variant]
-    scene = prt.HostScene(scene_json)
-    cfg = variant_config(scene, variant)
-    cfg.phase_function = phase
+    scene, cfg, _, env = variant_case(prt, variant, W, H)
     if pick is not None:
         cfg.pick_random_light = pick
     if camera == "pinhole":
@@ -62,7 +56,7 @@ def _case(prt, name):
     else:
         cam = prt.default_camera(W, H)
         assert cam.apertureRadius > 0.00001
-    return scene, cfg, cam, (prt.make_sky(64, 32) if use_env else None), prt.seed_pairs(frames), build
+    return scene, cfg, cam, env, prt.seed_pairs(frames), build
 
 
 @pytest.fixture(scope="module")

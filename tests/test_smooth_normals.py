@@ -1,29 +1,22 @@
 """prt_set_smooth_normals: smooth shading normals regenerated on the device from new vertices (include/prt.h; csrc/hip/pt_normals.h / .hip).
 
-`mirror_normals` below restates prt.h's formulas in float32 numpy (every operation rounded to f32, the sum of a corner taken member by
+`mirror_normals` (tests/mirrors.py) restates prt.h's formulas in float32 numpy (every operation rounded to f32, the sum of a corner taken member by
 member in ascending corner order); the kernels' bodies (run on the host by tests/emu/normals_emu.cpp) and the device (through the C ABI)
 must give its bytes.  The mirror finds a group's members with a stable argsort of its own, not with the library's table builder.
 
 CPU tests: the weld, the bodies, the loader equivalence, the group table.  GPU tests: the kernels against the mirror, composition with
 explicit normals, the render against the CPU oracle, lifetime and refusals."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from test_refit import Case, W, H, FRAMES, _context, _render, _assert_same, _bytes      # noqa: E402
-from test_rebuild import _leaf_root_desc                                               # noqa: E402
+from cases import Case, _leaf_root_desc, refit_context as _context, refit_render as _render
+from mirrors import AREA, LOADER_CREASE_COS, mirror_faces, mirror_normals, mirror_weld, UNIT
+from support import assert_same_render as _assert_same, bytes_flat as _bytes
 
 f32 = np.float32
-UNIT, AREA = 0, 1
-LOADER_CREASE_COS = -0.99619470
+W, H, FRAMES = Case.W, Case.H, Case.FRAMES
 
 
 @pytest.fixture(scope="module")
@@ -33,64 +26,13 @@ def emu():
     return normals_api
 
 
-# ---- the mirror ------------------------------------------------------------------------------------------------------------------------------
-
-def mirror_weld(vertices):
-    """groups by bit-identical position after x + 0.0f, numbered by first appearance in corner order"""
-    key = (np.ascontiguousarray(vertices, dtype=f32).reshape(-1, 4)[:, :3] + f32(0.0)).copy().view(np.uint32)
-    _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
-    rank = np.empty(len(first), dtype=np.int64)
-    rank[np.argsort(first, kind="stable")] = np.arange(len(first))
-    return rank[inv.reshape(-1)].astype(np.uint32), len(first)
-
-
-def mirror_faces(vertices):
-    """(r, l, f) of prt.h per face, float32"""
-    v = np.ascontiguousarray(vertices, dtype=f32).reshape(-1, 3, 4)
-    a, b, c = v[:, 0, :3], v[:, 1, :3], v[:, 2, :3]
-    with np.errstate(all="ignore"):
-        u, w = b - a, c - a
-        r = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], axis=1)
-        l = np.sqrt((r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2])
-        f = np.where((l > 0)[:, None], r / l[:, None], r)
-    assert r.dtype == f32 and l.dtype == f32 and f.dtype == f32
-    return r, l, f
-
-
-def mirror_normals(vertices, groups, weighting=UNIT, crease_cos=LOADER_CREASE_COS):
-    """float32 [3T, 4]: the corner rule of prt.h; step k adds member k of every corner's group, so every sum runs in member order"""
-    r, l, f = mirror_faces(vertices)
-    g = np.asarray(groups, dtype=np.int64)
-    n = len(g)
-    order = np.argsort(g, kind="stable")                       # corners by group, ascending corner index within a group
-    count = np.bincount(g, minlength=int(g.max()) + 1)
-    first = np.concatenate([[0], np.cumsum(count)[:-1]])
-    fi = f[np.arange(n) // 3]
-    s = np.zeros((n, 3), dtype=f32)
-    crease = f32(crease_cos)
-    with np.errstate(all="ignore"):
-        for k in range(int(count.max())):
-            act = np.nonzero(count[g] > k)[0]
-            j = order[first[g[act]] + k] // 3
-            fj, me = f[j], fi[act]
-            d = (fj[:, 0] * me[:, 0] + fj[:, 1] * me[:, 1]) + fj[:, 2] * me[:, 2]
-            ok = d >= crease                                   # (False for a NaN d)
-            add = fj if weighting == UNIT else r[j]
-            s[act] = np.where(ok[:, None], s[act] + add, s[act])
-        L = np.sqrt((s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1]) + s[:, 2] * s[:, 2])
-        out = np.zeros((n, 4), dtype=f32)
-        out[:, :3] = np.where((L > 0)[:, None], s / L[:, None], fi)
-    assert s.dtype == f32 and L.dtype == f32
-    return out
-
-
 # ---- meshes ----------------------------------------------------------------------------------------------------------------------------------
 
 _cache = {}
 
 
 def teapot(prt):
-    """cornell_coat through test_refit.Case: rest pose (v0, n0) and the deformed pose of seed 11 (v), with the weld of the rest pose"""
+    """cornell_coat through cases.Case: rest pose (v0, n0) and the deformed pose of seed 11 (v), with the weld of the rest pose"""
     if "teapot" not in _cache:
         case = Case(prt, "cornell_coat", seed=11)
         groups, n_groups = mirror_weld(case.v0)

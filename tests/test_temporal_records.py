@@ -5,105 +5,26 @@ every branch is there on purpose: the n >= 4 switch of the variance, history_cap
 away from its default, reprojection outside and half outside the frame, pixels the card uncovers, points behind the previous camera,
 depth / normal rejections of some of the four taps, non-finite history colours, frames of one row, one column and one pixel, a-trous steps
 larger than the frame.  After every call the record history read back and the picture are compared with the float64 mirrors of
-test_temporal.py and test_denoise.py (the previous history fed to the mirror is the device's own).  Every scenario also runs without a GPU,
+tests/mirrors.py -- temporal_ref, denoise_ref -- (the previous history fed to the mirror is the device's own).  Every scenario also runs without a GPU,
 the mirror standing in for the device, to assert that the branch it is named for holds enough pixels clear of every threshold."""
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from test_denoise import denoise_ref, lum, spatial_variance
-from test_denoise_records import _synthetic, _to_device
-from test_temporal import _close, camera_basis, centre_dirs, project, temporal_ref
-from support import bits as _bits, pkg as _pkg
+from cases import H0, MOVES, _plain_records, _synthetic, T_DEFAULTS, _unit, W0, World
+from mirrors import camera_basis, centre_dirs, _close, denoise_ref, lum, project, spatial_variance, temporal_ref
+from support import assert_api, bits as _bits, pkg as _pkg, to_device as _to_device
 
-PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 NEW_API = ("prt_read_records_history",)
-W0, H0 = 37, 29                          # no multiple of 16, wider than one workgroup
-T_DEFAULTS = dict(alpha_color=0.2, alpha_moments=0.2, tau_z=0.05, cos_n=0.9, history_cap=32)
 
 
 # ---- no GPU --------------------------------------------------------------------------------------------------------------------------------
 
 def test_api_is_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "prt.h")) as f:
-        header = f.read()
-    for name in NEW_API:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-    import importlib
-    capi = importlib.import_module("photorealistic-rendering-using-opencl_amd._capi")
-    assert set(NEW_API) <= {n for n, _, _ in capi.PRT_API}
-    lib = os.path.join(PKG, "libprt.so")
-    if not os.path.exists(lib):
-        import __graft_entry__ as ge
-        ge.build()
-    dll = C.CDLL(lib)
-    for name in NEW_API:
-        assert hasattr(dll, name), name
+    assert_api(NEW_API)
     assert callable(getattr(_pkg().Renderer, "read_records_history"))
 
 
 # ---- the synthetic world ---------------------------------------------------------------------------------------------------------------------
-
-def _unit(v):
-    return v / np.linalg.norm(v, axis=-1, keepdims=True)
-
-
-class World:
-    """two rectangles in world space, placed by the default camera of a W0 x H0 frame: `back` faces it at distance 10 and fills the middle
-    80 % of its view (the rim misses: cov = 0), `card` stands at distance 3.5, tilted, in front of part of it.  Colours and albedos are
-    functions of the world point (of 6 d for a ray that misses), so frames of different cameras show the same world."""
-
-    def __init__(self, prt):
-        P, M, Hz, Vt = camera_basis(prt.default_camera(W0, H0))
-        view, h, v = M - P, _unit(Hz), _unit(Vt)
-        tx, ty = np.linalg.norm(Hz), np.linalg.norm(Vt)
-        cn = _unit(-view + 0.45 * h + 0.2 * v)
-        cu = _unit(np.cross(cn, v))
-        self.surfaces = [(P + 10.0 * view, -view, h, v, 8.0 * tx, 8.0 * ty),
-                         (P + 3.5 * view + 0.25 * h - 0.1 * v, cn, cu, np.cross(cn, cu), 0.55, 0.45)]
-
-    @staticmethod
-    def colour(X):
-        base = 0.7 + 0.2 * np.sin(X @ np.array([[0.9, 0.2, -0.5], [0.3, 1.1, 0.4], [-0.6, 0.5, 0.8]]) + np.array([0.3, 1.7, 2.9]))
-        checker = 0.3 * (np.floor(2.2 * X).sum(-1) % 2)
-        return base + checker[..., None]
-
-    @staticmethod
-    def albedo(X):
-        return 0.5 + 0.3 * np.sin(X @ np.array([[0.5, -0.3, 0.2], [0.1, 0.6, -0.4], [0.3, 0.2, 0.7]]) + np.array([1.0, 2.0, 0.5]))
-
-    def records(self, cam, W, H, seed, noise=0.05):
-        """(records [H, W, 16] float32, surface [H, W]: 0 none, 1 back, 2 card) of camera `cam`; `seed`: the frame's colour noise, alpha and v"""
-        rng = np.random.default_rng(1000 + seed)
-        P = camera_basis(cam)[0]
-        d = centre_dirs(camera_basis(cam), W, H)
-        z = np.full((H, W), np.inf)
-        nrm, sid = np.zeros((H, W, 3)), np.zeros((H, W), dtype=np.int64)
-        for k, (Cc, n, u, v, hu, hv) in enumerate(self.surfaces):
-            with np.errstate(divide="ignore", invalid="ignore"):
-                t = ((Cc - P) @ n) / (d @ n)
-            X = P + d * t[..., None]
-            hit = (t > 1e-6) & (t < z) & (np.abs((X - Cc) @ u) <= hu) & (np.abs((X - Cc) @ v) <= hv)
-            z = np.where(hit, t, z)
-            nrm = np.where(hit[..., None], np.where(((d @ n) < 0)[..., None], n, -n), nrm)        # the normal faces the ray
-            sid = np.where(hit, k + 1, sid)
-        cov = sid > 0
-        X = np.where(cov[..., None], P + d * np.where(cov, z, 0.0)[..., None], 6.0 * d)
-        rec = np.zeros((H, W, 16), dtype=np.float32)
-        rec[..., 0:3] = self.colour(X) + rng.uniform(-noise, noise, (H, W, 3))
-        rec[..., 3] = rng.uniform(0.0, 1.0, (H, W))
-        rec[..., 4:7] = self.albedo(X)
-        rec[..., 7] = cov
-        rec[..., 8:11] = nrm
-        rec[..., 11] = np.where(cov, z, 0.0)
-        rec[..., 12] = rng.uniform(0.005, 0.1, (H, W))
-        rec[..., 13] = 1.0
-        return rec, sid
-
 
 def _geometry(rec, cam, cam_prev):
     """where the mirror projects every pixel of `rec` (camera cam) in the previous camera: x', y', dot(e, f), and the coverage"""
@@ -320,10 +241,6 @@ def scenario_alpha_one(prt, world, seq):
                     assert (np.abs(ref["ci"] - rec[..., 0:3]).max(-1) > 1e-3)[m].mean() > 0.5   # ... while the colour still blends
 
 
-MOVES = [dict(), dict(d_yaw=0.04, d_pitch=0.012), dict(d_yaw=0.10, d_pitch=0.03, d_radius=0.06), dict(d_yaw=0.13, d_pitch=-0.02, d_radius=-0.03),
-         dict(d_yaw=0.06, d_pitch=-0.06, d_radius=0.02)]
-
-
 def scenario_moving(prt, world, seq):
     """a camera that moves by pixels per call: reprojection outside the frame, half outside it (renormalised by the taps inside), and onto
     the card from pixels it has just uncovered.  The populations are counted over the calls of the orbit"""
@@ -534,24 +451,6 @@ def test_non_finite_colours_with_atrous_feedback(prt):
     seq.report()
     rc.close()
     other.close()
-
-
-def _plain_records(W, H, seed):
-    """records of a frame too small for a camera: O(1) colours, unit normals, a depth ramp, one uncovered pixel when there is room"""
-    rng = np.random.default_rng(seed)
-    rec = np.zeros((H, W, 16), dtype=np.float32)
-    rec[..., 0:3] = rng.uniform(0.2, 1.5, (H, W, 3))
-    rec[..., 3] = rng.uniform(0.0, 1.0, (H, W))
-    rec[..., 4:7] = 0.5 + rng.uniform(-0.05, 0.05, (H, W, 3))
-    rec[..., 7] = 1.0
-    n = np.array([0.1, 0.2, 1.0]) + rng.uniform(-0.03, 0.03, (H, W, 3))
-    rec[..., 8:11] = n / np.linalg.norm(n, axis=-1, keepdims=True)
-    rec[..., 11] = 3.0 + 0.05 * np.arange(W)[None, :] + 0.03 * np.arange(H)[:, None]
-    if W * H > 2:
-        rec[H - 1, W - 1, 7:12] = 0.0
-    rec[..., 12] = rng.uniform(0.005, 0.1, (H, W))
-    rec[..., 13] = 1.0
-    return rec
 
 
 @pytest.mark.gpu

@@ -1,5 +1,5 @@
 """Temporal response: the fast history and the clamp against it (prt_set_temporal_response, prt_read_response, prt_read_records_response;
-include/prt.h).  The contract checked here: response_ref, a float64 mirror of the prt.h text built on test_temporal's temporal_ref -- the fast
+include/prt.h).  The contract checked here: response_ref, a float64 mirror of the prt.h text built on temporal_ref (tests/mirrors.py) -- the fast
 history is temporal_ref with the fast colours in the colour lanes, alpha_color = 0 and history_cap = fast_cap; the clamp is two sweeps over the
 window of valid fast texels.  Scenarios on synthetic records reach every branch on purpose (clamped from above and from below, kept, no
 history, windows cut by every edge and corner, non-finite texels inside a window, a non-finite own colour, n cut and n kept, fast_cap = 1,
@@ -17,10 +17,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_denoise import denoise_ref
-from test_temporal import _close, temporal_ref
-from test_temporal_records import MOVES, T_DEFAULTS, World, _plain_records
-from support import bits as _bits, pkg as _pkg, to_device as _to_device
+from cases import meshes_of, move_quad, MOVES, _plain_records, T_DEFAULTS, World
+from mirrors import _close, denoise_ref, temporal_ref
+from support import assert_api, bits as _bits, pkg as _pkg, to_device as _to_device
 
 PKG = os.path.join(ROOT, "photorealistic-rendering-using-opencl_amd")
 HIP = os.path.join(PKG, "csrc", "hip")
@@ -35,22 +34,9 @@ LEFT_OUT_CAP = 0.02                      # of a scenario's pixels: those the com
 # ---- no GPU: the interface -------------------------------------------------------------------------------------------------------------------
 
 def test_api_is_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "prt.h")) as f:
-        header = f.read()
-    for name in NEW_API:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+    header = assert_api(NEW_API)
     assert "typedef struct prt_temporal_response" in header
-    import importlib
-    capi = importlib.import_module("photorealistic-rendering-using-opencl_amd._capi")
-    assert set(NEW_API) <= {n for n, _, _ in capi.PRT_API}
-    assert C.sizeof(capi.TemporalResponse) == 16
-    lib = os.path.join(PKG, "libprt.so")
-    if not os.path.exists(lib):
-        import __graft_entry__ as ge
-        ge.build()
-    dll = capi.load_library()                                            # (binds every prototype of PRT_API; torch's HIP runtime first)
-    for name in NEW_API:
-        assert hasattr(dll, name), name
+    assert C.sizeof(_pkg()._capi.TemporalResponse) == 16
     for name in ("set_temporal_response", "read_response", "read_records_response"):
         assert callable(getattr(_pkg().Renderer, name)), name
 
@@ -478,8 +464,6 @@ def test_step_of_the_light_on_the_mirror():
     assert np.mean(share[4:STEP_FRAME]) <= 0.05, share
 
 
-
-
 # ---- on the GPU --------------------------------------------------------------------------------------------------------------------------------
 
 def _ctx(prt):
@@ -623,7 +607,6 @@ def test_whole_frame_equals_records(prt, motion):
     """prt_denoise_temporal with the setting on gives the bits of prt_denoise_records_temporal on the exported records of the same frames;
     with prt_set_motion on, after a prt_update_primitives that moves the light quad between the frames"""
     import torch
-    from test_update_primitives import meshes_of, move_quad
     W, H = 64, 48
     resp = dict(fast_cap=3, radius=2, k=1.5)
     scene, cfg, r = _scene_ctx(prt, "cornell_quadlight.json", W, H, response=resp)

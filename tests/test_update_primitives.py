@@ -3,27 +3,23 @@ csrc/hip/pt_prims.h / .hip, the primitive-motion instances of the guide kernels 
 
 CPU tests run the bodies of pt_prims.h on the host (tests/emu/prims_emu.cpp) against a float32 numpy mirror, byte for byte.  GPU tests: a render
 after an update equals the CPU oracle on the moved scene and a fresh context that uploads it; refusals and the lifetime; the motion plane
-against test_denoise's float64 Caster, extended by the primitives' previous pose; the per-kind and the snapshot rule; the plumbing; and a
+against the float64 Caster of tests/mirrors.py, extended by the primitives' previous pose; the per-kind and the snapshot rule; the plumbing; and a
 sphere that approaches the camera, whose temporal history follows it only with the plane."""
 import ctypes as C
 import importlib
 import json
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import PKG_NAME, ROOT, VARIANTS, variant_camera, variant_config
-from test_denoise import MAT_COND, MAT_DIEL, MAT_ROUGH_COND, MAT_ROUGH_DIEL
-from test_motion import D_BOUND as TRI_D_BOUND
-from test_motion import MotionCaster, _bits, _point, temporal_ref_motion, _mirror_history
-from test_refit import deform
-from test_temporal import camera_basis, centre_dirs, project
-from support import assert_same_render, bytes_flat as _bytes, pkg as _pkg, rodrigues as _rodrigues, to_device
+from conftest import PKG_NAME, ROOT
+from cases import Case, _cmp, deform, desc_with, meshes_of, move_quad, move_sdf, move_sphere, TILT
+from mirrors import (camera_basis, centre_dirs, D_BOUND as TRI_D_BOUND, MAT_COND, MAT_DIEL, MAT_ROUGH_COND, MAT_ROUGH_DIEL, _mirror_history,
+                     MotionCaster, _point, project, temporal_ref_motion)
+from support import assert_api, assert_same_render, bits as _bits, bytes_flat as _bytes, pkg as _pkg, to_device, variant_case
 
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
 
 PKG = os.path.join(ROOT, PKG_NAME)
 NEW_API = ("prt_update_primitives", "prt_update_primitives_device")
@@ -35,20 +31,8 @@ NAN, INF = f32(np.nan), f32(np.inf)
 # ---- no GPU: the API ---------------------------------------------------------------------------------------------------------------------------------
 
 def test_api_is_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "prt.h")) as f:
-        header = f.read()
-    for name in NEW_API:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+    header = assert_api(NEW_API)
     assert "What still does not follow: spheres" not in header and "stays prt_upload_scene's job" not in header
-    capi = importlib.import_module(PKG_NAME + "._capi")
-    assert set(NEW_API) <= {n for n, _, _ in capi.PRT_API}
-    lib = os.path.join(PKG, "libprt.so")
-    if not os.path.exists(lib):
-        import __graft_entry__ as ge
-        ge.build()
-    dll = C.CDLL(lib)
-    for name in NEW_API:
-        assert hasattr(dll, name), name
     assert callable(getattr(_pkg().Renderer, "update_primitives"))
 
 
@@ -300,49 +284,6 @@ def test_pack_kernel_has_no_scratch():
 
 # ---- moved scenes ----------------------------------------------------------------------------------------------------------------------------------------
 
-def meshes_of(desc):
-    import prims_api
-    n = int(desc.object_count[7])
-    if not n:
-        return np.zeros(0, dtype=prims_api.MESH_DTYPE)
-    return np.frombuffer((C.c_uint8 * (prims_api.MESH_BYTES * n)).from_address(desc.meshes), dtype=prims_api.MESH_DTYPE).copy()
-
-
-def desc_with(prt, desc, meshes=None, **fields):
-    d = prt.SceneDesc.from_buffer_copy(bytes(desc))
-    d._keep = [meshes]
-    if meshes is not None:
-        d.meshes = meshes.ctypes.data
-    for k, v in fields.items():
-        if isinstance(v, np.ndarray):
-            d._keep.append(v)
-            v = v.ctypes.data_as(C.c_void_p)
-        setattr(d, k, v)
-    return d
-
-
-def move_sphere(m, i, dpos=(0, 0, 0), dr=0.0):
-    m["pos"][i, :3] = (m["pos"][i, :3].astype(np.float64) + dpos).astype(f32)
-    m["joker"][i, 0] = f32(m["joker"][i, 0] + dr)
-
-
-def move_sdf(m, i, dpos):
-    m["pos"][i, :3] = (m["pos"][i, :3].astype(np.float64) + dpos).astype(f32)
-
-
-def move_quad(m, i, dpos=(0, 0, 0), axis=(0.3, 1.0, 0.2), ang=0.0, scale=1.0):
-    j = m["joker"][i].astype(np.float64)
-    j[0:3] += dpos
-    for k in (3, 6, 9):
-        j[k:k + 3] = _rodrigues(j[k:k + 3], axis, ang)
-    j[3:9] *= scale
-    j[12] *= scale * scale
-    m["joker"][i] = j.astype(f32)
-
-
-TILT = (0.3, 1.0, 0.2)
-
-
 def moves_mixed(m, which="B"):
     """cornell_mixed: 4 spheres (0 the light, 1 a mirror, 2 glass, 3 rough glass), quads 4 .. 9 (4 the floor, 7 the back wall)"""
     s = 1.0 if which == "B" else -0.6
@@ -397,12 +338,7 @@ class Moved:
                 self.scene = prt.HostScene(_prims_only_text(), text=True)
                 self.cfg, self.cam, self.env = self.scene.config(), prt.default_camera(W, H), prt.make_sky(64, 32)
             else:
-                scene_json, phase, use_env = VARIANTS[name]
-                self.scene = prt.HostScene(scene_json)
-                self.cfg = variant_config(self.scene, name)
-                self.cfg.phase_function = phase
-                self.cam = variant_camera(prt, name, W, H)
-                self.env = prt.make_sky(64, 32) if use_env else None
+                self.scene, self.cfg, self.cam, self.env = variant_case(prt, name, W, H)
             self.desc = self.scene.desc
             self.m0 = meshes_of(self.desc)
             self.mA, self.mB = self.m0.copy(), self.m0.copy()
@@ -598,7 +534,6 @@ def test_count_zero_on_a_scene_without_primitives(prt):
 
 @pytest.mark.gpu
 def test_lifetime(prt, oracle):
-    from test_refit import Case
     sc = Moved(prt, "cornell_mixed")
     r = sc.context()
     r.render_frames(prt.seed_pairs(FRAMES))
@@ -652,7 +587,7 @@ def _delta(tb):
 
 
 class PrimCaster(MotionCaster):
-    """test_motion's MotionCaster on the CURRENT scene (moved primitives, given vertices), extended by the primitives' previous pose: plane()
+    """mirrors.MotionCaster on the CURRENT scene (moved primitives, given vertices), extended by the primitives' previous pose: plane()
     is prt.h's {D, m} of the pinhole centre rays in float64.  sphere: c_prev + (p - c) r_prev / r - p; quad: through (a, b)"""
 
     def __init__(self, prt, sc_desc, cfg, m_cur, m_prev, v_cur, v_prev):
@@ -1138,7 +1073,6 @@ def test_history_follows_the_sphere_on_the_device(prt):
     plane, to a mirror fed with the device's own inputs and history: n and the integrated colour within 1e-4, as the card test of test_motion
     (relative to the largest colour in the pixel's reprojection footprint: _footprint_scale says why).
     Figures (MI355X, 64x48, step 0.45): see DESIGN.md s4 "Moving primitives"."""
-    from test_motion import _cmp
     ap = Approach(prt)
     seeds = prt.seed_pairs(2 * max(ap.cfg.max_bounces, 8) + 64)
     hist = {}

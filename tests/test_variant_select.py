@@ -7,13 +7,11 @@ functions of the instance files (one Python function per launch_set_* function, 
 the table: a row or a branch that changes in pt_variant.h fails here until this file is changed with it, on purpose."""
 import itertools
 import os
-import sys
 
 import pytest
 
 from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+import support                          # noqa: F401  (its import puts tests/emu, where emu_api lives, on the path)
 
 # include/prt_types.h
 LIGHT, DIFF, COND, DIEL, COAT, ROUGH_COND, ROUGH_DIEL = 1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4, 1 << 10, 1 << 11
